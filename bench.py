@@ -53,7 +53,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # before the HIP runtime starts: see convnet_amd/__init__.py (streams share hardware queues)
 
 PEAK_FP32_MATRIX_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 64 FLOP/clk/SIMD @ 2.4 GHz
 PEAK_BF16_MATRIX_TFLOPS = 2500.0  # dense v_mfma_f32_32x32x16_bf16: 1024 FLOP/clk/SIMD
@@ -338,6 +337,33 @@ def ref_host_leg(args, dp=False, defer=True):
         return {"value": None, "note": f"failed: {e!r}"}
 
 
+DUMP_SAMPLE = 1 << 22     # --dump-outputs: a flat buffer longer than this is written as a fixed sample of this many entries
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(net, error, out_dir):
+    """--dump-outputs DIR: what the timed path's last TrainOneBatch left for its caller, one float32 / float64 .npy per array:
+    `parameters` (after the update) and `grad_parameters` (that step's gradients) — the net's flat buffers, sampled at the same
+    seeded, sorted positions when longer than DUMP_SAMPLE — `state_<layer>` (each output layer's state: the softmax
+    probabilities of the step's batch) and `error` (TrainOneBatch's return value, when it is not None)."""
+    import numpy as np
+    params = net.parameters_.ToNumpy().reshape(-1)
+    grads = net.grad_parameters_.ToNumpy().reshape(-1)
+    idx = slice(None)
+    if params.size > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(params.size, DUMP_SAMPLE, replace=False))
+    arrays = {"parameters": params[idx].astype(np.float32), "grad_parameters": grads[idx].astype(np.float32)}
+    for l in net.output_layers_:
+        arrays[f"state_{l.GetName()}"] = l.GetState().ToNumpy().astype(np.float32)
+    if error is not None:
+        arrays["error"] = np.asarray(error, dtype=np.float64).reshape(-1)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed {DUMP_LIMIT_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset): become the launcher — N ranks of this same
     command under torch.distributed.run on 127.0.0.1, one per GPU; rank 0 of the children prints the ONE JSON line on our stdout."""
@@ -414,6 +440,9 @@ def main():
     ap.add_argument("--no-ref-host", action="store_true",
                     help="skip the `ref_host` leg (the reference's own unmodified C++ ConvNet::TrainOneBatch loop linked to this library, "
                          "tools/ref_host_bench.py, timed in a child process after the product run; rank 0, 1 GPU only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (parameters, gradients, output probabilities) "
+                         "as DIR/<name>.npy (rank 0; inputs and initial parameters are seeded, so two builds compare output for output)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -503,17 +532,20 @@ def main():
     # every step carries them (18.9 vs 18.3 ms measured).
     timer_every = max(1, args.timer_every)
     timed_steps = 0
+    error = None
     t0 = time.perf_counter()
     for i in range(args.steps):
         on = (not args.no_kernel_timers) and i % timer_every == 0
         _lib.profile_enable(on)
         timed_steps += int(on)
-        net.TrainOneBatch()
+        error = net.TrainOneBatch()
     dt_enqueue = time.perf_counter() - t0   # host time to enqueue the K steps (launches are asynchronous)
     sync_all()
     dt = time.perf_counter() - t0
     _lib.profile_enable(False)
     prof = _lib.profile_report()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(net, error, args.dump_outputs)   # before the legs below train the same net further
 
     def max_over_ranks(x):
         if not dist.is_initialized():

@@ -10,23 +10,11 @@ Layout:
   convnet.py      ConvNet driver (src/convnet.cc): build/sort/alloc, Fprop/Bprop/TrainOneBatch
   data_parallel.py  RCCL gradient exchange (replaces the MPI Accumulate/Broadcast of convnet.cc:407-450)
 """
-import os as _os
-
 # A training step drives up to three HIP streams of its own (compute, weight gradients + optimizer steps, gradient exchange) and
-# RCCL adds its internal ones.  The HIP runtime multiplexes every stream of a process onto GPU_MAX_HW_QUEUES hardware queues
-# (default 4); two streams that land on one queue run strictly one after the other.  Measured on the MI355X with a 1-rank exchange:
-# 12.1 ms per AlexNet step at the default, 11.3 ms with 8 queues (11.1 ms without the exchange) — the "0.7-0.8 ms a 1-rank exchange
-# costs" of round 2 was the second stream sharing a queue with the first.  Must be in the environment before the HIP runtime
-# initialises (the first device call), so it is set at package import; an explicit setting wins.  C/C++ hosts: INTEGRATION.md §4.
-if "GPU_MAX_HW_QUEUES" not in _os.environ:
-    import sys as _sys
-    _t = _sys.modules.get("torch")
-    if _t is not None and _t.cuda.is_initialized():
-        # too late: the HIP runtime read the variable when it initialised (import convnet_amd before the first device call, or export it)
-        import warnings as _warnings
-        _warnings.warn("convnet_amd imported after the HIP runtime initialised: GPU_MAX_HW_QUEUES stays at the runtime's default (4); "
-                       "the second stream of the training step may serialise behind the first (export GPU_MAX_HW_QUEUES=8)")
-    else:
-        _os.environ["GPU_MAX_HW_QUEUES"] = "8"
+# RCCL adds its internal ones.  The HIP runtime multiplexes every stream of a process onto GPU_MAX_HW_QUEUES hardware queues, and
+# two streams that land on one queue run strictly one after the other.  The package leaves that setting to the environment: the
+# hardware queues of a card are shared by every process on it, so raising the count is the machine's decision, not a library's.
+# Measured on the MI355X: without a gradient exchange the queue count is neutral for the AlexNet step; with a 1-rank exchange on
+# 4 queues the second stream shared the first one's queue (12.1 ms per step instead of 11.3).  C/C++ hosts: INTEGRATION.md §4.
 
 __version__ = "0.1"

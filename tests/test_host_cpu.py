@@ -1,5 +1,6 @@
 """CPU: host logic that needs no GPU — the pbtxt reader, the model zoo against the reference's own
-model files (when mounted), graph building / sizing / parameter layout, optimizer schedules."""
+model files (their signatures, stored under tests/golden), graph building / sizing / parameter layout, optimizer schedules."""
+import json
 import math
 import os
 
@@ -9,7 +10,23 @@ from convnet_amd import models, pbtxt
 from convnet_amd.convnet import ConvNet
 from convnet_amd.optimizer import SGDOptimizer
 
-REF = "/root/reference/examples"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+# the reference's example nets (paths under its examples/) and the config messages convnet_amd/pbtxt.py restates:
+# tests/golden/make_reference_fixtures.py stores what the tests below compare against
+REF_MODELS = {"imagenet/CLS_net_20140621074703.pbtxt": models.alexnet, "mnist-conv/net.pbtxt": models.mnist_conv,
+              "imagenet/CLS_net_20140801232522.pbtxt": models.alexnet_nin}
+SCHEMA_MESSAGES = ("Layer", "Edge", "Optimizer", "Model", "LayerSlice")
+
+
+def model_signature(m):
+    """Every layer / edge / optimizer field of a parsed model the model zoo restates, as JSON-ready lists."""
+    out = [[l.name, l.num_channels, l.activation, l.dropprob, l.image_size_y, l.image_size_x] for l in m.layer]
+    for e in m.edge:
+        w, b = e.weight_optimizer, e.bias_optimizer
+        out.append([e.source, e.dest, e.edge_type, e.kernel_size, e.stride, e.padding, e.shared_bias, e.initialization, e.init_wt,
+                    e.init_bias, w.epsilon, w.final_momentum, w.momentum_transition_timescale, w.l2_decay, w.weight_norm_limit, w.weight_norm_constraint,
+                    b.epsilon, b.final_momentum, b.l2_decay, e.add_scale, e.pow_scale, e.frac_of_filters_response_norm])
+    return out
 
 
 def test_pbtxt_reader_defaults_presence_and_errors():
@@ -34,21 +51,11 @@ def test_pbtxt_reader_defaults_presence_and_errors():
     assert o.epsilon == 0.5 and o.l2_decay == 0.5
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted")
-@pytest.mark.parametrize("gen,path", [(models.alexnet, "imagenet/CLS_net_20140621074703.pbtxt"), (models.mnist_conv, "mnist-conv/net.pbtxt"),
-                                      (models.alexnet_nin, "imagenet/CLS_net_20140801232522.pbtxt")])
+@pytest.mark.parametrize("gen,path", [(gen, path) for path, gen in REF_MODELS.items()])
 def test_generated_models_equal_reference_pbtxt(gen, path):
-    ref, mine = pbtxt.read(os.path.join(REF, path)), pbtxt.parse(gen())
-
-    def sig(m):
-        out = [(l.name, l.num_channels, l.activation, l.dropprob, l.image_size_y, l.image_size_x) for l in m.layer]
-        for e in m.edge:
-            w, b = e.weight_optimizer, e.bias_optimizer
-            out.append((e.source, e.dest, e.edge_type, e.kernel_size, e.stride, e.padding, e.shared_bias, e.initialization, e.init_wt,
-                        e.init_bias, w.epsilon, w.final_momentum, w.momentum_transition_timescale, w.l2_decay, w.weight_norm_limit, w.weight_norm_constraint,
-                        b.epsilon, b.final_momentum, b.l2_decay, e.add_scale, e.pow_scale, e.frac_of_filters_response_norm))
-        return out
-    assert sig(ref) == sig(mine)
+    with open(os.path.join(GOLDEN, "ref_model_signatures.json")) as f:
+        ref = json.load(f)[path]
+    assert ref == model_signature(pbtxt.parse(gen()))
 
 
 def test_alexnet_graph_sizes_params_and_work_match_the_survey():
@@ -99,8 +106,8 @@ def test_sgd_schedules():
 
 def test_hdf5_io_layout_and_reference_written_file(tmp_path):
     """The HDF5 layer without a GPU: dataset shape convention (a column-major (rows, cols) matrix is a
-    row-major (cols, rows) dataset, util.cc:128-175), int attributes, missing-attribute default, size mismatch; and, when
-    the reference tree is mounted, a file the reference's own tools wrote (examples/imagenet/pixel_mean.h5)."""
+    row-major (cols, rows) dataset, util.cc:128-175), int attributes, missing-attribute default, size mismatch; and a file
+    the reference's own tools wrote (its examples/imagenet/pixel_mean.h5, stored as tests/golden/pixel_mean.h5)."""
     import numpy as np
     from convnet_amd import hdf5io
     p = str(tmp_path / "t.h5")
@@ -116,12 +123,10 @@ def test_hdf5_io_layout_and_reference_written_file(tmp_path):
             f.ReadHDF5CPU(11, "x:y:weight")
         with pytest.raises(KeyError):
             f.ReadHDF5Shape("nope")
-    ref = os.path.join(REF, "imagenet/pixel_mean.h5")
-    if os.path.exists(ref):
-        with hdf5io.File(ref) as f:
-            assert f.ReadHDF5Shape("pixel_mean") == (1, 3)
-            assert np.allclose(f.ReadHDF5CPU(3, "pixel_mean"), [122.77497, 115.91181, 102.984184], rtol=1e-6)
-            assert np.allclose(f.ReadHDF5CPU(3, "pixel_std"), [70.58011, 68.60053, 72.02416], rtol=1e-6)
+    with hdf5io.File(os.path.join(GOLDEN, "pixel_mean.h5")) as f:
+        assert f.ReadHDF5Shape("pixel_mean") == (1, 3)
+        assert np.allclose(f.ReadHDF5CPU(3, "pixel_mean"), [122.77497, 115.91181, 102.984184], rtol=1e-6)
+        assert np.allclose(f.ReadHDF5CPU(3, "pixel_std"), [70.58011, 68.60053, 72.02416], rtol=1e-6)
 
 
 def test_check_reduce_learning_rate_follows_the_reference_rule():
@@ -242,24 +247,24 @@ def test_pmc_traffic_summary_is_reproducible_from_the_committed_counter_files():
     assert dom["launches"] == 40 and 3.0e8 < dom["traffic_bytes"] < 4.0e8
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/proto/convnet_config.proto"), reason="reference tree not mounted")
 def test_pbtxt_schema_matches_the_reference_proto_field_for_field():
     """convnet_amd/pbtxt.py restates proto/convnet_config.proto by hand: every field of Layer / Edge / Optimizer / Model (and
-    LayerSlice) must exist with the proto's default, so a reference pbtxt means the same thing to both hosts.  The proto is
-    parsed with the same reader the seam build uses to generate its C++ config classes (oracle/seam/gen_config_pb.py)."""
+    LayerSlice) must exist with the proto's default, so a reference pbtxt means the same thing to both hosts.  The proto's fields
+    and enums are stored in tests/golden/ref_config_schema.json, parsed with the same reader the seam build uses to generate its
+    C++ config classes (oracle/seam/gen_config_pb.py; tests/golden/make_reference_fixtures.py)."""
     import importlib.util
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     spec = importlib.util.spec_from_file_location("gen_config_pb", os.path.join(root, "oracle", "seam", "gen_config_pb.py"))
     gen = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(gen)
     from convnet_amd import pbtxt
-    with open("/root/reference/proto/convnet_config.proto") as f:
-        msgs = {m.name: m for m in gen.flatten(gen.parse(f.read()))}
+    with open(os.path.join(GOLDEN, "ref_config_schema.json")) as f:
+        schema = json.load(f)
+    enums = schema["enums"]
     out_of_scope = {"Model": {"subnet", "train_dataset", "valid_dataset"}}   # sub-net merging and dataset configs: not on the path
     for name, cls in (("Layer", pbtxt.Layer), ("Edge", pbtxt.Edge), ("Optimizer", pbtxt.Optimizer), ("Model", pbtxt.Model),
                       ("LayerSlice", pbtxt.LayerSlice)):
-        proto = {f["name"]: f for f in msgs[name].fields}
-        enums = {e: [v for v, _ in vals] for m in msgs.values() for e, vals in m.enums}
+        proto = {f["name"]: f for f in schema["messages"][name]}
         assert set(proto) - set(cls.FIELDS) == out_of_scope.get(name, set()), name
         assert not set(cls.FIELDS) - set(proto), name
         for key, mine in cls.FIELDS.items():
