@@ -147,6 +147,12 @@ def _load():
     sig("convOutpGemm", None, M, M, M, S, S, S, ConvDesc, F, F)
     sig("convOutp", None, M, M, M, S, S, S, ConvDesc, I, I, F, F)
     sig("convUpBiasAct", None, M, M, M, M, S, S, S, ConvDesc, F, I)
+    # locally connected layers (csrc/local_conv.hip)
+    for n in ("localUp", "localDown", "localUpGemm", "localDownGemm"):
+        sig(n, None, M, M, M, S, S, S, ConvDesc, F)
+    for n in ("localOutp", "localOutpGemm"):
+        sig(n, None, M, M, M, S, S, S, ConvDesc, F, F)
+    sig("localUpBiasAct", None, M, M, M, M, S, S, S, ConvDesc, F, I)
     sig("convDownMask", None, M, M, M, M, S, S, S, ConvDesc, F, F)
     sig("dotMask", I, M, M, M, M, F, F, F)
     sig("MaxPoolUndoRelu", None, M, M, M, M, S, S, ConvDesc, F)

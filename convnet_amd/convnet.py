@@ -21,7 +21,7 @@ from collections import deque
 import torch
 
 from . import pbtxt
-from .edge import ConvEdge, Edge, EdgeWithWeight, FCEdge, ResponseNormEdge
+from .edge import ConvEdge, Edge, EdgeWithWeight, FCEdge, LocalEdge, ResponseNormEdge
 from .layer import Layer, SoftmaxLayer
 from .matrix import Matrix
 from .trainer import TrainLoopMixin
@@ -233,6 +233,8 @@ class ConvNet(TrainLoopMixin):
         e = l.incoming_edge_[0]
         if isinstance(e, ConvEdge):
             return e.has_no_bias_ or e.shared_bias_
+        if isinstance(e, LocalEdge):
+            return True            # localUpBiasAct: the (per-column) bias and the ReLU in the kernel's epilogue
         if isinstance(e, ResponseNormEdge):
             return l.is_relu       # the ReLU of an rnorm-fed layer rides in the rnorm kernel; other activations do not
         return isinstance(e, FCEdge)

@@ -2,7 +2,7 @@
 maxpool_edge.cc, avgpool_edge.cc, response_norm_edge.cc: same class names, same
 ComputeUp / ComputeDown / ComputeOuter / UpdateWeights contract, same parameter slicing.
 
-Local / one-to-one / up-down-sample / RGB->YUV edges are out of hot-path scope.
+Up-down-sample / RGB->YUV edges are out of hot-path scope.
 ``fused`` selects the library's fused entry points (conv+bias+ReLU epilogue, one-pass bias
 gradient); the unfused path issues exactly the reference's Matrix-call sequence.
 """
@@ -25,7 +25,7 @@ class Edge:
     def ChooseEdgeClass(edge_config):
         # src/edge.cc:19-66
         table = {"FC": FCEdge, "CONVOLUTIONAL": ConvEdge, "MAXPOOL": MaxPoolEdge, "AVERAGE_POOL": AvgPoolEdge,
-                 "RESPONSE_NORM": ResponseNormEdge, "CONV_ONETOONE": ConvOneToOneEdge}
+                 "RESPONSE_NORM": ResponseNormEdge, "CONV_ONETOONE": ConvOneToOneEdge, "LOCAL": LocalEdge}
         if edge_config.edge_type not in table:
             raise SystemExit(f"Error: Undefined edge type {edge_config.edge_type} (out of hot-path scope).")
         return table[edge_config.edge_type](edge_config)
@@ -471,6 +471,109 @@ class ConvEdge(EdgeWithWeight):
                     db_temp.SumRows(db, scale_targets, self.scale_gradients_ / batch_size)
             else:
                 deriv_output.SumRows(db, scale_targets, self.scale_gradients_ / batch_size)
+        self.IncrementNumGradsReceived()
+
+
+class LocalEdge(EdgeWithWeight):
+    """src/local_edge.{h,cc}: a locally connected layer — a convolution whose every module (output pixel) has its own filter bank.
+
+    Parameter slice (F, input_size + bias_locs), exactly as LocalEdge::SetMemory lays it out:
+    * weights: the first input_size = Kx*Ky*C*My*Mx columns, Shape4D (F, Kx, Ky, C*My*Mx); module m = my*Mx + mx owns the F*K floats
+      at m*F*K (K = Kx*Ky*C), element (f, c, ky, kx) of a block at f + F*(kx + Kx*(ky + Ky*c)) — a conv bank per module;
+    * bias: the next bias_locs = My*Mx columns, i.e. an (F, M) block, read as (1, F*M): ComputeUp adds element j to output column j
+      (AddRowVec), ComputeOuter sums deriv_output over the images into it.  There is no shared bias for local edges.
+    ComputeUp / ComputeDown / ComputeOuter issue the reference's Matrix calls (LocalUp / LocalDown / LocalOutp, src/matrix.cc:859-893);
+    ``fuse_relu`` selects localUpBiasAct (bias and ReLU in the kernel's epilogue)."""
+
+    def __init__(self, c):
+        super().__init__(c)
+        self.conv_desc_ = Edge.GetConvDesc(c)
+
+    def GetConvDesc(self):
+        return self.conv_desc_
+
+    def SetTiedTo(self, e):
+        super().SetTiedTo(e)
+        if not isinstance(e, LocalEdge):
+            raise SystemExit(f"Error: Edge {self.GetName()} cannot be tied to edge {e.GetName()} which is not of the same type.")
+        self.conv_desc_ = e.GetConvDesc().copy()
+
+    def SetImageSize(self, y, x, t):
+        super().SetImageSize(y, x, t)
+        d = self.conv_desc_
+        d.num_input_channels = self.num_input_channels_
+        d.num_output_channels = self.num_output_channels_
+        self.num_modules_y_, self.num_modules_x_, self.num_modules_t_ = Edge.GetNumModules(d, y, x, t)
+        if t != 1:
+            raise SystemExit("3-D locally connected layers are out of hot-path scope")
+
+    def GetDescription(self):
+        # src/local_edge.cc:GetDescription (Edge::GetDescription(conv_desc): kernel y-x-input channels : output channels)
+        d = self.conv_desc_
+        return (f"{self.name_}  Local Kernel: {d.kernel_size_y}-{d.kernel_size_x}-{d.num_input_channels} : {d.num_output_channels}"
+                f" Layer: {self.image_size_y_}-{self.image_size_x_} : {self.num_modules_y_}-{self.num_modules_x_}")
+
+    def _num_modules(self):
+        return self.num_modules_y_ * self.num_modules_x_ * self.num_modules_t_
+
+    def _input_size(self):
+        d = self.conv_desc_
+        return d.kernel_size_x * d.kernel_size_y * d.kernel_size_t * d.num_input_channels * self._num_modules()
+
+    def GetParameterMemoryRequirement(self):
+        if self.is_tied_:
+            return 0
+        return self.conv_desc_.num_output_channels * (self._input_size() + (0 if self.has_no_bias_ else self._num_modules()))
+
+    def SetMemory(self, p):
+        if self.is_tied_:
+            return
+        d = self.conv_desc_
+        input_size, bias_locs = self._input_size(), self._num_modules()
+        p.Reshape(d.num_output_channels, -1)
+        p.GetSlice(self.weights_, 0, input_size)
+        self.weights_.SetShape4D(d.num_output_channels, d.kernel_size_x, d.kernel_size_y,
+                                 d.num_input_channels * self.num_modules_y_ * self.num_modules_x_)
+        if not self.has_no_bias_:
+            p.GetSlice(self.bias_, input_size, input_size + bias_locs)
+            self.bias_.Reshape(1, -1)
+
+    def SetGradMemory(self, p, hist=None):
+        if self.is_tied_:
+            return
+        d = self.conv_desc_
+        input_size, bias_locs = self._input_size(), self._num_modules()
+        p.Reshape(d.num_output_channels, -1)
+        p.GetSlice(self.grad_weights_, 0, input_size)
+        self.grad_weights_.SetShape4D_like(self.weights_)
+        if not self.has_no_bias_:
+            p.GetSlice(self.grad_bias_, input_size, input_size + bias_locs)
+            self.grad_bias_.Reshape(1, -1)
+        self._alloc_optimizers(d.num_output_channels, input_size, bias_locs, hist)
+
+    def ComputeUp(self, input, output, overwrite, train=True, fuse_relu=None):
+        w = self.tied_edge_.GetWeight() if self.is_tied_ else self.weights_
+        scale_targets = 0 if overwrite else 1
+        b = None if self.has_no_bias_ else (self.tied_edge_.GetBias() if self.is_tied_ else self.bias_)
+        if fuse_relu is not None:
+            Matrix.LocalUpBiasAct(input, w, b, output, self.conv_desc_, scale_targets, fuse_relu)
+            return
+        Matrix.LocalUp(input, w, output, self.conv_desc_, scale_targets)
+        if b is not None:
+            output.AddRowVec(b)
+
+    def ComputeDown(self, deriv_output, input, output, deriv_input, overwrite):
+        w = self.tied_edge_.GetWeight() if self.is_tied_ else self.weights_
+        Matrix.LocalDown(deriv_output, w, deriv_input, self.conv_desc_, 0 if overwrite else 1)
+
+    def ComputeOuter(self, input, deriv_output):
+        dw = self.tied_edge_.GetGradWeight() if self.is_tied_ else self.grad_weights_
+        batch_size = input.GetRows()
+        scale_targets = 1 if self.GetNumGradsReceived() > 0 else 0
+        Matrix.LocalOutp(input, deriv_output, dw, self.conv_desc_, scale_targets, self.scale_gradients_ / batch_size)
+        if not self.has_no_bias_:
+            db = self.tied_edge_.GetGradBias() if self.is_tied_ else self.grad_bias_
+            deriv_output.SumRows(db, scale_targets, self.scale_gradients_ / batch_size)
         self.IncrementNumGradsReceived()
 
 

@@ -451,6 +451,30 @@ class Matrix:
                          ctypes.byref(deriv_output.shape_), ctypes.byref(dw.shape_), conv_desc, float(scale_targets),
                          float(scale_outputs))
 
+    # ---- locally connected layers: src/matrix.cc:859-893 (the *Gemm names, as a USE_GEMM build of the reference calls them) ----
+    @staticmethod
+    def LocalUp(input, w, output, conv_desc, scale_targets):
+        lib.localUpGemm(input.GetMat(), w.GetMat(), output.GetMat(), ctypes.byref(input.shape_), ctypes.byref(w.shape_),
+                        ctypes.byref(output.shape_), conv_desc, float(scale_targets))
+
+    @staticmethod
+    def LocalUpBiasAct(input, w, bias, output, conv_desc, scale_targets, relu):
+        """LocalUp + AddRowVec(bias) [+ ReLU] in one kernel (include/convnet_hip.h: localUpBiasAct)."""
+        lib.localUpBiasAct(input.GetMat(), w.GetMat(), bias.GetMat() if bias is not None else None, output.GetMat(),
+                           ctypes.byref(input.shape_), ctypes.byref(w.shape_), ctypes.byref(output.shape_), conv_desc,
+                           float(scale_targets), int(relu))
+
+    @staticmethod
+    def LocalDown(deriv_output, w, deriv_input, conv_desc, scale_targets):
+        lib.localDownGemm(deriv_output.GetMat(), w.GetMat(), deriv_input.GetMat(), ctypes.byref(deriv_output.shape_),
+                          ctypes.byref(w.shape_), ctypes.byref(deriv_input.shape_), conv_desc, float(scale_targets))
+
+    @staticmethod
+    def LocalOutp(input, deriv_output, dw, conv_desc, scale_targets, scale_outputs):
+        lib.localOutpGemm(input.GetMat(), deriv_output.GetMat(), dw.GetMat(), ctypes.byref(input.shape_),
+                          ctypes.byref(deriv_output.shape_), ctypes.byref(dw.shape_), conv_desc, float(scale_targets),
+                          float(scale_outputs))
+
     @staticmethod
     def ConvMaxPool(input, output, conv_desc):
         lib.MaxPoolGemm(input.GetMat(), output.GetMat(), ctypes.byref(input.shape_), ctypes.byref(output.shape_), conv_desc, 0.0, 1.0)

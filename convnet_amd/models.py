@@ -6,6 +6,7 @@ text so they can also be written to disk and fed to the reference's own binaries
                      conv5s2/256 -> max -> rnorm -> conv3p1/384 -> conv3p1/384 -> conv3/256 -> max ->
                      fc4096(drop .4) -> fc4096(drop .4) -> softmax1000; 62,357,608 parameters.
 * ``mnist_conv()`` — examples/mnist-conv/net.pbtxt (configs[0]/[1]).
+* ``cifar_local()`` — CIFAR-10 "conv + local" (two locally connected layers, LocalEdge).
 * ``vgg()``        — a VGG-style stack of 3x3 s1 p1 convs (configs[4]; no such pbtxt exists in the
                      reference).
 tests/test_models.py checks the first two against the reference's files when they are mounted.
@@ -158,6 +159,31 @@ def lenet5(grad_check=False):
     return s
 
 
+def _local(src, dst, k, stride=1, pad=0, eps=0.01, mom=0.9, tau=2000, l2=0.0005, init_wt=1.0, init_bias=0.0, grad_check=""):
+    """LOCAL (locally connected) edge: a conv geometry with one filter bank per module and one bias per (filter, module)."""
+    return (f'edge {{\n  source: "{src}"\n  dest: "{dst}"\n  edge_type: LOCAL\n  kernel_size: {k}\n  stride : {stride}\n'
+            f"  padding: {pad}\n  initialization: DENSE_UNIFORM_SQRT_FAN_IN\n  init_wt: {init_wt}\n"
+            f"  init_bias: {init_bias}\n" + _OPT_W.format(eps=eps, mom=mom, tau=tau, l2=l2, extra="") + grad_check + "}\n\n")
+
+
+def cifar_local(num_classes=10, grad_check=False):
+    """CIFAR-10 after cuda-convnet's "conv + local" model (layers-conv-local): 24x24x3 crops -> conv5p2/64 -> max3s2 -> rnorm ->
+    conv5p2/64 -> rnorm -> max3s2 -> local3p1/64 -> local3p1/32 -> fc10 -> softmax.  With this code base's pooling arithmetic
+    ((size - 3) // 2 + 1) the images are 24 -> 11 -> 5, so both local layers run on 5x5 modules: 64 and 32 filters of 3x3x64."""
+    gc = _gc(grad_check)
+    R = "RECTIFIED_LINEAR"
+    s = _header("cifar_local")
+    s += _layer("input", 3, size=24)
+    s += _layer("conv1", 64, R) + _layer("pool1", 64) + _layer("rnorm1", 64)
+    s += _layer("conv2", 64, R) + _layer("rnorm2", 64) + _layer("pool2", 64)
+    s += _layer("local3", 64, R) + _layer("local4", 32, R) + _layer("output", num_classes, "SOFTMAX")
+    s += _conv("input", "conv1", 5, 1, 2, grad_check=gc) + _pool("conv1", "pool1", 3, 2) + _rnorm("pool1", "rnorm1")
+    s += _conv("rnorm1", "conv2", 5, 1, 2, init_bias=1.0, grad_check=gc) + _rnorm("conv2", "rnorm2") + _pool("rnorm2", "pool2", 3, 2)
+    s += _local("pool2", "local3", 3, 1, 1, grad_check=gc) + _local("local3", "local4", 3, 1, 1, grad_check=gc)
+    s += _fc("local4", "output", grad_check=gc)
+    return s
+
+
 def vgg(image_size=224, num_classes=1000, widths=(64, 128, 256, 512, 512), depths=(2, 2, 3, 3, 3), dropprob=0.5):
     s = _header("vgg_style")
     s += _layer("input", 3, size=image_size)
@@ -181,10 +207,10 @@ def vgg(image_size=224, num_classes=1000, widths=(64, 128, 256, 512, 512), depth
 def count_macs(net):
     """(fwd_macs, train_macs) per image following BASELINE.md §2: train = fwd + wgrad (all weighted
     edges) + dgrad (all but edges whose source is an input layer, src/convnet.cc:370)."""
-    from .edge import ConvEdge, ConvOneToOneEdge, FCEdge
+    from .edge import ConvEdge, ConvOneToOneEdge, FCEdge, LocalEdge
     fwd = train = 0
     for e in net.edges_:
-        if isinstance(e, ConvEdge):
+        if isinstance(e, (ConvEdge, LocalEdge)):
             d = e.conv_desc_
             macs = e.num_modules_y_ * e.num_modules_x_ * d.num_output_channels * d.kernel_size_y * d.kernel_size_x * d.num_input_channels
         elif isinstance(e, ConvOneToOneEdge):     # 1x1 conv: C x F per pixel

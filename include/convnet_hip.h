@@ -224,6 +224,48 @@ void convOutp(cudamat* images, cudamat* derivs, cudamat* targets,
               ConvDesc conv_desc, int partialSumY, int partialSumX, float scaleTargets,
               float scaleOutput);
 
+/* ---- locally connected layers: cudamat_conv.cuh:14-33 and cudamat_conv_gemm.cuh:56-69 (src/local_edge.cc) -------------------------
+ * A convolution whose every module (output pixel m = my*Mx + mx, M = My*Mx) has its own filter bank.  Layouts as above; the bank is
+ * (F, Kx*Ky*C*M) column-major: module m owns the F*K floats (K = Kx*Ky*C) at offset m*F*K, and element (f, c, ky, kx) of that block sits at
+ * f + F*(kx + Kx*(ky + Ky*c)) — exactly a conv bank.  Its Shape4D is (F, Kx, Ky, C*My*Mx) (local_edge.cc SetMemory).
+ *   localUp:   targets[n, f, m] = scaleTargets*targets + sum_k W_m[f, k] * patch_m[k, n]
+ *   localDown: targets = scaleTargets*targets + the adjoint of localUp in the images
+ *   localOutp: targets = scaleTargets*targets + scaleOutput * sum_n derivs (x) patch, per module
+ * Padding (negated) and strides come from conv_desc; num_groups == 1 and the channel ranges as for convUp; kernel_size_t <= 1.  Shape
+ * mismatches abort through the same checks as convUpGemm, with filterModuleMult = M.  Both matrix paths; no atomics: bit-identical from
+ * call to call.  The plain and the *Gemm names are the same functions.
+ * REFERENCE QUIRK, not reproduced: the reference's _convUpGemm / _convDownGemm / _convOutpGemm with conv == false
+ * (cudamat_conv_gemm.cu:657, 800, 944) advance the bank pointer BEFORE the first module's GEMM, so module m uses block m + 1, the last
+ * module reads past the bank and its localOutp writes past dW (into the bias gradient that follows it in the edge's slice).  This library
+ * implements the definition above, which is also what the reference's non-GEMM localUp (filterActs) computes.
+ * localUpBiasAct (new, the analogue of convUpBiasAct): localUp, then bias element j added to output column j (the (F, M) bias slice read
+ * as (1, F*M), local_edge.cc ComputeUp: AddRowVec), then max(x, 0) when relu != 0 — bit-identical to localUp + add_row_vec
+ * [+ lower_bound_scalar(.., 0, ..)].  bias may be NULL. */
+void localUp(cudamat* images, cudamat* filters, cudamat* targets,
+             Shape4D* images_shape, Shape4D* filters_shape, Shape4D* targets_shape,
+             ConvDesc conv_desc, float scaleTargets);
+void localDown(cudamat* derivs, cudamat* filters, cudamat* targets,
+               Shape4D* derivs_shape, Shape4D* filters_shape, Shape4D* targets_shape,
+               ConvDesc conv_desc, float scaleTargets);
+void localOutp(cudamat* images, cudamat* derivs, cudamat* targets,
+               Shape4D* images_shape, Shape4D* derivs_shape, Shape4D* targets_shape,
+               ConvDesc conv_desc, float scaleTargets, float scaleOutput);
+void localUpGemm(cudamat* images, cudamat* filters, cudamat* targets,
+                Shape4D* images_shape, Shape4D* filters_shape,
+                Shape4D* targets_shape, ConvDesc conv_desc,
+                float scaleTargets);
+void localDownGemm(cudamat* derivs, cudamat* filters, cudamat* targets,
+                  Shape4D* derivs_shape, Shape4D* filters_shape,
+                  Shape4D* targets_shape, ConvDesc conv_desc,
+                  float scaleTargets);
+void localOutpGemm(cudamat* images, cudamat* derivs, cudamat* targets,
+                  Shape4D* images_shape, Shape4D* derivs_shape,
+                  Shape4D* targets_shape, ConvDesc conv_desc,
+                  float scaleTargets, float scaleOutput);
+void localUpBiasAct(cudamat* images, cudamat* filters, cudamat* bias, cudamat* targets,
+                    Shape4D* images_shape, Shape4D* filters_shape, Shape4D* targets_shape,
+                    ConvDesc conv_desc, float scaleTargets, int relu);
+
 /* ---- pooling: cudamat_conv_gemm.cuh:72-92 (and cudamat_conv.cuh:58-70) ------------------------------ */
 void MaxPoolGemm(cudamat* images, cudamat* targets, Shape4D* images_shape,
                  Shape4D* targets_shape, ConvDesc conv_desc, float scaleTargets,
