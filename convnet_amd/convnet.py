@@ -21,8 +21,8 @@ from collections import deque
 import torch
 
 from . import pbtxt
-from .edge import ConvEdge, Edge, EdgeWithWeight, FCEdge, LocalEdge, ResponseNormEdge
-from .layer import Layer, SoftmaxLayer
+from .edge import ConvEdge, Edge, EdgeWithWeight, FCEdge, LocalEdge, MaxPoolEdge, ResponseNormEdge
+from .layer import Layer, LinearLayer, ReLULayer, SoftmaxLayer
 from .matrix import Matrix
 from .trainer import TrainLoopMixin
 
@@ -118,6 +118,11 @@ class ConvNet(TrainLoopMixin):
                     e.SetDest(l)
                     e.SetOutputChannels(l.GetNumChannels())
         self.Sort()
+        for e in self.edges_:
+            if isinstance(e, MaxPoolEdge):
+                # the mask pair equals the reference's MaxPoolUndo only if backprop sees the raw maxima (edge.MaxPoolEdge)
+                d = e.GetDest()
+                e.mask_legal_ = d.dropprob_ == 0 and type(d) in (LinearLayer, ReLULayer)
         for l in self.layers_:
             if not l.incoming_edge_:
                 self.input_layers_.append(l)
@@ -348,7 +353,6 @@ class ConvNet(TrainLoopMixin):
         if not e.can_fuse_mask or e.IsBackPropBlocked() or l.store_dropout_noise_:
             return None
         scale = 1.0 / (1 - l.dropprob_) if (l.dropprob_ > 0 and l.dropout_scale_up_at_train_time_) else 1.0
-        from .edge import MaxPoolEdge
         if isinstance(e, MaxPoolEdge) and scale != 1.0:
             return None
         return scale

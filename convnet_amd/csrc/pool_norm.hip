@@ -7,6 +7,8 @@
 // read-once/write-once bytes plus L2-absorbed window overlap.
 #include <cfloat>
 #include <cstdlib>
+#include <mutex>
+#include <utility>
 
 #include "common.h"
 
@@ -985,6 +987,25 @@ inline int grid_for(size_t items) {
   return b ? (int)b : 1;
 }
 
+// The dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) belongs to the kernel, not to one launch: one instantiation serves
+// several channel counts (rnorm_undo_fast_kernel<64, 12, 24>: 73,216 B at C = 96, 66,560 B at C = 84), so the limit is only ever raised,
+// to the largest LDS any call of the kernel has asked for.  Setting it per call size would let C = 84 lower it below what a cached
+// C = 96 launch needs.  Process-wide (the attribute is), hence the lock.
+inline void rn_raise_lds_limit(const void* kernel, size_t smem) {
+  if (smem <= 64 * 1024) return;
+  static std::mutex mu;
+  static std::pair<const void*, size_t> raised[32];
+  static int count = 0;
+  std::lock_guard<std::mutex> lock(mu);
+  int i = 0;
+  while (i < count && raised[i].first != kernel) ++i;
+  if (i < count && raised[i].second >= smem) return;
+  CHIP_REQUIRE(i < 32);
+  CHIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  raised[i] = {kernel, smem};
+  if (i == count) ++count;
+}
+
 // Launch geometry of the persistent response-norm kernels: blocks per XCD = twice what its 32 CUs hold at once (the runtime's occupancy
 // figure for this kernel, block size and LDS: registers, LDS and wave slots), never more than the XCD has tiles.
 inline unsigned rn_pipe_grid(const void* kernel, unsigned tiles, size_t smem, int threads) {
@@ -994,7 +1015,7 @@ inline unsigned rn_pipe_grid(const void* kernel, unsigned tiles, size_t smem, in
   for (const Key& e : cache)
     if (e.k == kernel && e.smem == smem && e.threads == threads) n = e.n;
   if (!n) {
-    if (smem > 64 * 1024) CHIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    rn_raise_lds_limit(kernel, smem);
     CHIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, smem));
     if (n < 1) n = 1;
     static thread_local int next = 0;

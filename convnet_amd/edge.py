@@ -731,21 +731,32 @@ _POOL_MASK = os.environ.get("CONVNET_POOL_MASK", "1") != "0"   # A/B switch (too
 class MaxPoolEdge(_PoolEdge):
     """src/maxpool_edge.{h,cc}.  With the host's fused entry points on (ConvNet(fused=True) sets ``fused``) the forward pass also records
     the window masks (include/convnet_hip.h: MaxPoolMask) and the backward pass routes the derivatives from them alone — it reads neither
-    the layer's input (1.19 GB for AlexNet's pool1) nor its maxima.  Bit-identical to the reference's call pair; geometries without a mask
-    kernel, and a ComputeDown that is handed other matrices than the ComputeUp before it, take the reference's calls."""
+    the layer's input (1.19 GB for AlexNet's pool1) nor its maxima.
+    The reference's MaxPoolUndo routes a derivative to the inputs that equal the pool layer's state AS BACKPROP SEES IT, i.e. after the
+    layer's activation and dropout (src/convnet.cc:377-405, src/maxpool_edge.cc:60-65); the mask records the raw window maximum.  The two
+    agree only when the destination layer has no dropout and a linear or ReLU activation (ReLU' zeroes the derivative wherever ReLU moved
+    the maximum), so ConvNet sets ``mask_legal_`` from the destination and only then is the mask pair used; it is bit-identical to the
+    reference's call pair there.  Other destinations, geometries without a mask kernel, and a ComputeDown that is handed other matrices
+    than the ComputeUp before it take the reference's calls."""
     can_fuse_mask = True
 
     def __init__(self, c):
         super().__init__(c)
         self.fused = False
+        self.mask_legal_ = False   # set by ConvNet.BuildNet from the destination layer (see the class docstring)
         self.mask_ = None
         self.mask_for_ = None   # (input data pointer, output data pointer, batch) of the ComputeUp that wrote mask_
+        self.mask_refused_ = set()   # (batch, input size, output size) the mask kernel refused: no mask, no call from then on
+
+    def MaskEligible(self):
+        return self.fused and self.mask_legal_ and _POOL_MASK
 
     def ComputeUp(self, input, output, overwrite, train=True, fuse_relu=None):
         if not overwrite:
             raise SystemExit(" In MaxPoolEdge::ComputeUp() : some other layer is writing to this maxpool layer's output as well. Not implemented.")
         self.mask_for_ = None
-        if self.fused and train and _POOL_MASK:
+        key = (output.GetRows(), input.GetCols(), output.GetCols())
+        if train and self.MaskEligible() and key not in self.mask_refused_:
             need = (output.GetRows(), (output.GetCols() + 1) // 2)
             if self.mask_ is None or (self.mask_.GetRows(), self.mask_.GetCols()) != need:
                 self.mask_ = Matrix()
@@ -753,6 +764,8 @@ class MaxPoolEdge(_PoolEdge):
             if Matrix.ConvMaxPoolMask(input, output, self.mask_, self.conv_desc_):
                 self.mask_for_ = (input.mat_.data_device, output.mat_.data_device, output.GetRows())
                 return
+            self.mask_refused_.add(key)   # refused by geometry and batch (the alignment it also checks holds for whole layer buffers)
+            self.mask_ = None
         Matrix.ConvMaxPool(input, output, self.conv_desc_)
 
     def ComputeDown(self, deriv_output, input, output, deriv_input, overwrite, fuse_mask=None):
