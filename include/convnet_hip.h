@@ -109,7 +109,12 @@ const char* convnet_hip_version(void);
  *       - a conv FILTER operand (pre-split outside the loops, filter_planes_rt_kernel) above that range (or +-inf) saturates to
  *         +-3.3895e38 (bf16 max); an FC weight or a weight-gradient operand (split inside the loops) gives NaN like an activation.
  *       - operands below ~2^-110 in magnitude: their second / third split terms are denormals, which the matrix pipe flushes;
- *         the product then carries 8-16 instead of 24 significant bits (measured <= 2^-20 of sum|ab| at |x| ~ 2^-116).
+ *         the product then carries 8-16 instead of 24 significant bits (measured <= 2^-20 of sum|ab| at |x| ~ 2^-116 on the conv2 /
+ *         conv4 samples; up to 2^-18.2, 12 x path 0, over every output of the per-build rows, profiles/split_error_builds.txt).
+ *     Per build (tests/split_cases.py: every split kernel family, epilogue, tail-split and split-K launch): within the shared bounds
+ *     on N(0,1), wide-range and huge data except where the two paths run different launches (k order, split-K / tail plan): the
+ *     ratio of their maxima reaches 1.3 x, 2.1-2.4 x on conv3-type dgrad where path 0 splits the reduction.  Pairwise cancellation
+ *     along taps (C = 3), on reductions of K < 1000 and in the local kernels costs both paths up to 0.96 units (path 0) and 0.93 (path 1).
  * Initial value: environment CONVNET_GG_SPLIT (0/1), else 0.  May be changed between calls at any time. */
 void convnet_hip_set_matrix_path(int path);
 int convnet_hip_get_matrix_path(void);

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "prec.h"
 #include "../../convnet_amd/csrc/gather_gemm.h"   // (the .hip files are compiled one by one against the same stand-in header and linked in:
                                                   // tests/test_emulated_kernels.py)
 
@@ -420,9 +421,155 @@ static void sgd_case(int rows, int cols) {
   verdict("abi sgd_momentum_step " + std::to_string(rows) + " x " + std::to_string(cols), std::max(rel_err_f(p, p2.data(), n), rel_err_f(h, h2.data(), n)), rc == 0);
 }
 
+// ---- precision mode: error against double in units of 2^-24 of sum|ab| (prec.h), N(0,1) data and pairwise cancellation -----------------
+// axis: what the product reduces over and the cancellation pairs — "channels" / "taps" (C = 3: x columns and filter taps, stride and
+// padding even) for convUp, "filters" for convDown, "images" for convOutpBias
+static void prec_conv(const Geo& g, const char* which, const char* axis, int patch_mode, int wgrad_tile) {
+  const int My = g.My(), Mx = g.Mx(), TYX = g.Ky * g.Kx, K = g.C * TYX;
+  for (int fam = 0; fam < 2; ++fam) {
+    convnet_hip_set_patch_mode(patch_mode);
+    convnet_hip_set_wgrad_tile(wgrad_tile);
+    auto xv = rnd((size_t)g.C * g.H * g.W * g.N, 61), wv = rnd((size_t)g.F * K, 62), yv = rnd((size_t)g.F * My * Mx * g.N, 63), bv = rnd(g.F, 64);
+    float *x = al16(xv), *w = al16(wv), *y = al16(yv), *b = al16(bv);
+    for (size_t i = 0; i < (size_t)g.F * K; ++i) w[i] *= 0.05f;
+    const std::string ax = axis;
+    if (fam == 1) {
+      std::mt19937 r(65);
+      if (ax == "channels") { prec::pair(x, 1, g.C, (size_t)g.H * g.W * g.N, false, r); prec::pair(w, 1, g.C, (size_t)TYX * g.F, true, r); }
+      if (ax == "taps") { prec::pair(x, (size_t)g.C * g.H, g.W, g.N, false, r); prec::pair(w, (size_t)g.C * g.Ky, g.Kx, g.F, true, r); }
+      if (ax == "filters") { prec::pair(y, 1, g.F, (size_t)My * Mx * g.N, false, r); prec::pair(w, (size_t)K, g.F, 1, true, r); }
+      if (ax == "images") { prec::pair(x, (size_t)g.C * g.H * g.W, g.N, 1, false, r); prec::pair(y, (size_t)g.F * My * Mx, g.N, 1, true, r); }
+    }
+    cudamat mx = mat(x, g.N, g.H * g.W * g.C), mw = mat(w, g.F, K), my = mat(y, g.N, My * Mx * g.F), mb = mat(b, 1, g.F);
+    Shape4D sx{{g.N, g.W, g.H, g.C}}, sw{{g.F, g.Kx, g.Ky, g.C}}, sy{{g.N, Mx, My, g.F}};
+    const std::string what = which;
+    const float *out = nullptr;
+    std::vector<double> ref, mag;
+    std::vector<float> cat;
+    if (what == "up") {
+      ref.assign((size_t)g.F * My * Mx * g.N, 0.0); mag = ref;
+      for (int f = 0; f < g.F; ++f)
+        for (int oy = 0; oy < My; ++oy)
+          for (int ox = 0; ox < Mx; ++ox)
+            for (int c = 0; c < g.C; ++c)
+              for (int a = 0; a < g.Ky; ++a)
+                for (int bb = 0; bb < g.Kx; ++bb) {
+                  const int ys = oy * g.sy - g.pad + a, xs = ox * g.sx - g.pad + bb;
+                  if (ys < 0 || ys >= g.H || xs < 0 || xs >= g.W) continue;
+                  const double wv1 = w[f + (size_t)g.F * (a * g.Kx + bb + TYX * c)];
+                  for (int n = 0; n < g.N; ++n) {
+                    const double t = wv1 * x[((size_t)(c * g.H + ys) * g.W + xs) * g.N + n];
+                    const size_t o = ((size_t)(f * My + oy) * Mx + ox) * g.N + n;
+                    ref[o] += t; mag[o] += std::fabs(t);
+                  }
+                }
+      convUp(&mx, &mw, &my, &sx, &sw, &sy, desc(g), 0.f);
+      out = y;
+    } else if (what == "down") {
+      ref.assign((size_t)g.C * g.H * g.W * g.N, 0.0); mag = ref;
+      for (int c = 0; c < g.C; ++c)
+        for (int iy = 0; iy < g.H; ++iy)
+          for (int ix = 0; ix < g.W; ++ix)
+            for (int f = 0; f < g.F; ++f)
+              for (int a = 0; a < g.Ky; ++a)
+                for (int bb = 0; bb < g.Kx; ++bb) {
+                  const int ty = iy + g.pad - a, tx = ix + g.pad - bb;
+                  if (ty < 0 || tx < 0 || ty % g.sy || tx % g.sx) continue;
+                  const int oy = ty / g.sy, ox = tx / g.sx;
+                  if (oy >= My || ox >= Mx) continue;
+                  const double wv1 = w[f + (size_t)g.F * (a * g.Kx + bb + TYX * c)];
+                  for (int n = 0; n < g.N; ++n) {
+                    const double t = wv1 * y[((size_t)(f * My + oy) * Mx + ox) * g.N + n];
+                    const size_t o = ((size_t)(c * g.H + iy) * g.W + ix) * g.N + n;
+                    ref[o] += t; mag[o] += std::fabs(t);
+                  }
+                }
+      convDown(&my, &mw, &mx, &sy, &sw, &sx, desc(g), 0.f);
+      out = x;
+    } else {   // weight gradient, then the bias gradient as the last F entries
+      ref.assign((size_t)g.F * K + g.F, 0.0); mag = ref;
+      for (int f = 0; f < g.F; ++f) {
+        for (int c = 0; c < g.C; ++c)
+          for (int a = 0; a < g.Ky; ++a)
+            for (int bb = 0; bb < g.Kx; ++bb) {
+              const size_t i = f + (size_t)g.F * (a * g.Kx + bb + TYX * c);
+              for (int oy = 0; oy < My; ++oy)
+                for (int ox = 0; ox < Mx; ++ox) {
+                  const int ys = oy * g.sy - g.pad + a, xs = ox * g.sx - g.pad + bb;
+                  if (ys < 0 || ys >= g.H || xs < 0 || xs >= g.W) continue;
+                  for (int n = 0; n < g.N; ++n) {
+                    const double t = (double)x[((size_t)(c * g.H + ys) * g.W + xs) * g.N + n] * y[((size_t)(f * My + oy) * Mx + ox) * g.N + n];
+                    ref[i] += t; mag[i] += std::fabs(t);
+                  }
+                }
+            }
+        for (size_t i = 0; i < (size_t)My * Mx * g.N; ++i) {
+          const double t = y[(size_t)f * My * Mx * g.N + i];
+          ref[(size_t)g.F * K + f] += t; mag[(size_t)g.F * K + f] += std::fabs(t);
+        }
+      }
+      convOutpBias(&mx, &my, &mw, &mb, &sx, &sy, &sw, desc(g), 0.f, 1.f);
+      cat.assign(w, w + (size_t)g.F * K);
+      cat.insert(cat.end(), b, b + g.F);
+      out = cat.data();
+    }
+    const std::string name = "abi conv" + what + " " + gname(g) + " mode " + std::to_string(patch_mode) + "/" + std::to_string(wgrad_tile) + " [" +
+                             chip::g_last_kernel + "]";
+    if (!prec::verdict(name.c_str(), fam ? "cancellation" : "normal", prec::err(out, ref, mag))) ++g_fail;
+  }
+}
+// NT / NN / TN of an FC layer (fc_edge.cc), cancellation along the axis each reduces over
+static void prec_dot(int N, int D, int F) {
+  for (int fam = 0; fam < 2; ++fam) {
+    auto xv = rnd((size_t)N * D, 71), wv = rnd((size_t)F * D, 72), dv = rnd((size_t)N * F, 73), tv = rnd((size_t)std::max(N, F) * std::max(D, F), 74);
+    float *x = al16(xv), *w = al16(wv), *dy = al16(dv), *t = al16(tv);
+    for (int form = 0; form < 3; ++form) {
+      std::vector<float> xs(x, x + (size_t)N * D), ws(w, w + (size_t)F * D), ds(dy, dy + (size_t)N * F);
+      if (fam == 1) {
+        std::mt19937 r(75 + form);
+        if (form == 0) { prec::pair(xs.data(), 1, D, N, false, r); prec::pair(ws.data(), 1, D, F, true, r); }          // x[d][n], w[d][f]: over d
+        if (form == 1) { prec::pair(ds.data(), 1, F, N, false, r); prec::pair(ws.data(), D, F, 1, true, r); }          // over f
+        if (form == 2) { prec::pair(ds.data(), F, N, 1, false, r); prec::pair(xs.data(), D, N, 1, true, r); }          // over n
+      }
+      std::copy(xs.begin(), xs.end(), x); std::copy(ws.begin(), ws.end(), w); std::copy(ds.begin(), ds.end(), dy);
+      const int rows = form == 0 ? N : form == 1 ? N : F, cols = form == 0 ? F : form == 1 ? D : D, kk = form == 0 ? D : form == 1 ? F : N;
+      std::vector<double> ref((size_t)rows * cols, 0.0), mag = ref;
+      for (int i = 0; i < rows; ++i)
+        for (int j = 0; j < cols; ++j)
+          for (int k = 0; k < kk; ++k) {
+            const double v = form == 0 ? (double)x[i + (size_t)N * k] * w[j + (size_t)F * k]
+                           : form == 1 ? (double)dy[i + (size_t)N * k] * w[k + (size_t)F * j] : (double)dy[k + (size_t)N * i] * x[k + (size_t)N * j];
+            ref[i + (size_t)rows * j] += v; mag[i + (size_t)rows * j] += std::fabs(v);
+          }
+      cudamat mt = mat(t, rows, cols);
+      int rc;
+      if (form == 0) { cudamat a = mat(x, N, D), b = mat(w, F, D); b.is_trans = 1; rc = dot(&a, &b, &mt, 0.f, 1.f); }
+      else if (form == 1) { cudamat a = mat(dy, N, F), b = mat(w, F, D); rc = dot(&a, &b, &mt, 0.f, 1.f); }
+      else { cudamat a = mat(dy, N, F), b = mat(x, N, D); a.is_trans = 1; rc = dot(&a, &b, &mt, 0.f, 1.f); }
+      const std::string name = std::string("abi dot ") + (form == 0 ? "NT" : form == 1 ? "NN" : "TN") + " N" + std::to_string(N) + " D" + std::to_string(D) +
+                               " F" + std::to_string(F) + " [" + chip::g_last_kernel + "]";
+      if (rc || !prec::verdict(name.c_str(), fam ? "cancellation" : "normal", prec::err(t, ref, mag))) ++g_fail;
+    }
+  }
+}
+
 int main(int argc, char** argv) {
   const std::string what = argc > 1 ? argv[1] : "quick";   // abi | gpp | gpw | gpv | gpvtail | gpwtail | wgw | wgwvar | wgwfin | quick (a subset of each, ~1 minute) | all
   const bool all = what == "all", quick = what == "quick";   // ("all" does not include gpwtail: its 8-slot chip is a process-wide setting)
+  if (what == "prec") {   // every split build emulation runs, N(0,1) and pairwise-cancelling data, error vs double per sum|ab|
+    prec_conv(Geo{64, 3, 16, 16, 96, 7, 7, 2, 2, 2}, "up", "taps", 0, 0);        // gfc_kernel
+    prec_conv(Geo{48, 3, 16, 16, 96, 7, 7, 2, 2, 2}, "up", "taps", 0, 0);        // generic-k ggp_kernel<1,4,3,64,split,pre>
+    prec_conv(Geo{32, 32, 6, 6, 128, 3, 3, 1, 1, 1}, "up", "channels", 0, 0);    // ggp_kernel<2,2,2,128,split,pre>
+    prec_conv(Geo{32, 32, 6, 6, 32, 3, 3, 1, 1, 1}, "up", "channels", 0, 0);     // gg_kernel<1,4,1,128,rc,split>
+    prec_conv(Geo{64, 16, 9, 9, 128, 3, 3, 1, 1, 1}, "up", "channels", 4, 0);    // gpw_kernel
+    prec_conv(Geo{32, 128, 6, 6, 32, 3, 3, 1, 1, 1}, "down", "filters", 0, 0);   // ggp_kernel<2,2,2,128,split,pre>, one stride class
+    prec_conv(Geo{64, 96, 19, 19, 16, 5, 5, 2, 2, 0}, "down", "filters", 4, 0);  // gpv_kernel<96x512>: four stride classes
+    prec_conv(Geo{32, 16, 9, 9, 128, 3, 3, 1, 1, 1}, "outp", "images", 0, 0);    // wg_kernel<2,2,2,2,split>, bias row
+    prec_conv(Geo{32, 3, 15, 15, 96, 7, 7, 2, 2, 1}, "outp", "images", 0, 0);    // wg_kernel<2,2,5,3,x16,split>, bias row
+    prec_conv(Geo{32, 32, 9, 9, 192, 3, 3, 1, 1, 1}, "outp", "images", 0, 1);    // wgw_kernel<256x192,split>
+    prec_dot(64, 256, 128);                                                       // gg_kernel<4,1,1,64,rc|kc,split>, wg_kernel
+    prec_dot(256, 96, 128);                                                       // ggp_kernel<2,2,2,128,split>, gg_kernel<1,4,3,64,kc,split>
+  }
   if (what == "abi" || all || quick) {   // the default kernels through the C ABI: the calibration of the harness (green on hardware)
     abi_conv_case(Geo{64, 16, 9, 9, 128, 3, 3, 1, 1, 1}, "up");      // ggp_kernel<2,2,2,128>, pre-split filter planes
     abi_conv_case(Geo{32, 16, 9, 9, 128, 3, 3, 1, 1, 1}, "outp");    // wg_kernel<2,2,2,2>, K = 144: bias row in the second k tile

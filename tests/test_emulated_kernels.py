@@ -86,3 +86,16 @@ def test_group_patch_kernel_tail_split_in_emulation(emu_binary):
     r = subprocess.run([emu_binary, "gpvtail"], capture_output=True, text=True, timeout=1200)
     lines = r.stdout.strip().splitlines()
     assert r.returncode == 0 and lines[-1] == "ALL PASSED" and "tail_splits=3" in lines[0], r.stdout + r.stderr
+
+
+def test_split_builds_error_against_double_in_emulation(emu_binary):
+    """The precision half of parity, before any GPU run: every split build emulation runs (gfc_kernel, generic-k and tap-major
+    ggp_kernel, gg_kernel rc and kc, gpw_kernel, gpv_kernel's stride classes, wg_kernel 2,2,2,2 and x16 with the bias row, the FC NT /
+    NN / TN products) on N(0,1) data and on data whose terms cancel in pairs along the axis each product reduces over, against double:
+    max |out - exact| / sum|ab| within tests/emu/prec.h's bounds.  The 1e-4 parity cases above cannot tell a dropped cross term from
+    rounding; these can (the bounds' calibration against the m*m-dropped and zero-l-plane mutants is in tests/emu/prec.h)."""
+    r = subprocess.run([emu_binary, "prec"], capture_output=True, text=True, timeout=1200)
+    lines = r.stdout.strip().splitlines()
+    print(r.stdout)
+    assert r.returncode == 0 and lines and lines[-1] == "ALL PASSED", r.stdout + r.stderr
+    assert sum(l.startswith("PASS prec") for l in lines) == 32, r.stdout

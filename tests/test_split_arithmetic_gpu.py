@@ -53,11 +53,13 @@ BOUNDS = {"normal": (1.25, 1.0, 8.0), "huge": (1.25, 1.0, 8.0), "dynamic_range":
           "tiny": (8.0, 0.0, 32.0)}
 
 
-def _check(tag, kind, es, ef, table):
+def _check(tag, kind, es, ef, table, bound=None):
+    """bound: a row-specific (ratio, floor, cap) in place of BOUNDS[kind] (tests/split_cases.py states each one's reason)"""
     u = 2.0 ** -24
-    table.append(f"{tag:12s} {kind:14s} split {es / u:8.3f} x 2^-24   fp32 path {ef / u:8.3f} x 2^-24 of sum|ab|   ratio {es / max(ef, 1e-300):5.2f}")
+    table.append(f"{tag:12s} {kind:14s} split {es / u:8.3f} x 2^-24   fp32 path {ef / u:8.3f} x 2^-24 of sum|ab|   ratio {es / max(ef, 1e-300):5.2f}"
+                 + ("   (row bound)" if bound else ""))
     print(table[-1])
-    ratio, floor, cap = BOUNDS[kind]
+    ratio, floor, cap = bound or BOUNDS[kind]
     assert np.isfinite(es) and np.isfinite(ef), (tag, kind, es, ef)
     assert es <= cap * u, (tag, kind, "absolute cap", es / u, cap)
     assert es <= max(ratio * ef, floor * u), (tag, kind, "ratio to the fp32 path", es / u, ef / u, ratio)
@@ -305,3 +307,375 @@ def test_default_path_of_the_c_abi_gives_ieee_values_for_non_finite_operands(hip
     assert np.isposinf(y[:, :, :, 3]).any() and np.isneginf(y[:, :, :, 8]).any() and not np.isnan(y).any()
     fin = np.isfinite(ref)
     assert np.abs(y[fin] - ref[fin]).max() < 1e-4 * np.abs(ref[fin & (np.abs(ref) < 1e30)]).mean() or np.allclose(y[fin], ref[fin], rtol=1e-4)
+
+
+# ---- one row per split build (tests/split_cases.py) ------------------------------------------------------------------------------
+# Every kernel family the dispatch can launch on the split path, its epilogues, tail-split / split-K fix and reduce kernels, at the
+# shapes that select it; the row's timer names must appear.  Error in the units above: |out - exact| / (|st t0| + |so| sum|ab| + |bias|),
+# ReLU and mask applied to the exact value.  Measured table: profiles/split_error_builds.txt.
+import split_cases  # noqa: E402
+from split_cases import CASES  # noqa: E402
+
+ROW_TABLE = []
+
+
+def _run_case(case, fn):
+    """fn() on both paths with the patch / wgrad-tile modes of the row; the split path's timer names"""
+    from convnet_amd import _lib
+    names = set()
+    pm, wt = _lib.lib.convnet_hip_get_patch_mode(), _lib.lib.convnet_hip_get_wgrad_tile()
+
+    def call():
+        on_split = _lib.lib.convnet_hip_get_matrix_path() == 1
+        if on_split:
+            _lib.profile_report()
+            _lib.profile_enable(True)
+        try:
+            out = fn()
+        finally:
+            if on_split:
+                names.update(r["kernel"] for r in _lib.profile_report())
+                _lib.profile_enable(False)
+        return out
+    try:
+        if case.patch_mode >= 0:
+            _lib.lib.convnet_hip_set_patch_mode(case.patch_mode)
+        if case.wgrad_tile >= 0:
+            _lib.lib.convnet_hip_set_wgrad_tile(case.wgrad_tile)
+        s, f = _both_paths(call)
+    finally:
+        _lib.lib.convnet_hip_set_patch_mode(pm)
+        _lib.lib.convnet_hip_set_wgrad_tile(wt)
+    return s, f, names
+
+
+def _cancel(kind, rng, a, b, axis_a, axis_b):
+    """pair the terms of every dot product along (axis_a of a, axis_b of b): a's odd slices repeat the even ones up to 2^-12, b's odd
+    slices negate them — the pairs cancel to ~2^-12 of their magnitude.  Each operand is paired over its whole axis; an odd last
+    slice of b is zeroed, so no term is left without its partner."""
+    if kind != "cancellation":
+        return a, b
+    a, b = np.moveaxis(a.copy(), axis_a, 0), np.moveaxis(b.copy(), axis_b, 0)
+    ha, hb = a.shape[0] // 2, b.shape[0] // 2
+    a[1:2 * ha:2] = a[0:2 * ha:2] * (1 + np.float32(2.0 ** -12) * rng.standard_normal(a[1:2 * ha:2].shape, dtype=np.float32))
+    b[1:2 * hb:2] = -b[0:2 * hb:2]
+    if b.shape[0] % 2:
+        b[-1] = 0
+    return np.moveaxis(a, 0, axis_a), np.moveaxis(b, 0, axis_b)
+
+
+def _scaled(kind, rng, shape, scale_a, scale_b, k):
+    """a target / bias operand of the magnitude of the row's products (scale_a * scale_b * sqrt(k))"""
+    return (rng.standard_normal(shape) * (scale_a * scale_b * np.sqrt(k))).astype(np.float32)
+
+
+def _scale_of(v):
+    s = np.abs(v.reshape(-1)[:: max(1, v.size // 4096)]).astype(np.float64)
+    s = s[s > 0]
+    return float(np.median(s)) if s.size else 0.0
+
+
+def _epilogue_err(out, acc, mag, case, t0=None, bias=None, mask=None):
+    """max |out - exact| / denominator over the given outputs (arrays broadcast together)"""
+    st, so = case.st, case.so
+    t0 = np.zeros_like(acc) if t0 is None else t0.astype(np.float64)
+    bias = np.zeros_like(acc) if bias is None else bias.astype(np.float64)
+    exact = st * t0 + so * acc + bias
+    den = np.abs(st * t0) + abs(so) * mag + np.abs(bias)
+    if case.relu:
+        exact = np.maximum(exact, 0.0)
+    if mask is not None:
+        exact = np.where(mask > 0, case.post_scale * exact, 0.0)
+        den = abs(case.post_scale) * den
+    with np.errstate(invalid="ignore", divide="ignore"):
+        e = np.abs(out.astype(np.float64) - exact) / den
+    bad = ~np.isfinite(out) | (den == 0) & (out != exact)
+    if bad.any():
+        return float("inf")
+    return float(np.nanmax(np.where(den > 0, e, 0.0)))
+
+
+def _conv_fprop_at(g, x, w, pix):
+    """(acc, mag) (F, N) per sampled output pixel"""
+    res = []
+    for (oy, ox) in pix:
+        acc = np.zeros((g.F, g.N)); mag = np.zeros((g.F, g.N))
+        for ky in range(g.Ky):
+            for kx in range(g.Kx):
+                iy, ix = oy * g.sy + ky - g.pady, ox * g.sx + kx - g.padx
+                if 0 <= iy < g.H and 0 <= ix < g.W:
+                    a, b = w[:, ky, kx, :].astype(np.float64), x[:, iy, ix, :].astype(np.float64)
+                    acc += a.T @ b
+                    mag += np.abs(a).T @ np.abs(b)
+        res.append((acc, mag))
+    return res
+
+
+def _conv_dgrad_at(g, dy, w, pix):
+    res = []
+    for (iy, ix) in pix:
+        acc = np.zeros((g.C, g.N)); mag = np.zeros((g.C, g.N))
+        for ky in range(g.Ky):
+            for kx in range(g.Kx):
+                ty, tx = iy + g.pady - ky, ix + g.padx - kx
+                if ty % g.sy or tx % g.sx:
+                    continue
+                oy, ox = ty // g.sy, tx // g.sx
+                if 0 <= oy < g.My and 0 <= ox < g.Mx:
+                    a, b = w[:, ky, kx, :].astype(np.float64), dy[:, oy, ox, :].astype(np.float64)
+                    acc += a @ b
+                    mag += np.abs(a) @ np.abs(b)
+        res.append((acc, mag))
+    return res
+
+
+def _conv_wgrad_at(g, x, dy, taps):
+    res = []
+    oy, ox = np.arange(g.My), np.arange(g.Mx)
+    for (c, ky, kx) in taps:
+        iy, ix = oy * g.sy + ky - g.pady, ox * g.sx + kx - g.padx
+        my, mx = (iy >= 0) & (iy < g.H), (ix >= 0) & (ix < g.W)
+        xs = x[c][np.ix_(iy[my], ix[mx])].astype(np.float64).reshape(-1)
+        ds = dy[:, oy[my]][:, :, ox[mx]].astype(np.float64).reshape(g.F, -1)
+        res.append((ds @ xs, np.abs(ds) @ np.abs(xs)))
+    return res
+
+
+def _conv_case(hip, case, kind, rng):
+    from convnet_amd.matrix import Matrix
+    from hip_adapter import _desc, _mat
+    N, C, H, W, F, Ky, Kx, sy, sx, pad = case.shape
+    g = Geom(N=N, C=C, H=H, W=W, F=F, Ky=Ky, Kx=Kx, sy=sy, sx=sx, pady=pad, padx=pad)
+    x, w, dy = _data("normal" if kind == "cancellation" else kind, rng, g)
+    if kind == "cancellation":
+        if case.axis == "taps":
+            # C = 3: taps kx, kx + 1 (kx even) read columns ix, ix + 1 with ix = sx*ox + kx - pad even (sx, pad even), so x columns
+            # are paired over the whole row and the filter's tap pairs negated (the odd last tap zeroed); W even keeps every pair
+            # either inside the image or in the padding
+            assert sx % 2 == 0 and pad % 2 == 0 and W % 2 == 0, case.id
+            x, w = _cancel(kind, rng, x, w, 2, 2)
+        elif case.axis == "channels":
+            x, w = _cancel(kind, rng, x, w, 0, 0)
+        elif case.axis == "filters":
+            dy, w = _cancel(kind, rng, dy, w, 0, 3)
+        else:
+            x, dy = _cancel(kind, rng, x, dy, 3, 3)
+    if case.op == "wgrad" and kind == "tiny":
+        dy = dy * np.float32(2.0 ** 116)
+    opix = [(0, 0), (g.My - 1, g.Mx - 1), (0, g.Mx - 1), (g.My - 1, 0)] + [(int(rng.integers(g.My)), int(rng.integers(g.Mx))) for _ in range(6)]
+    ipix = [(0, 0), (g.H - 1, g.W - 1), (1, g.W - 2), (g.H - 1, 0)] + [(int(rng.integers(g.H)), int(rng.integers(g.W))) for _ in range(6)]
+    taps = [(0, 0, 0), (C - 1, Ky - 1, Kx - 1)] + [(int(rng.integers(C)), int(rng.integers(Ky)), int(rng.integers(Kx))) for _ in range(6)]
+    if case.op == "fprop":
+        t0 = _scaled(kind, rng, g.out_shape(), _scale_of(x), _scale_of(w), g.K) if case.st else None
+        bias = _scaled(kind, rng, (F,), _scale_of(x), _scale_of(w), g.K) if case.entry == "convUpBiasAct" else None
+
+        def fn():
+            X, Wm = hip._act(x, N, W, H, C), _mat(w, F, g.K, (F, Kx, Ky, C))
+            T = hip._act(t0 if t0 is not None else np.zeros(g.out_shape(), np.float32), N, g.Mx, g.My, F)
+            if bias is not None:
+                Matrix.ConvUpBiasAct(X, Wm, _mat(bias, 1, F), T, _desc(g), case.st, bool(case.relu))
+            else:
+                Matrix.ConvUp(X, Wm, T, _desc(g), case.st)
+            return T.ToNumpy().reshape(g.out_shape())
+        ys, yf, names = _run_case(case, fn)
+        sums = _conv_fprop_at(g, x, w, opix)
+
+        def err(y):
+            return max(_epilogue_err(y[:, oy, ox, :], acc, mag, case, None if t0 is None else t0[:, oy, ox, :],
+                                     None if bias is None else bias[:, None]) for (oy, ox), (acc, mag) in zip(opix, sums))
+        return err(ys), err(yf), names
+    if case.op == "dgrad":
+        t0 = _scaled(kind, rng, g.in_shape(), _scale_of(dy), _scale_of(w), F * Ky * Kx // (sy * sx)) if case.st else None
+        mask = rng.standard_normal(g.in_shape()).astype(np.float32) if case.entry == "convDownMask" else None
+
+        def fn():
+            D, Wm = hip._act(dy, N, g.Mx, g.My, F), _mat(w, F, g.K, (F, Kx, Ky, C))
+            T = hip._act(t0 if t0 is not None else np.zeros(g.in_shape(), np.float32), N, W, H, C)
+            if mask is not None:
+                Matrix.ConvDownMask(D, Wm, hip._act(mask, N, W, H, C), T, _desc(g), case.st, case.post_scale)
+            else:
+                Matrix.ConvDown(D, Wm, T, _desc(g), case.st)
+            return T.ToNumpy().reshape(g.in_shape())
+        ds, df, names = _run_case(case, fn)
+        sums = _conv_dgrad_at(g, dy, w, ipix)
+
+        def err(d):
+            return max(_epilogue_err(d[:, iy, ix, :], acc, mag, case, None if t0 is None else t0[:, iy, ix, :],
+                                     None, None if mask is None else mask[:, iy, ix, :]) for (iy, ix), (acc, mag) in zip(ipix, sums))
+        return err(ds), err(df), names
+    # weight gradient (+ bias gradient)
+    M = g.My * g.Mx * N
+    t0 = _scaled(kind, rng, g.filt_shape(), _scale_of(x), _scale_of(dy), M) if case.st else np.zeros(g.filt_shape(), np.float32)
+    b0 = _scaled(kind, rng, (F,), 1.0, _scale_of(dy), M)
+    with_bias = case.entry == "convOutpBias"
+
+    def fn():
+        from hip_adapter import conv_outp_bias
+        if with_bias:
+            return conv_outp_bias(g, x, dy, t0, b0, case.st, case.so)
+        return hip.conv_outp(g, x, dy, t0, case.st, case.so), None
+    (ws, bs), (wf, bf), names = _run_case(case, fn)
+    sums = _conv_wgrad_at(g, x, dy, taps)
+    dyf = dy.astype(np.float64).reshape(F, -1)
+    bacc, bmag = dyf.sum(1), np.abs(dyf).sum(1)
+
+    def err(dw, db):
+        e = max(_epilogue_err(dw[c, ky, kx, :], acc, mag, case, t0[c, ky, kx, :]) for (c, ky, kx), (acc, mag) in zip(taps, sums))
+        if with_bias:
+            e = max(e, _epilogue_err(db, bacc, bmag, case, b0))
+        return e
+    return err(ws, bs), err(wf, bf), names
+
+
+def _fc_case(hip, case, kind, rng):
+    """every output against float64.  numpy layouts: in (D, N), W (D, F), dout (F, N) — the column-major (N, D), (F, D), (N, F)."""
+    from convnet_amd.matrix import Matrix
+    from hip_adapter import _mat
+    N, D, F = case.shape
+    a = rng.standard_normal((D, N), dtype=np.float32)
+    w = rng.standard_normal((D, F), dtype=np.float32) * np.float32(0.05)
+    dy = rng.standard_normal((F, N), dtype=np.float32)
+    if kind == "dynamic_range":
+        a *= np.exp2(rng.integers(-20, 21, (D, 1))).astype(np.float32)
+        w *= np.exp2(rng.integers(-20, 21, (D, 1))).astype(np.float32)
+        dy *= np.exp2(rng.integers(-20, 21, (F, 1))).astype(np.float32)
+    elif kind == "tiny":
+        a, w, dy = a * np.float32(2.0 ** -116), w * np.float32(2.0 ** 20), dy * np.float32(2.0 ** -116)
+    elif kind == "huge":
+        with np.errstate(over="ignore"):
+            a = np.clip(a * np.float32(1e38), -BF16_RNE_LIMIT, BF16_RNE_LIMIT)
+            dy = np.clip(dy * np.float32(1e38), -BF16_RNE_LIMIT, BF16_RNE_LIMIT)
+        w = w * np.float32(2.0 ** -20)
+    if case.trans == "NT":
+        a, w = _cancel(kind, rng, a, w, 0, 0)
+        A, B, out_shape, k = a, w, (F, N), D              # out (N, F) = in (N, D) W (F, D)^T
+        exact = w.astype(np.float64).T @ a.astype(np.float64)
+        mag = np.abs(w).astype(np.float64).T @ np.abs(a).astype(np.float64)
+        ta, tb = False, True
+    elif case.trans == "NN":
+        dy, w = _cancel(kind, rng, dy, w, 0, 1)
+        A, B, out_shape, k = dy, w, (D, N), F           # din (N, D) = dout (N, F) W (F, D)
+        exact = w.astype(np.float64) @ dy.astype(np.float64)
+        mag = np.abs(w).astype(np.float64) @ np.abs(dy).astype(np.float64)
+        ta, tb = False, False
+    else:
+        if kind == "tiny":
+            dy = dy * np.float32(2.0 ** 116)
+        dy, a = _cancel(kind, rng, dy, a, 1, 1)
+        A, B, out_shape, k = dy, a, (D, F), N             # dW (F, D) = dout (N, F)^T in (N, D)
+        exact = (dy.astype(np.float64) @ a.astype(np.float64).T).T
+        mag = (np.abs(dy).astype(np.float64) @ np.abs(a).astype(np.float64).T).T
+        ta, tb = True, False
+    rows = out_shape[0]   # bias / per-row quantities: outputs of numpy shape (rows of the column-major target = cols here)
+    t0 = _scaled(kind, rng, out_shape, _scale_of(A), _scale_of(B), k) if case.st else np.zeros(out_shape, np.float32)
+    bias = _scaled(kind, rng, (rows,), _scale_of(A), _scale_of(B), k) if case.entry == "dotBiasAct" else None
+    mask = rng.standard_normal(out_shape).astype(np.float32) if case.entry == "dotMask" else None
+
+    def fn():
+        Am, Bm, T = _mat(A, A.shape[1], A.shape[0]), _mat(B, B.shape[1], B.shape[0]), _mat(t0, out_shape[1], out_shape[0])
+        if case.entry == "dotBiasAct":
+            Matrix.DotBiasAct(Am, Bm, _mat(bias, 1, rows), T, case.st, case.so, ta, tb, bool(case.relu))
+        elif case.entry == "dotMask":
+            _dot_mask(Am, Bm, mask, T, case, out_shape, ta, tb)
+        else:
+            Matrix.Dot(Am, Bm, T, case.st, case.so, ta, tb)
+        return T.ToNumpy().reshape(out_shape)
+    ys, yf, names = _run_case(case, fn)
+
+    def err(y):
+        return _epilogue_err(y, exact, mag, case, t0 if case.st else None, None if bias is None else bias[:, None], mask)
+    return err(ys), err(yf), names
+
+
+def _dot_mask(Am, Bm, mask, T, case, out_shape, ta, tb):
+    from convnet_amd._lib import lib
+    from hip_adapter import _mat
+    am = Am.GetMatTranspose() if ta else Am.GetMat()
+    bm = Bm.GetMatTranspose() if tb else Bm.GetMat()
+    rc = lib.dotMask(am, bm, _mat(mask, out_shape[1], out_shape[0]).GetMat(), T.GetMat(), float(case.st), float(case.so), float(case.post_scale))
+    assert rc == 0, rc
+
+
+def _local_case(case, kind, rng):
+    import local_ref as L
+    from local_ref import LocalGeom
+    import test_local_gpu as TL
+    N, C, H, W, F, Ky, Kx, sy, sx, pad = case.shape
+    g = LocalGeom(N=N, C=C, H=H, W=W, F=F, Ky=Ky, Kx=Kx, sy=sy, sx=sx, pady=pad, padx=pad)
+    x = rng.standard_normal(g.in_shape(), dtype=np.float32)
+    w = rng.standard_normal(g.bank_shape(), dtype=np.float32) * np.float32(0.05)
+    dy = rng.standard_normal(g.out_shape(), dtype=np.float32)
+    if kind == "dynamic_range":
+        x *= np.exp2(rng.integers(-20, 21, (C, 1, 1, 1))).astype(np.float32)
+        w *= np.exp2(rng.integers(-20, 21, (1, C, 1, 1, 1))).astype(np.float32)
+        dy *= np.exp2(rng.integers(-20, 21, (F, 1, 1, 1))).astype(np.float32)
+    elif kind == "tiny":
+        x, w, dy = x * np.float32(2.0 ** -116), w * np.float32(2.0 ** 20), dy * np.float32(2.0 ** -116)
+        if case.op == "local_outp":
+            dy = dy * np.float32(2.0 ** 116)
+    elif kind == "huge":
+        with np.errstate(over="ignore"):
+            x = np.clip(x * np.float32(1e38), -BF16_RNE_LIMIT, BF16_RNE_LIMIT)
+            dy = np.clip(dy * np.float32(1e38), -BF16_RNE_LIMIT, BF16_RNE_LIMIT)
+        w = w * np.float32(2.0 ** -20)
+    elif kind == "cancellation":
+        if case.axis == "channels":
+            x, w = _cancel(kind, rng, x, w, 0, 1)
+        elif case.axis == "filters":
+            dy, w = _cancel(kind, rng, dy, w, 0, 4)
+        else:
+            x, dy = _cancel(kind, rng, x, dy, 3, 3)
+    if case.op == "local_up":
+        t0 = _scaled(kind, rng, g.out_shape(), _scale_of(x), _scale_of(w), g.K) if case.st else None
+        bias = _scaled(kind, rng, (F, g.My, g.Mx), _scale_of(x), _scale_of(w), g.K) if case.entry == "localUpBiasAct" else None
+
+        def fn():
+            if bias is None:
+                return TL.run_up(g, x, w, t0, case.st, "localUp")
+            from convnet_amd._lib import lib
+            import ctypes
+            X, (Wm, _), T = TL._x(g, x), TL._w(g, w), TL._y(g, t0 if t0 is not None else np.zeros(g.out_shape()))
+            lib.localUpBiasAct(X.GetMat(), Wm.GetMat(), TL._mat(bias, 1, F * g.M).GetMat(), T.GetMat(), ctypes.byref(X.shape_),
+                               ctypes.byref(Wm.shape_), ctypes.byref(T.shape_), TL._desc(g), float(case.st), int(case.relu))
+            return T.ToNumpy().reshape(g.out_shape())
+        exact, mag = L.torch_up(g, x, w), L.torch_up(g, np.abs(x), np.abs(w))
+        extra = {"t0": t0, "bias": None if bias is None else bias[..., None]}
+    elif case.op == "local_down":
+        t0 = _scaled(kind, rng, g.in_shape(), _scale_of(dy), _scale_of(w), F * Ky * Kx) if case.st else None
+
+        def fn():
+            return TL.run_down(g, dy, w, t0, case.st, "localDown")
+        exact, mag = L.torch_down(g, dy, w), L.torch_down(g, np.abs(dy), np.abs(w))
+        extra = {"t0": t0}
+    else:
+        t0 = _scaled(kind, rng, g.bank_shape(), _scale_of(x), _scale_of(dy), N) if case.st else None
+
+        def fn():
+            return TL.run_outp(g, x, dy, t0, case.st, case.so, "localOutp")[0]
+        exact, mag = L.torch_outp(g, x, dy), L.torch_outp(g, np.abs(x), np.abs(dy))
+        extra = {"t0": t0}
+    ys, yf, names = _run_case(case, fn)
+    return _epilogue_err(ys, exact, mag, case, **extra), _epilogue_err(yf, exact, mag, case, **extra), names
+
+
+def _kinds(case):
+    return ["normal", "dynamic_range", "cancellation"] + (["tiny", "huge"] if case.direction == "fwd" else [])
+
+
+ROWS = [(c, k) for c in CASES for k in _kinds(c)]
+
+
+@pytest.mark.parametrize("case,kind", ROWS, ids=[f"{c.id}-{k}" for c, k in ROWS])
+def test_every_split_build_is_within_the_bounds_against_float64(hip, case, kind):
+    rng = np.random.default_rng(sum(map(ord, case.id + kind)))
+    if case.entry.startswith("local"):
+        es, ef, names = _local_case(case, kind, rng)
+    elif case.entry.startswith("dot"):
+        es, ef, names = _fc_case(hip, case, kind, rng)
+    else:
+        es, ef, names = _conv_case(hip, case, kind, rng)
+    missing = [n for n in case.expect if n not in names]
+    assert not missing, (case.id, "expected kernels did not run", missing, sorted(names))
+    if case.fp32:
+        assert not any(",split" in n for n in names if split_cases.family(n) == split_cases.family(case.expect[0])), sorted(names)
+    _check(case.id, kind, es, ef, ROW_TABLE, case.bound(kind))
