@@ -200,6 +200,12 @@ def _load():
     sig("get_softmax_cross_entropy_row_major", I, M, M, M, F)
     sig("softmax_ce_grad_correct", I, M, M, M, M, M, F)
     sig("sgd_momentum_step", I, M, M, M, F, F, F, F)
+    # batch normalisation (csrc/batch_norm.hip): the reference's three cudamat entries and the two fused ones
+    sig("bn_bprop_inplace", I, M, M, M)
+    sig("bn_bprop", I, M, M, M, M, M, M, F)
+    sig("bn_grad", I, M, M, M, M, M, M)
+    sig("bn_fprop_act", I, M, M, M, M, M, M, M, F, F, I, I)
+    sig("bn_bprop_fused", I, M, M, M, M, M, M, M)
     sig("sgd_momentum_step_normlimit", I, M, M, M, F, F, F, F, F, I)
     sig("sgd_momentum_step_multi", I, I, P(M), P(M), P(M), c_float_p, c_float_p, c_float_p, c_float_p)
     R = P(rnd_struct)

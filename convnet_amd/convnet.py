@@ -21,7 +21,7 @@ from collections import deque
 import torch
 
 from . import pbtxt
-from .edge import ConvEdge, Edge, EdgeWithWeight, FCEdge, LocalEdge, MaxPoolEdge, ResponseNormEdge
+from .edge import AvgPoolEdge, ConvEdge, Edge, EdgeWithWeight, FCEdge, LocalEdge, MaxPoolEdge, ResponseNormEdge
 from .layer import Layer, LinearLayer, ReLULayer, SoftmaxLayer
 from .matrix import Matrix
 from .trainer import TrainLoopMixin
@@ -75,6 +75,16 @@ class ConvNet(TrainLoopMixin):
                     b_opt = m.default_bias_optimizer.copy()
                     b_opt.MergeFrom(e.bias_optimizer)
                     e.mutable("bias_optimizer").CopyFrom(b_opt)
+        # ... and for batch-normalised layers (src/convnet.cc:56-64), quirk included: beta's own block is merged into the GAMMA
+        # config's copy (which is then unused), so beta always runs the plain default bias optimizer
+        for l in m.layer:
+            if l.batch_normalize:
+                w_opt = m.default_weight_optimizer.copy()
+                w_opt.MergeFrom(l.gamma_optimizer)
+                l.mutable("gamma_optimizer").CopyFrom(w_opt)
+                b_opt = m.default_bias_optimizer.copy()
+                w_opt.MergeFrom(l.beta_optimizer)
+                l.mutable("beta_optimizer").CopyFrom(b_opt)
         Matrix.InitRandom(m.seed + process_id)   # src/convnet.cc:67
         self.model_name_ = m.name
         self.layers_, self.edges_ = [], []
@@ -86,7 +96,11 @@ class ConvNet(TrainLoopMixin):
         self.train_dataset_ = None
         self.correct_accum_ = None
         self._logits_pending = set()   # output layers whose state still holds logits (fused softmax)
+        self._bn_steps = []            # fused host: the gamma / beta SGD steps planned during Bprop, run with the edges' batch
         self.BuildNet()
+        if exchange is not None and any(l.UseBatchNormalization() for l in self.layers_):
+            # the reference keeps gamma / beta per replica and steps them inside Bprop, before any exchange: P x (B/P) != 1 x B
+            raise SystemExit("batch_normalize is not supported with a gradient exchange (data-parallel training)")
 
     def log(self, *a):
         if self.verbose:
@@ -118,6 +132,12 @@ class ConvNet(TrainLoopMixin):
                     e.SetDest(l)
                     e.SetOutputChannels(l.GetNumChannels())
         self.Sort()
+        for l in self.layers_:
+            l.fused = self.fused
+            if l.UseBatchNormalization():
+                self._check_batch_norm(l)
+                # fused host: the gamma / beta steps are planned into the step's one sgd_momentum_step_multi launch (PlanFusedStep)
+                l.gamma_optimizer_.fused = l.beta_optimizer_.fused = self.fused
         for e in self.edges_:
             if isinstance(e, MaxPoolEdge):
                 # the mask pair equals the reference's MaxPoolUndo only if backprop sees the raw maxima (edge.MaxPoolEdge)
@@ -146,6 +166,22 @@ class ConvNet(TrainLoopMixin):
             self.log(f"Layer {l.GetName()}: {y}x{x}")
             for e in l.outgoing_edge_:
                 e.SetImageSize(y, x, t)
+
+    @staticmethod
+    def _check_batch_norm(l):
+        """The supported set of batch-normalised layers; anything else stops with the reason."""
+        name = l.GetName()
+        if l.IsInput() or l.IsOutput():
+            raise SystemExit(f"batch_normalize on layer {name}: input and output layers cannot be batch-normalised")
+        if type(l) not in (LinearLayer, ReLULayer):
+            raise SystemExit(f"batch_normalize on layer {name}: only LINEAR and RECTIFIED_LINEAR activations are supported")
+        for e in l.incoming_edge_:
+            if isinstance(e, (MaxPoolEdge, ResponseNormEdge)):
+                # their undo reads this layer's output state, which batch normalisation has overwritten (the reference then routes
+                # almost no gradient)
+                raise SystemExit(f"batch_normalize on layer {name}: not supported behind a {e.__class__.__name__} (edge {e.GetName()})")
+            if not isinstance(e, (FCEdge, ConvEdge, LocalEdge, AvgPoolEdge)):
+                raise SystemExit(f"batch_normalize on layer {name}: edge {e.GetName()} ({e.__class__.__name__}) is not supported")
 
     def Sort(self):
         # breadth-first topological sort, src/convnet.cc:312-353
@@ -247,11 +283,18 @@ class ConvNet(TrainLoopMixin):
     def Fprop(self, train):
         for l in self.layers_:
             fused_act = self._can_fuse_up(l)
+            bn = l.UseBatchNormalization()
             for e in l.incoming_edge_:
                 src = e.GetSource()
                 overwrite = l.AddOrOverwriteState(e.GetDestSliceName())
-                e.ComputeUp(src.GetState(), l.GetState(), overwrite, train, fuse_relu=(l.is_relu if fused_act else None))
-            if not l.IsInput() and not fused_act:
+                # batch normalisation sits between the edge and the activation: the bias may ride in the edge's epilogue, the ReLU not
+                e.ComputeUp(src.GetState(), l.GetState(), overwrite, train, fuse_relu=((l.is_relu and not bn) if fused_act else None))
+            if bn:
+                # src/convnet.cc:382-384; the fused entry applies the ReLU in the same pass
+                l.ApplyBatchNormalization(train, relu=self.fused and l.is_relu)
+                if not self.fused:
+                    l.ApplyActivation()
+            elif not l.IsInput() and not fused_act:
                 if self.fused and isinstance(l, SoftmaxLayer) and l.IsOutput() and train:
                     self._logits_pending.add(l)   # softmax + CE derivative + correct count are fused in ComputeDeriv
                 else:
@@ -362,11 +405,19 @@ class ConvNet(TrainLoopMixin):
             scale = self._fused_down_scale(l)
             for e in l.outgoing_edge_:
                 self._bprop_edge(e.GetDest(), l, e, fuse_mask=scale)
-            if scale is not None:
-                continue   # dropout' and ReLU' were applied by the edge's epilogue
-            l.ApplyDerivativeofDropout()
-            if not l.IsInput() and not l.IsOutput():
-                l.ApplyDerivativeOfActivation()
+            if scale is None:   # else dropout' and ReLU' were applied by the edge's epilogue
+                l.ApplyDerivativeofDropout()
+                if not l.IsInput() and not l.IsOutput():
+                    l.ApplyDerivativeOfActivation()
+            if l.UseBatchNormalization():
+                # src/convnet.cc:401-403
+                if not self.fused and self._in_train_step and self.side_stream_ is not None and self.overlap_wgrad_:
+                    # the unfused sequence rewrites the state in place (recover y, restore), and the weight gradients of this layer's
+                    # outgoing edges read that state on the side stream: order the rewrite after them
+                    ev = torch.cuda.Event()
+                    ev.record(self.side_stream_)
+                    torch.cuda.current_stream().wait_event(ev)
+                l.ApplyDerivativeofBatchNormalization(self._bn_steps if (self.fused and self._in_train_step) else None)
 
     def ComputeDeriv(self):
         for l in self.output_layers_:
@@ -413,6 +464,7 @@ class ConvNet(TrainLoopMixin):
 
     # ---- update: src/convnet.cc:440-450 -------------------------------------------------------------------
     def UpdateWeights(self):
+        bn_steps, self._bn_steps = self._bn_steps, []
         if self._in_train_step and self.side_stream_ is not None:
             if self.overlap_update_:
                 # every edge went through _bprop_edge: drain what is still waiting for its bucket, then make the
@@ -422,9 +474,10 @@ class ConvNet(TrainLoopMixin):
             done.record(self.side_stream_)
             torch.cuda.current_stream().wait_event(done)   # weight gradients (and side-stream updates) are in
             if self.overlap_update_:
+                Matrix.SGDMomentumStepMulti(bn_steps)
                 return
         # fused host: the plain SGD steps of every edge (AlexNet: five convolution banks and eight biases) leave as ONE launch behind the loop
-        batch = [] if self.fused else None
+        batch = list(bn_steps) if self.fused else None   # (+ the batch-norm gamma / beta steps planned during Bprop)
         for e in self.edges_:
             if e.IsBackPropBlocked():
                 continue

@@ -16,6 +16,13 @@ _f = np.float32   # the reference does all of this arithmetic in `float`
 
 
 class GradChecker(ConvNet):
+    def BuildNet(self):
+        super().BuildNet()
+        if any(l.UseBatchNormalization() for l in self.layers_):
+            # the reference's checker runs Fprop(false) on the running statistics, then a Bprop that divides by the last training
+            # batch's sigma and steps gamma / beta halfway through the check: its verdict on a batch-normalised net means nothing
+            raise SystemExit("GradChecker does not support batch_normalize layers")
+
     def GetLoss(self):
         # src/grad_check.cc:10-18
         for l in self.layers_:

@@ -1,8 +1,11 @@
 """Layers — mirror of src/layer.{h,cc} for the hot path: Linear / ReLU / Softmax layers with binary
-dropout, CE loss and the classification metric.  Batch-norm, logistic, slices and the
+dropout, batch normalisation, CE loss and the classification metric.  Logistic, slices and the
 model-parallel state copies are out of scope."""
+import numpy as np
+
 from .loss_functions import LossFunction
 from .matrix import Matrix
+from .optimizer import Optimizer
 
 
 class Layer:
@@ -44,8 +47,19 @@ class Layer:
         self.dropout_noise_ = Matrix()
         self.add_or_overwrite_state_ = True
         self.add_or_overwrite_deriv_ = True
-        if config.batch_normalize or config.layer_slice or self.gaussian_dropout_:
-            raise SystemExit("batch_normalize / layer_slice / gaussian_dropout are out of hot-path scope")
+        if config.layer_slice or self.gaussian_dropout_:
+            raise SystemExit("layer_slice / gaussian_dropout are out of hot-path scope")
+        # batch normalisation (src/layer.cc:60-64; the optimizer configs were merged with the model's defaults by ConvNet)
+        self.batch_normalize_ = bool(config.batch_normalize)
+        self.bn_f_ = config.bn_f
+        self.bn_epsilon_ = config.bn_epsilon
+        self.gamma_optimizer_ = self.beta_optimizer_ = None
+        if self.batch_normalize_:
+            self.gamma_optimizer_ = Optimizer.ChooseOptimizer(config.gamma_optimizer)
+            self.beta_optimizer_ = Optimizer.ChooseOptimizer(config.beta_optimizer)
+        self.gamma_, self.beta_, self.grad_gamma_, self.grad_beta_ = Matrix(), Matrix(), Matrix(), Matrix()
+        self.mu_, self.sigma_, self.batch_mu_, self.batch_sigma_ = Matrix(), Matrix(), Matrix(), Matrix()
+        self.fused = False
 
     # ---- graph ----------------------------------------------------------------------------------------
     def AddIncoming(self, e):
@@ -104,8 +118,14 @@ class Layer:
         self.add_or_overwrite_state_ = True
         self.add_or_overwrite_deriv_ = True
 
+    def UseBatchNormalization(self):
+        return self.batch_normalize_
+
     def NotifyStart(self):
-        pass
+        # src/layer.cc:520-525
+        if self.batch_normalize_:
+            self.gamma_optimizer_.NotifyStart(self.gamma_)
+            self.beta_optimizer_.NotifyStart(self.beta_)
 
     # ---- memory: src/layer.cc:252-288 ----------------------------------------------------------------
     def AllocateMemory(self, batch_size):
@@ -121,6 +141,84 @@ class Layer:
         if self.is_output_:
             self.loss_ = LossFunction.ChooseLossFunction(self.loss_function_)
             self.performance_ = LossFunction.ChooseLossFunction(self.performance_metric_)
+        if self.batch_normalize_:
+            # src/layer.cc:264-278.  Not part of the flat parameter buffer: ConvNet::Save writes edges only (convnet.cc:669-680)
+            C = self.num_channels_
+            for m, what in ((self.gamma_, "gamma"), (self.beta_, "beta"), (self.grad_gamma_, "grad gamma"), (self.grad_beta_, "grad beta"),
+                            (self.batch_mu_, "batch mu"), (self.batch_sigma_, "batch sigma"), (self.mu_, "mu"), (self.sigma_, "sigma")):
+                m.AllocateGPUMemory(1, C, f"{self.name_} bn {what}")
+            self.gamma_optimizer_.AllocateMemory(1, C)
+            self.beta_optimizer_.AllocateMemory(1, C)
+            self.gamma_.Set(1)
+            self.beta_.Set(0)
+            self.mu_.Set(0)
+            self.sigma_.Set(1)
+            for m in (self.grad_gamma_, self.grad_beta_, self.batch_mu_, self.batch_sigma_):
+                m.Set(0)
+
+    # ---- batch normalisation: src/layer.cc:452-510 --------------------------------------------------------------------
+    def ApplyBatchNormalization(self, train, relu=False):
+        """Unfused: the reference's call sequence.  Fused (``self.fused``): bn_fprop_act, which also applies this layer's ReLU when
+        ``relu`` (the caller then skips ApplyActivation)."""
+        if self.fused:
+            Matrix.BNFpropAct(self.state_, self.gamma_, self.beta_, self.mu_, self.sigma_, self.batch_mu_, self.batch_sigma_,
+                              self.bn_f_, self.bn_epsilon_, train, relu)
+            return
+        assert not relu
+        st = self.state_
+        batch_size = st.GetRows()
+        st.Reshape(-1, self.num_channels_)
+        n = st.GetRows()
+        inv_n = float(np.float32(1) / np.float32(n))   # 1.0f / n
+        if train:
+            st.SumRows(self.batch_mu_, 0, inv_n)
+            st.AddRowVec(self.batch_mu_, -1)
+            st.SqSumAxis(self.batch_sigma_, 0, inv_n, 0)
+            self.batch_sigma_.Add(self.bn_epsilon_)
+            self.batch_sigma_.Sqrt()
+            st.DivideByRowVec(self.batch_sigma_)
+            one_minus_f = float(np.float32(1) - np.float32(self.bn_f_))
+            self.mu_.Mult(self.bn_f_)
+            self.mu_.Add(self.batch_mu_, one_minus_f)
+            self.sigma_.Mult(self.bn_f_)
+            self.sigma_.Add(self.batch_sigma_, one_minus_f)
+        else:
+            st.AddRowVec(self.mu_, -1)
+            st.DivideByRowVec(self.sigma_)
+        st.MultByRowVec(self.gamma_)
+        st.AddRowVec(self.beta_, 1)
+        st.Reshape(batch_size, -1)
+
+    def ApplyDerivativeofBatchNormalization(self, fused_steps=None):
+        """The derivative and, as in the reference, the gamma / beta optimizer steps.  Fused: bn_bprop_fused (the state is only read);
+        with ``fused_steps`` (a list) the plain SGD steps are appended to it as data for the host's one sgd_momentum_step_multi launch
+        instead of running here — nothing reads gamma or beta between here and the end of the step."""
+        if self.fused:
+            Matrix.BNBpropFused(self.deriv_, self.state_, self.gamma_, self.beta_, self.batch_sigma_, self.grad_gamma_, self.grad_beta_)
+            for opt, g, p in ((self.gamma_optimizer_, self.grad_gamma_, self.gamma_), (self.beta_optimizer_, self.grad_beta_, self.beta_)):
+                item = opt.PlanFusedStep(g, p) if fused_steps is not None else None
+                if item is None:
+                    opt.Optimize(g, p)
+                else:
+                    fused_steps.append(item)
+            return
+        st, dv = self.state_, self.deriv_
+        batch_size = st.GetRows()
+        dv.Reshape(-1, self.num_channels_)
+        st.Reshape(-1, self.num_channels_)
+        n = st.GetRows()
+        st.AddRowVec(self.beta_, -1)
+        st.DivideByRowVec(self.gamma_)
+        dv.SumRows(self.grad_beta_, 0, float(np.float32(1) / np.float32(n)))
+        Matrix.BNBpropInplace(dv, st, self.grad_gamma_)
+        dv.MultByRowVec(self.gamma_)
+        dv.DivideByRowVec(self.batch_sigma_)
+        st.MultByRowVec(self.gamma_)
+        st.AddRowVec(self.beta_, 1)
+        st.Reshape(batch_size, -1)
+        dv.Reshape(batch_size, -1)
+        self.gamma_optimizer_.Optimize(self.grad_gamma_, self.gamma_)
+        self.beta_optimizer_.Optimize(self.grad_beta_, self.beta_)
 
     # ---- activation / dropout ----------------------------------------------------------------------------
     def ApplyActivation(self):

@@ -560,6 +560,30 @@ class Matrix:
         _chk(lib.sgd_momentum_step_normlimit(grad.GetMat(), param.GetMat(), history.GetMat(), float(l2_decay), float(gradient_clip),
                                              float(epsilon), float(momentum), float(norm), int(bool(constraint))), "sgd step + norm limit")
 
+    # ---- batch normalisation (src/matrix.cc:1077-1102; fused entries: include/convnet_hip.h) -------------------------------
+    @staticmethod
+    def BNBpropInplace(deriv, acts, dgamma):
+        _chk(lib.bn_bprop_inplace(deriv.GetMat(), acts.GetMat(), dgamma.GetMat()), "BNBpropInplace")
+
+    @staticmethod
+    def BNBprop(deriv, input, gamma, mu, sigma, target, scale_targets):
+        _chk(lib.bn_bprop(deriv.GetMat(), input.GetMat(), gamma.GetMat(), mu.GetMat(), sigma.GetMat(), target.GetMat(), float(scale_targets)),
+             "BNBprop")
+
+    @staticmethod
+    def BNGrad(deriv, input, mu, sigma, dgamma, dbeta):
+        _chk(lib.bn_grad(deriv.GetMat(), input.GetMat(), mu.GetMat(), sigma.GetMat(), dgamma.GetMat(), dbeta.GetMat()), "BNGrad")
+
+    @staticmethod
+    def BNFpropAct(state, gamma, beta, mu, sigma, batch_mu, batch_sigma, bn_f, bn_epsilon, train, relu):
+        _chk(lib.bn_fprop_act(state.GetMat(), gamma.GetMat(), beta.GetMat(), mu.GetMat(), sigma.GetMat(), batch_mu.GetMat(),
+                              batch_sigma.GetMat(), float(bn_f), float(bn_epsilon), int(bool(train)), int(bool(relu))), "bn_fprop_act")
+
+    @staticmethod
+    def BNBpropFused(deriv, state, gamma, beta, batch_sigma, dgamma, dbeta):
+        _chk(lib.bn_bprop_fused(deriv.GetMat(), state.GetMat(), gamma.GetMat(), beta.GetMat(), batch_sigma.GetMat(), dgamma.GetMat(),
+                                dbeta.GetMat()), "bn_bprop_fused")
+
     # ---- temp / ones pools (src/matrix.cc:633-676) -------------------------------------------------
     @staticmethod
     def RegisterTempMemory(size, why=""):

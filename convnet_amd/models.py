@@ -9,6 +9,9 @@ text so they can also be written to disk and fed to the reference's own binaries
 * ``cifar_local()`` — CIFAR-10 "conv + local" (two locally connected layers, LocalEdge).
 * ``vgg()``        — a VGG-style stack of 3x3 s1 p1 convs (configs[4]; no such pbtxt exists in the
                      reference).
+* ``vgg_bn()``     — the same with batch normalisation on every conv layer.
+* ``small_bn()``   — a small batch-normalised net for tests: conv-BN-ReLU, avgpool, conv-BN-ReLU + dropout, FC-BN-ReLU,
+                     softmax.
 tests/test_models.py checks the first two against the reference's files when they are mounted.
 """
 
@@ -201,6 +204,52 @@ def vgg(image_size=224, num_classes=1000, widths=(64, 128, 256, 512, 512), depth
     s += _layer("output", num_classes, "SOFTMAX")
     edges += _fc(prev, "fc6") + _fc("fc6", "fc7") + _fc("fc7", "output")
     return s + edges
+
+
+_BN = "  batch_normalize: true\n"
+# gamma runs the default WEIGHT optimizer, beta the default BIAS optimizer (src/convnet.cc:56-64)
+_BN_DEFAULTS = "".join(f"""{kind} {{
+  epsilon: 0.01
+  initial_momentum : 0.5
+  final_momentum : 0.9
+  momentum_transition_timescale : 2000
+}}
+""" for kind in ("default_weight_optimizer", "default_bias_optimizer")) + "\n"
+
+
+def vgg_bn(image_size=224, num_classes=1000, widths=(64, 128, 256, 512, 512), depths=(2, 2, 3, 3, 3), dropprob=0.5):
+    """vgg() with batch normalisation (batch_normalize: true) on all 13 conv layers, the standard way to train VGG-16."""
+    s = _header("vgg_bn") + _BN_DEFAULTS
+    s += _layer("input", 3, size=image_size)
+    edges, prev = "", "input"
+    for b, (w, d) in enumerate(zip(widths, depths), 1):
+        for i in range(1, d + 1):
+            name = f"conv{b}_{i}"
+            s += _layer(name, w, "RECTIFIED_LINEAR", extra=_BN)
+            edges += _conv(prev, name, 3, 1, 1)
+            prev = name
+        s += _layer(f"pool{b}", w)
+        edges += _pool(prev, f"pool{b}", 2, 2)
+        prev = f"pool{b}"
+    s += _layer("fc6", 4096, "RECTIFIED_LINEAR", dropprob) + _layer("fc7", 4096, "RECTIFIED_LINEAR", dropprob)
+    s += _layer("output", num_classes, "SOFTMAX")
+    edges += _fc(prev, "fc6") + _fc("fc6", "fc7") + _fc("fc7", "output")
+    return s + edges
+
+
+def small_bn(image_size=12, num_classes=10, dropprob=0.25, bn_f=0.9, relu=True):
+    """A small batch-normalised net for tests: conv-BN-ReLU, avgpool, conv-BN-ReLU + dropout, FC-BN-ReLU, softmax.  relu=False makes
+    the three BN layers LINEAR."""
+    act = "RECTIFIED_LINEAR" if relu else "LINEAR"
+    bn = _BN + f"  bn_f: {bn_f}\n"
+    s = _header("small_bn") + _BN_DEFAULTS
+    s += _layer("input", 3, size=image_size)
+    s += _layer("conv1", 16, act, extra=bn) + _layer("pool1", 16)
+    s += _layer("conv2", 24, act, dropprob, extra=bn) + _layer("fc3", 32, act, extra=bn)
+    s += _layer("output", num_classes, "SOFTMAX")
+    s += _conv("input", "conv1", 3, 1, 1, init_wt=0.3) + _pool("conv1", "pool1", 2, 2, kind="AVERAGE_POOL")
+    s += _conv("pool1", "conv2", 3, 1, 1, init_wt=0.3) + _fc("conv2", "fc3", init_wt=0.3) + _fc("fc3", "output", init_wt=0.3)
+    return s
 
 
 # forward MACs per image of a built net (for roofline accounting): see bench.py

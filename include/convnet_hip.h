@@ -333,6 +333,18 @@ int subtract_elementwise(cudamat* mat1, cudamat* mat2, cudamat* target);
 int mult_elementwise(cudamat* mat1, cudamat* mat2, cudamat* target, float scale_targets);
 int apply_sqrt(cudamat* mat, cudamat* target);
 
+/* ---- batch normalisation: cudamat.cuh:298-303 (src/matrix.cc:1077-1102; csrc/batch_norm.hip) ------------------------------------
+ * Column c of the (h, w) matrices is one channel's contiguous run (Layer::ApplyBatchNormalization reshapes the state to (-1, C)); the
+ * vectors are (1, w).  The reference's checks and error codes.  Sums run as per-wave slab partials combined in a fixed order (no
+ * atomics): bit-identical from call to call, and tolerance-equal (fp32 summation order) to the reference's 32-thread column loops.
+ *  bn_bprop_inplace: dgamma = mean(deriv·act); deriv -= dgamma·act; deriv -= mean(deriv)            (kBNBpropInplace)
+ *  bn_bprop        : cs = Σ(x-mu)·d / ((h-1)·sigma²); v = gamma·(d - (x-mu)·cs)/sigma; target = scale_targets·target + v - mean(v)
+ *  bn_grad         : dgamma = Σ (x-mu)/sigma · d; dbeta = Σ d  (sums, not means)                          (kBNGrad)
+ * Unlike eigenmat's bn_bprop_inplace (eigenmat.cc:2515-2537, which has no return statement), these return 0 on success. */
+int bn_bprop_inplace(cudamat* deriv, cudamat* act, cudamat* dgamma);
+int bn_bprop(cudamat* deriv, cudamat* input, cudamat* gamma, cudamat* mu, cudamat* sigma, cudamat* target, float scale_targets);
+int bn_grad(cudamat* deriv, cudamat* input, cudamat* mu, cudamat* sigma, cudamat* dgamma, cudamat* dbeta);
+
 /* ---- output layer (cudamat.cuh:249-262) ------------------------------------------------------------ */
 int softmax_row_major(cudamat* mat, cudamat* target);
 int softmax_row_major_multi(cudamat* mat, int numslices, cudamat* target);
@@ -383,6 +395,26 @@ int sgd_momentum_step_multi(int count, cudamat** grads, cudamat** params, cudama
 int softmax_ce_grad_correct(cudamat* logits, cudamat* labels, cudamat* probs, cudamat* deriv,
                             cudamat* correct_accum, float deriv_scale);
 int relu_dropout(rnd_struct* rnd_state, cudamat* mat, float dropprob, float scale);
+/* Batch normalisation of a layer's state in place, `state` read as (numel / C, C) with C = numel(gamma) (layer.cc:454: Reshape(-1, C));
+ * gamma, beta, mu, sigma, batch_mu, batch_sigma are C-float device vectors.
+ *  bn_fprop_act  : Layer::ApplyBatchNormalization(train) (src/layer.cc:452-480) [+ ReLULayer::ApplyActivation, layer.cc:549-551 when
+ *                  relu != 0].  train != 0: batch_mu = mean, batch_sigma = sqrt(biased variance + bn_epsilon) from ONE read of the
+ *                  state (per-wave Welford partials, Chan's combine in segment order; tolerance-equal to the reference's centred two
+ *                  passes SumRows / AddRowVec / SqSumAxis / Add / Sqrt), mu = bn_f·mu + (1-bn_f)·batch_mu, sigma likewise (the running
+ *                  average of the STD); then state = (state - m)·(gamma/s) + beta with (m, s) = the batch statistics (train) or
+ *                  (mu, sigma) (train == 0; batch_mu / batch_sigma are then not touched and may be empty).  Replaces 12 calls
+ *                  (9 passes over the state, 11 with the ReLU) by 3 passes; per element within a few ulp of the reference sequence.
+ *  bn_bprop_fused: Layer::ApplyDerivativeofBatchNormalization (src/layer.cc:482-510) without the optimizer steps: with
+ *                  y = (state - beta)/gamma recovered in registers, dbeta = mean(deriv), dgamma = mean(deriv·y),
+ *                  deriv = (deriv - dgamma·y - mean(deriv - dgamma·y))·gamma/batch_sigma.  `state` is only read (the reference
+ *                  rewrites it twice), so a weight gradient reading it on another stream needs no ordering.  Replaces 8 calls
+ *                  (19 passes) by 5 passes; tolerance-equal to the reference sequence.
+ * Both return ERROR_UNSUPPORTED for tensors of more than INT_MAX (2^31 - 1) floats, as do the three entries above.  Bit-identical
+ * from call to call. */
+int bn_fprop_act(cudamat* state, cudamat* gamma, cudamat* beta, cudamat* mu, cudamat* sigma, cudamat* batch_mu, cudamat* batch_sigma,
+                 float bn_f, float bn_epsilon, int train, int relu);
+int bn_bprop_fused(cudamat* deriv, cudamat* state, cudamat* gamma, cudamat* beta, cudamat* batch_sigma, cudamat* dgamma,
+                   cudamat* dbeta);
 /* Backward fusions: the producing kernel applies the consumer layer's ReLU' (and dropout' scale) in
  * its epilogue instead of a separate read-modify-write pass over the derivative
  * (Layer::ApplyDerivativeofDropout + ReLULayer::ApplyDerivativeOfActivation, src/layer.cc:399-413,556-558):
