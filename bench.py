@@ -9,15 +9,21 @@ exchange]) of the AlexNet-class model (BASELINE.json metric) on N MI355X GPUs of
 One process per GPU, each rank a full replica on its own synthetic batch, gradients averaged over RCCL
 (the reference's train_convnet_data_parallel semantics, src/convnet.cc:407-450).  With N > 1 the headline
 run is BASELINE's configuration 4 — AlexNet at a GLOBAL batch of 256 split over the ranks (256/N each:
-`scaling` "strong", `config4_value` = `value`), with the weak run (--batch images on EVERY rank) nested
+`scaling` "strong", `config4_value` = `value`), with --full the weak run (--batch images on EVERY rank) nested
 as `weak` and `exchange_ms_exposed` = the step with the exchange minus the same step without it;
 --weak swaps the roles, --global-batch G sets the global batch.  Rank 0 prints ONE JSON line.  `value` =
 images processed by all ranks / max-over-ranks wall time of K steps, bracketed by barrier +
 torch.cuda.synchronize().  The weight gradients run on a second HIP stream by default (--no-overlap-wgrad: one
-stream); `one_stream_ms_per_step` / `two_stream_ms_per_step` time the same K steps both ways after the headline
-region, without kernel timers, so that what the second stream is worth on the box is on every line.
+stream).
 
-Extra objects on the line:
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs, and
+prints the line; its `roofline` comes from the sampled kernel timers of the timed region alone.  --full adds every
+leg below, each after the timed region: `one_stream_ms_per_step` / `two_stream_ms_per_step` (the same K steps both
+ways, without kernel timers: what the second stream is worth on the box), the fully timed one-stream steps behind
+`roofline`, the objects listed below and, with N > 1, the other scaling mode and the replica check.  The --no-* options
+of those legs skip them within --full.
+
+Extra objects on the line with --full:
   roofline      dominant MFMA kernel: algorithmic flops / HIP-event time per launch, against the peak of the matrix pipe the
                 kernel EXECUTES on.  The kernel's duration is taken with the launch alone on the chip — four fully timed one-stream
                 steps of this process right after the timed region (the clock that agrees with rocprofv3's serialised kernel trace,
@@ -35,6 +41,8 @@ Extra objects on the line:
                 with N(0,1) operand planes, measured in the run by the library's probe (csrc/probe.hip) — the part clocks
                 to its power budget, ~0.74 of the nominal peak; `frac` stays against the nominal 416.7,
                 `frac_of_power_ceiling` travels beside it.
+                Without --full, `roofline` is the dominant kernel by its event spans in the timed region's sampled steps, with
+                `families` from the same spans and no `traffic`, `power_ceiling` or `one_stream`.
   fp32_mfma_path  the same step with every GEMM kernel on v_mfma_f32_32x32x2_f32 instead (--matrix-path fp32),
                 timed in this process right after the main run (rank 0, N=1 only), with its OWN `roofline` object
                 (dominant kernel, `frac` against the fp32 instruction's 157.3 TFLOP/s, `all_mfma_kernels`): the numbers
@@ -134,8 +142,8 @@ def live_pmc_traffic(kernel, args):
     tmp = tempfile.mkdtemp(prefix="bench_pmc_", dir="/tmp")
     env = dict(os.environ, TMPDIR="/tmp")
     child = [sys.executable, os.path.abspath(__file__), "--steps", "3", "--warmup", "1", "--batch", str(args.batch), "--model", args.model,
-             "--matrix-path", args.matrix_path, "--no-cpu-baseline", "--no-ref-host", "--no-other-path", "--no-kernel-timers", "--no-live-traffic"]
-    child += ["--no-power-probe", "--no-two-stream-leg"] + (["--unfused"] if args.unfused else []) + (["--no-overlap-wgrad"] if args.no_overlap_wgrad else []) + \
+             "--matrix-path", args.matrix_path, "--no-kernel-timers"]   # a plain run (no --full): no leg beyond the timed steps
+    child += (["--unfused"] if args.unfused else []) + (["--no-overlap-wgrad"] if args.no_overlap_wgrad else []) + \
              (["--side-stream-update"] if args.side_stream_update and not args.no_side_stream_update else [])
     sums = {}
     try:
@@ -399,10 +407,15 @@ def main():
     ap.add_argument("--no-side-stream-update", action="store_true", help="(the default now; accepted for older command lines)")
     ap.add_argument("--no-overlap-wgrad", action="store_true",
                     help="every edge's weight gradient on the main stream instead of on a second HIP stream beside the rest of the backward pass "
-                         "(bit-identical either way).  Round 6, same-call legs without kernel timers on two gpurun calls: two streams 9.44-9.51 ms, one "
-                         "stream 9.58 (profiles/r06_stream_legs.txt) — the second stream stays the default, and BOTH legs travel on every line "
+                         "(bit-identical either way).  Round 6, legs of one process without kernel timers, in two separate runs: two streams 9.44-9.51 ms, one "
+                         "stream 9.58 (profiles/r06_stream_legs.txt) — the second stream stays the default, and BOTH legs travel on every --full line "
                          "(`one_stream_ms_per_step`, `two_stream_ms_per_step`)")
     ap.add_argument("--overlap-wgrad", action="store_true", help="(the default; accepted for symmetry)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run every leg beyond the headline as well: the one- and two-stream legs, the fully timed "
+                         "one-stream steps behind `roofline`, the live PMC traffic passes, the power probe, the other matrix path, the CPU "
+                         "baseline, the reference host legs and, with N > 1, the other scaling mode and the replica check (each --no-* option "
+                         "below still skips its leg).  Without it a run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
     ap.add_argument("--no-two-stream-leg", action="store_true", help="skip the extra untimed-by-events runs of the same steps on one / two streams")
     ap.add_argument("--weak", action="store_true",
                     help="with --gpus N > 1: --batch images on EVERY rank as the headline run (weak scaling).  Default for N > 1 is "
@@ -444,6 +457,9 @@ def main():
                     help="after the timed steps, write what the last timed step computed (parameters, gradients, output probabilities) "
                          "as DIR/<name>.npy (rank 0; inputs and initial parameters are seeded, so two builds compare output for output)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: every leg after the timed region is --full's
+        args.no_two_stream_leg = args.no_other_path = args.no_live_traffic = args.no_power_probe = True
+        args.no_cpu_baseline = args.no_ref_host = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
 
@@ -573,7 +589,7 @@ def main():
     prof_one_stream, dt_one_stream, dt_two_stream = None, None, None
     side_update = args.side_stream_update and not args.no_side_stream_update
     two_main = (not args.no_overlap_wgrad) or side_update
-    if not args.no_kernel_timers:
+    if args.full and not args.no_kernel_timers:
         keep = (net.overlap_wgrad_, net.overlap_update_)
         net.overlap_wgrad_, net.overlap_update_ = False, False
         net.TrainOneBatch()
@@ -641,7 +657,7 @@ def main():
         return _lib.lib.convnet_hip_comm_size() if args.transport == "abi" else (dist.get_world_size() if dist.get_backend() == "nccl" else 0)
     rccl_ranks = rccl_count()
     strong_obj, weak_obj, compute_only_ms = None, None, None
-    if (world > 1 or (args.strong_selftest and exchange is not None)) and args.model == "alexnet" and 256 % world == 0 and not args.staged_input:
+    if args.full and (world > 1 or (args.strong_selftest and exchange is not None)) and args.model == "alexnet" and 256 % world == 0 and not args.staged_input:
         from convnet_amd.data_parallel import GradientExchange
         exchange.Close()
 
@@ -679,7 +695,7 @@ def main():
     # every replica must hold the same parameters after the same steps (the exchange's result is identical on all ranks and the
     # optimizer is deterministic): checked on the weak run's net, reported on the line
     replicas_identical = None
-    if dist.is_initialized() and world > 1:
+    if args.full and dist.is_initialized() and world > 1:
         import hashlib
         torch.cuda.synchronize()
         digest = hashlib.sha1(net.parameters_.ToNumpy().tobytes()).hexdigest()
@@ -748,7 +764,7 @@ def main():
             all_flops = sum(v["flops"] for v in mfma_rows.values())
             all_ms = sum(v["ms"] for v in mfma_rows.values())
             all_steps = 4 if prof_one_stream else timed_steps
-            traffic_fields = None
+            traffic_fields = None if args.full else {"traffic": None}
             if world == 1 and not args.no_live_traffic:
                 traffic_fields = live_pmc_traffic(dom_name, args)
             if traffic_fields is None:
@@ -812,8 +828,8 @@ def main():
             "value": round(value, 2), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 3),
             "one_stream_ms_per_step": round(1e3 * dt_one_stream / args.steps, 3) if dt_one_stream else None,
-            "stream_legs_note": "one_stream / two_stream_ms_per_step: the same K steps timed after the headline region without kernel timers (weight gradients on "
-                                "the main stream / on a second HIP stream); the headline region carries sampled HIP-event pairs (~0.07 ms per step)",
+            "stream_legs_note": "one_stream / two_stream_ms_per_step (--full only): the same K steps timed after the headline region without kernel timers "
+                                "(weight gradients on the main stream / on a second HIP stream); the headline region carries sampled HIP-event pairs (~0.07 ms per step)",
             "two_stream_ms_per_step": round(1e3 * dt_two_stream / args.steps, 3) if dt_two_stream else None,
             "host_enqueue_ms_per_step": round(1e3 * dt_enqueue / args.steps, 3), "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",

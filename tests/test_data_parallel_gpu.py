@@ -439,7 +439,7 @@ def test_bench_launches_two_ranks_and_prints_the_scale_line(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-device", "--steps", "3", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-ref-host", "--no-other-path", "--no-live-traffic"],
+                          "--full", "--no-cpu-baseline", "--no-ref-host", "--no-other-path", "--no-live-traffic"],
                          capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]

@@ -417,3 +417,31 @@ def test_train_loop_validate_polyak_lr_schedule_checkpoint_and_feature_extractio
     net2.Fprop(False)
     last = net2.GetLayerByName("output").GetState().ToNumpy().T
     assert np.array_equal(probs[32:], last[:8]) and np.array_equal(probs[:8], last[8:])
+
+
+def test_plain_bench_run_prints_the_headline_line_and_runs_no_full_leg(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: set-up, warm-up, the timed steps, --dump-outputs and ONE JSON
+    line with the headline fields; no leg of --full (stream legs, other matrix path, CPU baseline, reference host, live traffic, power
+    probe, fully timed one-stream steps) leaves a figure on the line."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=300, cwd=root)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "images/sec (fprop+bprop+wgrad) AlexNet 224x224 bs=256" and d["unit"] == "images/sec"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["value"] == pytest.approx(256 / (d["ms_per_step"] * 1e-3), rel=1e-3)
+    assert d["one_stream_ms_per_step"] is None and d["two_stream_ms_per_step"] is None
+    for k in ("fp32_mfma_path", "cpu_baseline", "ref_host", "ref_host_eager", "ref_host_dp", "weak", "strong", "replicas_identical"):
+        assert k not in d, k
+    r = d["roofline"]
+    assert r["dominant_by"] == "time in the timed region" and r["traffic"] is None and "power_ceiling" not in r and "one_stream" not in r
+    assert 0 < r["frac"] <= 1
+    names = sorted(p.name for p in dump.iterdir())
+    assert "parameters.npy" in names and "grad_parameters.npy" in names and any(n.startswith("state_") for n in names)

@@ -5,8 +5,8 @@ TAG=${1:-head}
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p "$O"; cd "$R" || exit 1
-Q="--no-cpu-baseline --no-ref-host --no-other-path --no-live-traffic"
-timeout 400 python bench.py > "$O/bench_n1.json" 2> "$O/bench_n1.err"; echo "bench rc=$?"; cut -c60-175 "$O/bench_n1.json"
+Q="--full --no-cpu-baseline --no-ref-host --no-other-path --no-live-traffic"
+timeout 400 python bench.py --full > "$O/bench_n1.json" 2> "$O/bench_n1.err"; echo "bench rc=$?"; cut -c60-175 "$O/bench_n1.json"
 cd /tmp && export TMPDIR=/tmp
 timeout 200 rocprofv3 --kernel-trace --stats -d "$O/prof" -o b --output-format csv -- python "$R/bench.py" --steps 10 --warmup 3 $Q > "$O/bench_under_rocprof.json" 2> "$O/rocprof.err"; echo "rocprof rc=$?"
 find "$O/prof" -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} "$O/bench_kernel_stats.csv"; rm -rf "$O/prof"

@@ -9,9 +9,9 @@ PREV=${2:-r05}   # the previous round's library for the same-call A/B: convnet_a
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/profile_$TAG
 mkdir -p "$O"; cd "$R" || exit 1
-Q="--no-cpu-baseline --no-ref-host --no-other-path --no-live-traffic"
-echo "== bench (default flags: what the driver runs)"
-timeout 500 python bench.py > "$O/bench_n1.json" 2> "$O/bench_n1.err"; echo "rc=$?"; cut -c1-230 "$O/bench_n1.json"
+Q="--full --no-cpu-baseline --no-ref-host --no-other-path --no-live-traffic"
+echo "== bench --full (every leg: live PMC traffic, CPU baseline, reference host, other matrix path)"
+timeout 500 python bench.py --full > "$O/bench_n1.json" 2> "$O/bench_n1.err"; echo "rc=$?"; cut -c1-230 "$O/bench_n1.json"
 echo "== one-stream bench"
 timeout 200 python bench.py --no-overlap-wgrad --no-side-stream-update $Q > "$O/bench_n1_one_stream.json" 2>/dev/null; cut -c60-160 "$O/bench_n1_one_stream.json"
 echo "== same-call A/B against the previous round's library (convnet_amd/lib/libconvnet_hip_$PREV.so), where it is present"
@@ -29,12 +29,12 @@ timeout 120 python tools/layer_bench.py > "$O/layer_bench.txt" 2>&1; grep -v amd
 timeout 120 python tools/pool_bench.py > "$O/pool_bench.txt" 2>&1
 echo "== per-GPU batch sweep (strong scaling of a global batch of 256: 128 / 64 / 32 images per GPU), both matrix paths"
 for b in 128 64 32; do
-  timeout 200 python bench.py --batch $b --steps 20 --warmup 5 --no-cpu-baseline --no-ref-host --no-live-traffic > "$O/bench_b$b.json" 2>/dev/null; echo "b=$b $(cut -c60-170 "$O/bench_b$b.json")"
+  timeout 200 python bench.py --batch $b --steps 20 --warmup 5 --full --no-cpu-baseline --no-ref-host --no-live-traffic > "$O/bench_b$b.json" 2>/dev/null; echo "b=$b $(cut -c60-170 "$O/bench_b$b.json")"
 done
 echo "== bench.py data-parallel paths on one rank (RCCL, 1-rank world): torch transport, C-ABI transport, strong-scaling flag"
 timeout 200 python bench.py --force-exchange --steps 12 --warmup 4 $Q > "$O/bench_dp1_torch.json" 2> "$O/bench_dp1_torch.err"; echo "rc=$?"; cut -c60-200 "$O/bench_dp1_torch.json"
 timeout 200 python bench.py --force-exchange --transport abi --steps 12 --warmup 4 $Q > "$O/bench_dp1_abi.json" 2> "$O/bench_dp1_abi.err"; echo "rc=$?"; cut -c60-200 "$O/bench_dp1_abi.json"
-timeout 60 python bench.py --gpus 2 > "$O/bench_gpus2_on_one_gpu.txt" 2>&1; echo "--gpus 2 on this box: rc=$? $(tail -1 "$O/bench_gpus2_on_one_gpu.txt")"
+timeout 60 python bench.py --gpus 2 --full > "$O/bench_gpus2_on_one_gpu.txt" 2>&1; echo "--gpus 2 on this box: rc=$? $(tail -1 "$O/bench_gpus2_on_one_gpu.txt")"
 echo "== other models"
 timeout 200 python bench.py --model vgg --batch 128 --steps 5 --warmup 2 $Q > "$O/bench_vgg_bs128.json" 2>/dev/null; cut -c1-200 "$O/bench_vgg_bs128.json"
 timeout 200 python bench.py --model alexnet_nin --steps 10 --warmup 3 $Q > "$O/bench_alexnet_nin.json" 2>/dev/null; cut -c1-200 "$O/bench_alexnet_nin.json"
