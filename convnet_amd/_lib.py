@@ -153,6 +153,16 @@ def _load():
     for n in ("localOutp", "localOutpGemm"):
         sig(n, None, M, M, M, S, S, S, ConvDesc, F, F)
     sig("localUpBiasAct", None, M, M, M, M, S, S, S, ConvDesc, F, I)
+    # spatio-temporal (3-D) convolution and response norm (csrc/conv3d.hip): the reference's five entries and the fused ones
+    for n in ("convUp3DGemm", "convDown3DGemm"):
+        sig(n, None, M, M, M, S, S, S, ConvDesc, F)
+    sig("convOutp3DGemm", None, M, M, M, S, S, S, ConvDesc, F, F)
+    for n in ("ResponseNormCrossMap3DGemm", "ResponseNormCrossMap3DRelu"):
+        sig(n, None, M, M, I, I, F, F, ctypes.c_bool, I)
+    sig("ResponseNormCrossMap3DUndoGemm", None, M, M, M, I, I, F, F, ctypes.c_bool, I)
+    sig("convUp3DBiasAct", None, M, M, M, M, S, S, S, ConvDesc, F, I)
+    sig("convDown3DMask", None, M, M, M, M, S, S, S, ConvDesc, F, F)
+    sig("convOutp3DBias", None, M, M, M, M, S, S, S, ConvDesc, F, F)
     sig("convDownMask", None, M, M, M, M, S, S, S, ConvDesc, F, F)
     sig("dotMask", I, M, M, M, M, F, F, F)
     sig("MaxPoolUndoRelu", None, M, M, M, M, S, S, ConvDesc, F)

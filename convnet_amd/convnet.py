@@ -163,6 +163,9 @@ class ConvNet(TrainLoopMixin):
                 e0 = l.incoming_edge_[0]
                 y, x, t = e0.GetNumModulesY(), e0.GetNumModulesX(), e0.GetNumModulesT()
             l.SetSize(y, x, t)
+            if t > 1 and l.UseBatchNormalization():
+                # the (-1, C) view of the state groups by channel only for one frame (time is the outermost index)
+                raise SystemExit(f"batch_normalize on layer {l.GetName()}: not supported on a layer with image_size_t > 1 ({t} frames)")
             self.log(f"Layer {l.GetName()}: {y}x{x}")
             for e in l.outgoing_edge_:
                 e.SetImageSize(y, x, t)

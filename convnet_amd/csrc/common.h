@@ -17,6 +17,8 @@ hipStream_t stream();
 void* workspace(size_t bytes);
 void* workspace_aux(size_t bytes);   // independent second arena (dgrad filter images)
 void* workspace_planes(size_t bytes);   // independent third arena (bf16 planes of a gather-GEMM's source tensor)
+void* workspace_banks(size_t bytes);    // independent fourth arena (class banks of a 3-D dgrad call, conv3d.hip)
+void* workspace_slabs(size_t bytes);    // independent fifth arena (the frames' split-K slabs of a batched 3-D wgrad call, conv3d.hip)
 // 256 bytes of device zeros (allocated once): where branch-free kernels point out-of-range loads.
 const float* zero_page();
 // 1: GEMM kernels form fp32 products on the bf16 matrix pipe from exact three-way operand splits (default); 0: fp32 MFMA.
@@ -99,6 +101,21 @@ inline int env_int(const char* name, int dflt) {
 #else
 #define CHIP_DIAG_KNOB(name, dflt) (dflt)
 #endif
+
+// Hooks the 3-D entries (conv3d.hip) hold around their frame launches of the 2-D paths; outside them nothing changes.
+//  * filter_planes_share(true .. false): a filter-bank preparation launch (bf16 planes, tap-major copy) that repeats the IMMEDIATELY
+//    preceding one — same bank, same destination in the scratch arena, same geometry — is skipped: its result is still there, nothing
+//    else has written that arena in between (any other preparation launch, and every other writer of the aux arena, forgets it).  filter_planes_shared(key) is the launchers' test.
+//  * wg_batch_begin(frames, arena, max_bytes) .. wg_batch_end(): gather_gemm.hip, "one reduction for the frames of a 3-D weight gradient".
+void filter_planes_share(bool on);
+bool filter_planes_shared(const long long* key, int n);   // true: skip the launch
+// Both hooks are process-wide state, like the library's one current stream: a host that issues a weight gradient or a bank
+// preparation from a second thread or stream in the MIDDLE of a 3-D call would be taken for one of its frames.  Not supported (the
+// library is not thread-safe, see stream()).
+void wg_batch_begin(int frames, void* (*slab_arena)(size_t bytes), size_t max_bytes);
+bool wg_batch_active();
+int wg_batch_frame();
+void wg_batch_end();
 
 inline int divup(int a, int b) { return (a + b - 1) / b; }
 inline size_t numel(const cudamat* m) { return (size_t)m->size[0] * (size_t)m->size[1]; }

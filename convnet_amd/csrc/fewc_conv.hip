@@ -452,6 +452,7 @@ bool gfc_try(const float* images, const float* filters, const float* bias, float
     once = true;
   }
   u32x4* planes = static_cast<u32x4*>(workspace_aux(A_BYTES + DUMP_BYTES));
+  (void)filter_planes_shared(nullptr, 0);   // another writer of the aux arena: a shared preparation (common.h) is forgotten
   {
     KernelTimer timer("filter_planes_kernel", "conv_fprop", 0.0, 4.0 * F * C * Ky * Kx + A_BYTES);
     hipLaunchKernelGGL(gfc_planes_kernel, dim3(divup(NCH * 2 * ROWS, 256)), dim3(256), 0, stream(), filters, planes, F);

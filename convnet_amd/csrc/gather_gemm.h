@@ -587,6 +587,8 @@ constexpr int WG_PITCH = WG_NB + 4;  // conflict-free ds_read_b128 across rows
 // slab reduce of the weight-gradient kernels (gather_gemm.hip): dst (and the fused bias row) = scaleTargets*dst + scaleOutput * sum of
 // the `splits` slabs of `total` floats in p.partial, in fixed order; two levels when groups > 1 (stage area behind the slabs)
 void wg_reduce_launch(const WGParams& p, size_t total, int splits, int groups, const char* op);
+// a frame of a batched 3-D weight gradient (common.h: wg_batch_begin): where its slabs go, or nullptr outside a batch
+float* wg_batch_partial(const WGParams& p, size_t total, int splits);
 // wgw_kernel (wgrad_wide.hip): takes the launch and returns true when the wide tile is selected (convnet_hip_set_wgrad_tile) and applies
 bool wgw_try(WGParams& p, bool vec, bool split_products, const char* op, double flops, double exec);
 

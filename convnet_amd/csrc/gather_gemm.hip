@@ -1249,7 +1249,7 @@ __global__ __launch_bounds__(WM* WN * 64) void wg_kernel(const WGParams p) {
     __syncthreads();
   }
 
-  const bool fin = p.splits == 1;
+  const bool fin = p.splits == 1 && !p.partial;   // (a 3-D call's frames write slabs even unsplit: wg_batch_partial)
   const int KB = p.K + (p.bias_dst ? 1 : 0);
   float* out = fin ? p.dst : p.partial + (size_t)split * KB * p.F;
   if constexpr (TS == 32 && WM == 2 && WN == 2 && MT == 2 && NTL == 2) {
@@ -1692,6 +1692,62 @@ void wg_reduce_launch(const WGParams& p, size_t total, int splits, int groups, c
                      p.scaleTargets, p.scaleOutput);
 }
 
+// ---- one reduction for the frames of a 3-D weight gradient (conv3d.hip) -------------------------------------------------------------
+// Between wg_batch_begin(frames, arena, max_bytes) and wg_batch_end() every weight-gradient launch is one frame of the same geometry: it
+// writes its split-K slabs (one slab when unsplit) at its own offset of ONE arena and skips its reduce; wg_batch_end() sums all
+// frames x splits slabs in fixed order (two levels when many) and applies scaleTargets / scaleOutput once: dW is written once per call.
+// The arena is the caller's (`slab_arena`, an arena of its own): the slabs outlive the frame launches, and workspace() is taken in
+// between by the frames themselves and by the column sum of a fused bias gradient (conv_outp_impl -> sum_by_axis).  Slabs above
+// `max_bytes` end the batch at its first frame; the caller then accumulates frame by frame.  Off (no batch) every launch is exactly
+// what it was.
+namespace {
+struct WGBatch {
+  int frames = 0, frame = 0, splits = 0;
+  size_t total = 0;
+  void* (*arena)(size_t) = nullptr;
+  size_t max_bytes = 0;
+  WGParams last;
+};
+WGBatch g_wgb;
+}  // namespace
+void wg_batch_begin(int frames, void* (*slab_arena)(size_t), size_t max_bytes) {
+  g_wgb = WGBatch{};
+  g_wgb.frames = frames;
+  g_wgb.arena = slab_arena;
+  g_wgb.max_bytes = max_bytes;
+}
+bool wg_batch_active() { return g_wgb.frames > 0; }
+int wg_batch_frame() { return g_wgb.frame; }
+float* wg_batch_partial(const WGParams& p, size_t total, int splits) {
+  WGBatch& b = g_wgb;
+  if (!b.frames) return nullptr;
+  CHIP_REQUIRE(b.frame < b.frames);
+  const size_t S = (size_t)b.frames * splits;
+  const size_t bytes = sizeof(float) * total * (S + (S > 64 ? 32 : 0));
+  if (b.frame == 0) {
+    if (bytes > b.max_bytes) {
+      b.frames = 0;
+      return nullptr;
+    }
+    b.splits = splits;
+    b.total = total;
+  }
+  CHIP_REQUIRE(b.splits == splits && b.total == total);   // every frame has the same geometry
+  float* arena = static_cast<float*>(b.arena(bytes));
+  b.last = p;
+  b.last.partial = arena;
+  return arena + (size_t)b.frame++ * splits * total;
+}
+void wg_batch_end() {
+  WGBatch& b = g_wgb;
+  if (b.frames && b.frame > 0) {
+    CHIP_REQUIRE(b.frame == b.frames);
+    const int S = b.frames * b.splits;
+    wg_reduce_launch(b.last, b.total, S, S > 64 ? 32 : 1, "conv_wgrad");
+  }
+  b.frames = 0;
+}
+
 void gg_reduce_launch(const GGParams& p, size_t dst_elems, int splits, const char* op) {
   KernelTimer timer("gg_reduce_kernel", op, 0.0, sizeof(float) * (double)dst_elems * (splits + 1));
   size_t nb = (dst_elems + 255) / 256;
@@ -1767,7 +1823,9 @@ void wg_launch_cfg(WGParams& p, bool vec) {
   splits = divup(p.chunks_total, p.chunks_per_split);
   p.splits = splits;
   const int groups = splits > 64 ? 32 : 1;   // two-level reduce when the slab count dwarfs the tile
-  p.partial = splits > 1 ? static_cast<float*>(workspace(sizeof(float) * total * (splits + (groups > 1 ? groups : 0)))) : nullptr;
+  float* const frame_slabs = wg_batch_partial(p, total, splits);   // a frame of a 3-D weight gradient: its slabs, reduced once per call
+  p.partial = frame_slabs ? frame_slabs
+                          : splits > 1 ? static_cast<float*>(workspace(sizeof(float) * total * (splits + (groups > 1 ? groups : 0)))) : nullptr;
   dim3 grid(((tiles * splits + 7) / 8) * 8), block(WM * WN * 64);
   static const std::string kname_f = "wg_kernel<" + std::to_string(WM) + "," + std::to_string(WN) + "," + std::to_string(MT) + "," + std::to_string(NTL) + (TS == 16 ? ",x16>" : ">");
   static const std::string kname_s = kname_f.substr(0, kname_f.size() - 1) + ",split>";
@@ -1786,7 +1844,7 @@ void wg_launch_cfg(WGParams& p, bool vec) {
       hipLaunchKernelGGL((wg_kernel<WM, WN, MT, NTL, false, TS>), grid, block, lds, stream(), p);
     }
   }
-  if (splits > 1) {
+  if (splits > 1 && !frame_slabs) {
     KernelTimer timer("wg_reduce_kernel", t_op, 0.0, sizeof(float) * (double)total * (splits + 1));
     size_t nb = (total + 255) / 256;
     if (nb > 4096) nb = 4096;
@@ -1945,8 +2003,11 @@ void conv_up_impl(cudamat* images, cudamat* filters, cudamat* bias, cudamat* tar
       float* wt = static_cast<float*>(workspace_aux(sizeof(float) * welems));
       int nb = (int)((welems + 255) / 256);
       if (nb > 2048) nb = 2048;
-      KernelTimer timer("filter_tapmajor_kernel", "conv_fprop", 0.0, 8.0 * welems);
-      hipLaunchKernelGGL(filter_tapmajor_kernel, dim3(nb), dim3(256), 0, stream(), filters->data_device, wt, g.F, g.C, p.TYX);
+      const long long key[6] = {2, (long long)(uintptr_t)filters->data_device, (long long)(uintptr_t)wt, g.F, g.C, p.TYX};
+      if (!filter_planes_shared(key, 6)) {
+        KernelTimer timer("filter_tapmajor_kernel", "conv_fprop", 0.0, 8.0 * welems);
+        hipLaunchKernelGGL(filter_tapmajor_kernel, dim3(nb), dim3(256), 0, stream(), filters->data_device, wt, g.F, g.C, p.TYX);
+      }
       p.A = wt;
     }
     p.KC = g.C;
@@ -2105,6 +2166,7 @@ static void conv_down_impl(cudamat* derivs, cudamat* filters, cudamat* targets, 
       } else if (welems > 0) {
         int nb = (int)((welems + 255) / 256);
         if (nb > 2048) nb = 2048;
+        (void)filter_planes_shared(nullptr, 0);   // another writer of the aux arena: a shared preparation is forgotten
         KernelTimer timer("dgrad_filter_kernel", "conv_dgrad", 0.0, 8.0 * welems);
         hipLaunchKernelGGL(dgrad_filter_kernel, dim3(nb), dim3(256), 0, stream(), filters->data_device, wc, g.F, g.C, g.Ky,
                            g.Kx, cy, cx, g.sy, g.sx, TYc, TXc, tapm ? 1 : 0);
@@ -2186,7 +2248,8 @@ static void conv_outp_impl(cudamat* images, cudamat* derivs, cudamat* targets, c
     view.size[1] = g.F;
     view.is_trans = 0;
     view.owns_data = 0;
-    CHIP_REQUIRE(sum_by_axis(&view, bias_grad, 0, scaleOutput, scaleTargets) == 0);
+    // (a later frame of a batched 3-D call accumulates: only its dW waits for the call's one reduction)
+    CHIP_REQUIRE(sum_by_axis(&view, bias_grad, 0, scaleOutput, wg_batch_active() && wg_batch_frame() > 1 ? 1.f : scaleTargets) == 0);
   }
 }
 

@@ -962,6 +962,107 @@ __global__ void __launch_bounds__(512) rnorm_undo_fast_kernel(const float* __res
   }
 }
 
+// ---- pooling over time --------------------------------------------------------------------------------------------------------------
+// Activations (N, W, H, C, T) with time outermost (include/convnet_hip.h); py / px / pt are the ConvDesc (negated) paddings.  The
+// streaming gathers above with a time extent: used when a tensor of T > 1 frames is pooled with Kt > 1, stride_t > 1 or padding_t != 0.
+struct Pool3DGeo {
+  int N, C, H, W, T, Ky, Kx, Kt, sy, sx, st, py, px, pt, My, Mx, Mt;
+  int nvec;   // ceil(N/4)
+};
+
+// work item = (output frame ot, channel c, output pixel, image quad q); q fastest so a wave reads 1 KiB runs.
+template <bool MAX>
+__global__ void pool3d_fwd_kernel(const float* __restrict__ in, float* __restrict__ out, Pool3DGeo g, float st, float so, bool vec) {
+  const size_t total = (size_t)g.Mt * g.C * g.My * g.Mx * g.nvec;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int q = (int)(i % g.nvec);
+    size_t r = i / g.nvec;
+    const int ox = (int)(r % g.Mx);
+    r /= g.Mx;
+    const int oy = (int)(r % g.My);
+    r /= g.My;
+    const int c = (int)(r % g.C);
+    const int ot = (int)(r / g.C);
+    const int n = 4 * q;
+    const int y0 = max(0, oy * g.sy + g.py), y1 = min(g.H, oy * g.sy + g.py + g.Ky);
+    const int x0 = max(0, ox * g.sx + g.px), x1 = min(g.W, ox * g.sx + g.px + g.Kx);
+    const int t0 = max(0, ot * g.st + g.pt), t1 = min(g.T, ot * g.st + g.pt + g.Kt);
+    f32x4 acc = MAX ? f32x4{-FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX} : f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int t = t0; t < t1; ++t)
+      for (int y = y0; y < y1; ++y)
+        for (int x = x0; x < x1; ++x) {
+          const f32x4 v = ldv(in + (((size_t)(t * g.C + c) * g.H + y) * g.W + x) * g.N + n, n, g.N, vec);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[e] = MAX ? (acc[e] < v[e] ? v[e] : acc[e]) : acc[e] + v[e];
+        }
+    if (!MAX) {
+      const float cnt = (float)((y1 - y0) * (x1 - x0) * (t1 - t0));   // the CLIPPED box (regionSize)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[e] = acc[e] / cnt;
+    }
+    float* op = out + (((size_t)(ot * g.C + c) * g.My + oy) * g.Mx + ox) * g.N + n;
+    f32x4 res = so * acc;
+    if (st != 0.f) res = st * ldv(op, n, g.N, vec) + res;
+    stv(op, res, n, g.N, vec);
+  }
+}
+
+// work item = (input frame it, c, input pixel, image quad): a gather over the output boxes that contain the element.  MAX: every box
+// whose maximum equals this input routes its derivative here (all ties count); AVG: each box gives d_out / |clipped box|.
+template <bool MAX>
+__global__ void pool3d_undo_kernel(const float* __restrict__ images, const float* __restrict__ grads, const float* __restrict__ acts,
+                                   float* __restrict__ out, Pool3DGeo g, float st, bool vec, bool relu_mask) {
+  const size_t total = (size_t)g.T * g.C * g.H * g.W * g.nvec;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int q = (int)(i % g.nvec);
+    size_t r = i / g.nvec;
+    const int ix = (int)(r % g.W);
+    r /= g.W;
+    const int iy = (int)(r % g.H);
+    r /= g.H;
+    const int c = (int)(r % g.C);
+    const int it = (int)(r / g.C);
+    const int n = 4 * q;
+    int oy0, oy1, ox0, ox1, ot0, ot1;
+    cover(iy, g.py, g.Ky, g.sy, g.My, oy0, oy1);
+    cover(ix, g.px, g.Kx, g.sx, g.Mx, ox0, ox1);
+    cover(it, g.pt, g.Kt, g.st, g.Mt, ot0, ot1);
+    // (i - pad) / s truncates towards zero: an input left of / before the first window would get hi = 1 without this
+    const bool inside = ix >= g.px && iy >= g.py && it >= g.pt;
+    const size_t t = (((size_t)(it * g.C + c) * g.H + iy) * g.W + ix) * g.N + n;
+    f32x4 img = {0.f, 0.f, 0.f, 0.f};
+    if (MAX) img = ldv(images + t, n, g.N, vec);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if (inside)
+      for (int ot = ot0; ot < ot1; ++ot) {
+        const float rt = (float)(min(g.T, g.pt + ot * g.st + g.Kt) - max(0, g.pt + ot * g.st));
+        for (int oy = oy0; oy < oy1; ++oy) {
+          const float ry = (float)(min(g.H, g.py + oy * g.sy + g.Ky) - max(0, g.py + oy * g.sy));
+          for (int ox = ox0; ox < ox1; ++ox) {
+            const size_t o = (((size_t)(ot * g.C + c) * g.My + oy) * g.Mx + ox) * g.N + n;
+            const f32x4 gv = ldv(grads + o, n, g.N, vec);
+            if (MAX) {
+              const f32x4 av = ldv(acts + o, n, g.N, vec);
+#pragma unroll
+              for (int e = 0; e < 4; ++e) acc[e] += (img[e] == av[e]) ? gv[e] : 0.f;
+            } else {
+              const float rx = (float)(min(g.W, g.px + ox * g.sx + g.Kx) - max(0, g.px + ox * g.sx));
+              const float inv = 1.0f / (rx * ry * rt);
+#pragma unroll
+              for (int e = 0; e < 4; ++e) acc[e] += gv[e] * inv;
+            }
+          }
+        }
+      }
+    if (st != 0.f) acc = st * ldv(out + t, n, g.N, vec) + acc;
+    if (MAX && relu_mask) {   // fused ReLU' of the layer below: its state IS `images`
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[e] = img[e] > 0.f ? acc[e] : 0.f;
+    }
+    stv(out + t, acc, n, g.N, vec);
+  }
+}
+
 namespace {
 
 inline bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -1110,6 +1211,31 @@ bool rnorm_undo_fast(const float* dout, const float* in, float* out, size_t locs
   return true;
 }
 
+void pool3d_fwd_launch(bool max, const float* in, float* out, const Pool3DGeo& g, float scaleTargets, float scaleOutput, bool vec) {
+  const size_t total = (size_t)g.Mt * g.C * g.My * g.Mx * g.nvec;
+  // algorithmic bytes: read the input once, write the output once
+  KernelTimer timer(max ? "pool3d_fwd_kernel<max>" : "pool3d_fwd_kernel<avg>", "pool_fwd", 0.0,
+                    4.0 * g.N * g.C * ((double)g.H * g.W * g.T + (double)g.My * g.Mx * g.Mt));
+  if (max)
+    hipLaunchKernelGGL(pool3d_fwd_kernel<true>, dim3(grid_for(total)), dim3(256), 0, stream(), in, out, g, scaleTargets, scaleOutput, vec);
+  else
+    hipLaunchKernelGGL(pool3d_fwd_kernel<false>, dim3(grid_for(total)), dim3(256), 0, stream(), in, out, g, scaleTargets, scaleOutput, vec);
+}
+
+void pool3d_undo_launch(bool max, const float* images, const float* grads, const float* acts, float* out, const Pool3DGeo& g,
+                        float scaleTargets, bool vec, bool relu_mask) {
+  const size_t total = (size_t)g.T * g.C * g.H * g.W * g.nvec;
+  const double in_el = (double)g.H * g.W * g.T, out_el = (double)g.My * g.Mx * g.Mt;
+  KernelTimer timer(max ? "pool3d_undo_kernel<max>" : "pool3d_undo_kernel<avg>", "pool_undo", 0.0,
+                    4.0 * g.N * g.C * ((max ? 2.0 : 1.0) * in_el + (max ? 2.0 : 1.0) * out_el + (scaleTargets != 0.f ? in_el : 0.0)));
+  if (max)
+    hipLaunchKernelGGL(pool3d_undo_kernel<true>, dim3(grid_for(total)), dim3(256), 0, stream(), images, grads, acts, out, g, scaleTargets,
+                       vec, relu_mask);
+  else
+    hipLaunchKernelGGL(pool3d_undo_kernel<false>, dim3(grid_for(total)), dim3(256), 0, stream(), images, grads, acts, out, g, scaleTargets,
+                       vec, false);
+}
+
 PoolGeo pool_geo(const Shape4D* in, const Shape4D* out, const ConvDesc& d, const cudamat* mi, const cudamat* mo) {
   PoolGeo g;
   g.N = in->shape[0]; g.W = in->shape[1]; g.H = in->shape[2]; g.C = in->shape[3];
@@ -1118,11 +1244,36 @@ PoolGeo pool_geo(const Shape4D* in, const Shape4D* out, const ConvDesc& d, const
   g.nvec = divup(g.N, 4);
   g.xper = g.xtotal = g.xrows = g.xbx = 0;
   CHIP_REQUIRE(out->shape[0] == g.N && out->shape[3] == g.C);
-  CHIP_REQUIRE(d.num_input_channels == g.C && d.num_output_channels == g.C);  // cudamat_conv_gemm.cu:1150-1160
+  // T frames of d.num_input_channels channels behind a window without a time extent are simply more channels (time is outermost)
+  const bool frames = d.num_input_channels > 0 && g.C % d.num_input_channels == 0 && d.kernel_size_t <= 1 && d.stride_t <= 1 && d.padding_t == 0;
+  CHIP_REQUIRE((d.num_input_channels == g.C || frames) && d.num_output_channels == d.num_input_channels);  // cudamat_conv_gemm.cu:1150-1160
   CHIP_REQUIRE(mi->size[0] == g.N && mi->size[1] == g.H * g.W * g.C);
   CHIP_REQUIRE(mo->size[0] == g.N && mo->size[1] == g.My * g.Mx * g.C);
   CHIP_REQUIRE(g.My == (g.H - 2 * g.py - g.Ky) / g.sy + 1 && g.Mx == (g.W - 2 * g.px - g.Kx) / g.sx + 1);
   return g;
+}
+
+// A window with a time extent on a tensor of T > 1 frames (shape[3] = C·T): fills the geometry of the pool3d kernels.  T == 1, or
+// kernel_size_t <= 1 with stride_t <= 1 and padding_t == 0, is the 2-D case above and returns false.
+bool pool_time_geo(const Shape4D* in, const Shape4D* out, const ConvDesc& d, const cudamat* mi, const cudamat* mo, Pool3DGeo& g) {
+  const int C = d.num_input_channels;
+  if (C <= 0 || in->shape[3] == C || in->shape[3] % C != 0) return false;
+  if (d.kernel_size_t <= 1 && d.stride_t <= 1 && d.padding_t == 0) return false;
+  g.N = in->shape[0]; g.W = in->shape[1]; g.H = in->shape[2]; g.C = C; g.T = in->shape[3] / C;
+  g.Mx = out->shape[1]; g.My = out->shape[2];
+  g.Ky = d.kernel_size_y; g.Kx = d.kernel_size_x; g.Kt = d.kernel_size_t > 1 ? d.kernel_size_t : 1;
+  g.sy = d.stride_y; g.sx = d.stride_x; g.st = d.stride_t > 1 ? d.stride_t : 1;
+  g.py = d.padding_y; g.px = d.padding_x; g.pt = d.padding_t;
+  g.nvec = divup(g.N, 4);
+  CHIP_REQUIRE(d.num_output_channels == C && out->shape[0] == g.N && out->shape[3] % C == 0);
+  g.Mt = out->shape[3] / C;
+  CHIP_REQUIRE(mi->size[0] == g.N && (size_t)mi->size[1] == (size_t)g.H * g.W * g.C * g.T);
+  CHIP_REQUIRE(mo->size[0] == g.N && (size_t)mo->size[1] == (size_t)g.My * g.Mx * g.C * g.Mt);
+  CHIP_REQUIRE(g.sy > 0 && g.sx > 0 && g.Ky > 0 && g.Kx > 0);
+  CHIP_REQUIRE(-g.py < g.Ky && -g.px < g.Kx && -g.pt < g.Kt);   // no window lies wholly in the padding (an empty box has no max and no mean)
+  CHIP_REQUIRE(g.My == (g.H - 2 * g.py - g.Ky) / g.sy + 1 && g.Mx == (g.W - 2 * g.px - g.Kx) / g.sx + 1 &&
+               g.Mt == (g.T - 2 * g.pt - g.Kt) / g.st + 1 && g.My > 0 && g.Mx > 0 && g.Mt > 0);
+  return true;
 }
 
 // 10*K+S when a compile-time (K, S) instantiation exists and its 3-D grid is legal, else 0 (generic kernel)
@@ -1145,6 +1296,11 @@ inline dim3 pool_xcd_grid(PoolGeo& g, int xblocks, int rows, dim3 plain) {
 
 template <bool MAX>
 void pool_fwd(cudamat* images, cudamat* targets, Shape4D* is, Shape4D* ts, const ConvDesc& d, float st, float so) {
+  Pool3DGeo g3;
+  if (pool_time_geo(is, ts, d, images, targets, g3)) {
+    pool3d_fwd_launch(MAX, images->data_device, targets->data_device, g3, st, so, g3.N % 4 == 0 && a16(images->data_device) && a16(targets->data_device));
+    return;
+  }
   PoolGeo g = pool_geo(is, ts, d, images, targets);
   const bool vec = g.N % 4 == 0 && a16(images->data_device) && a16(targets->data_device);
   const size_t total = (size_t)g.C * g.My * g.Mx * g.nvec;
@@ -1171,6 +1327,14 @@ void pool_fwd(cudamat* images, cudamat* targets, Shape4D* is, Shape4D* ts, const
 template <bool MAX>
 void pool_undo(cudamat* images, cudamat* grads, cudamat* acts, cudamat* targets, Shape4D* in_shape, Shape4D* pooled_shape,
                const ConvDesc& d, float st, bool relu_mask = false) {
+  Pool3DGeo g3;
+  if (pool_time_geo(in_shape, pooled_shape, d, targets, grads, g3)) {
+    const bool v3 = g3.N % 4 == 0 && a16(grads->data_device) && a16(targets->data_device) &&
+                    (!MAX || (a16(images->data_device) && a16(acts->data_device)));
+    pool3d_undo_launch(MAX, MAX ? images->data_device : nullptr, grads->data_device, MAX ? acts->data_device : nullptr, targets->data_device, g3,
+                       st, v3, relu_mask);
+    return;
+  }
   PoolGeo g = pool_geo(in_shape, pooled_shape, d, targets, grads);
   const bool vec = g.N % 4 == 0 && a16(grads->data_device) && a16(targets->data_device) &&
                    (!MAX || (a16(images->data_device) && a16(acts->data_device)));
@@ -1252,6 +1416,8 @@ static bool mask_geo_ok(const PoolGeo& g, const cudamat* images, const cudamat* 
 }
 int MaxPoolMask(cudamat* images, cudamat* targets, cudamat* mask, Shape4D* images_shape, Shape4D* targets_shape, ConvDesc conv_desc) {
   if (!images->on_device || !targets->on_device || !mask->on_device) return ERROR_NOT_ON_DEVICE;
+  Pool3DGeo g3;
+  if (pool_time_geo(images_shape, targets_shape, conv_desc, images, targets, g3)) return ERROR_UNSUPPORTED;   // the mask pair is 2-D only
   PoolGeo g = pool_geo(images_shape, targets_shape, conv_desc, images, targets);
   if (!mask_geo_ok(g, images, targets, nullptr, mask)) return ERROR_UNSUPPORTED;
   KernelTimer timer("pool_fwd_mask_kernel<max>", "pool_fwd", 0.0, (double)g.N * g.C * (4.0 * g.H * g.W + 6.0 * g.My * g.Mx));
@@ -1268,6 +1434,8 @@ int MaxPoolUndoMask(cudamat* maxGrads, cudamat* mask, cudamat* targets, Shape4D*
   // MaxPoolUndoRelu masks the WHOLE result, accumulated target included, by input > 0 — known from the masks only where the input is some
   // window's maximum: the fused ReLU' is offered for an overwriting undo only
   if (relu && scaleTargets != 0.f) return ERROR_UNSUPPORTED;
+  Pool3DGeo g3;
+  if (pool_time_geo(targets_shape, maxGrads_shape, conv_desc, targets, maxGrads, g3)) return ERROR_UNSUPPORTED;
   PoolGeo g = pool_geo(targets_shape, maxGrads_shape, conv_desc, targets, maxGrads);
   if (!mask_geo_ok(g, targets, maxGrads, nullptr, mask)) return ERROR_UNSUPPORTED;
   KernelTimer timer("pool_undo_mask_kernel<max>", "pool_undo", 0.0,

@@ -68,7 +68,7 @@ struct Arena {
   void* p = nullptr;
   size_t cap = 0;
 };
-std::map<hipStream_t, Arena> g_arena[3];
+std::map<hipStream_t, Arena> g_arena[5];
 
 void* arena_get(int which, size_t bytes, size_t slack) {
   flush_pending();
@@ -89,6 +89,12 @@ void* workspace(size_t bytes) { return arena_get(0, bytes, size_t(1) << 22); }
 void* workspace_aux(size_t bytes) { return arena_get(1, bytes, size_t(1) << 20); }
 // Third arena: the bf16 planes of the source tensor of one gather-GEMM call (patch_gemm.hip), alive beside the other two.
 void* workspace_planes(size_t bytes) { return arena_get(2, bytes, size_t(1) << 22); }
+// Fourth arena: the per-class filter banks of one 3-D dgrad call (conv3d.hip), alive across all of its frame launches, each of which
+// takes the other three.
+void* workspace_banks(size_t bytes) { return arena_get(3, bytes, size_t(1) << 20); }
+// Fifth arena: the split-K slabs of ALL frames of one batched 3-D weight gradient (conv3d.hip hands it to wg_batch_begin): they stay alive
+// until the call's one reduction while the frame launches — and the column sums of a fused bias gradient — take workspace().
+void* workspace_slabs(size_t bytes) { return arena_get(4, bytes, size_t(1) << 20); }
 
 const float* zero_page() {
   static float* z = nullptr;

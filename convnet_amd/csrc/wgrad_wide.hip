@@ -253,7 +253,7 @@ __global__ __launch_bounds__(256, 1) void wgw_kernel(const WGParams p) {
   }
 
   // ---- write-out --------------------------------------------------------------------------------------------------------------------
-  const bool fin = p.splits == 1;
+  const bool fin = p.splits == 1 && !p.partial;   // (a 3-D call's frames write slabs even unsplit: wg_batch_partial)
   const int KB = p.K + (p.bias_dst ? 1 : 0);
   float* out = fin ? p.dst : p.partial + (size_t)split * KB * p.F;
   if (p.wide) {
@@ -358,14 +358,16 @@ void wgw_launch(WGParams& p, const char* op, double flops, double exec) {
   splits = divup(p.chunks_total, p.chunks_per_split);
   p.splits = splits;
   const int groups = splits > 64 ? 32 : 1;
-  p.partial = splits > 1 ? static_cast<float*>(workspace(sizeof(float) * total * (splits + (groups > 1 ? groups : 0)))) : nullptr;
+  float* const frame_slabs = wg_batch_partial(p, total, splits);   // a frame of a 3-D weight gradient (gather_gemm.h)
+  p.partial = frame_slabs ? frame_slabs
+                          : splits > 1 ? static_cast<float*>(workspace(sizeof(float) * total * (splits + (groups > 1 ? groups : 0)))) : nullptr;
   dim3 grid(((tiles * splits + 7) / 8) * 8), block(256);
   {
     KernelTimer timer(NTL == 4 ? "wgw_kernel<256x256,split>" : "wgw_kernel<256x192,split>",
                       op, flops, 0.0, exec);
     hipLaunchKernelGGL((wgw_kernel<NTL>), grid, block, lds, stream(), p);
   }
-  if (splits > 1) wg_reduce_launch(p, total, splits, groups, op);
+  if (splits > 1 && !frame_slabs) wg_reduce_launch(p, total, splits, groups, op);
 }
 
 }  // namespace

@@ -343,7 +343,9 @@ class EdgeWithWeight(Edge):
 
 
 class ConvEdge(EdgeWithWeight):
-    """src/conv_edge.{h,cc} (2-D; image_size_t == 1 in all target configs)."""
+    """src/conv_edge.{h,cc}.  A source layer with image_size_t > 1 frames makes the edge a spatio-temporal (3-D) convolution
+    (kernel_size_t, stride_t; time is the outermost index of activations and bank, include/convnet_hip.h): it then issues the reference's
+    Conv3D* calls, the shared bias is added per output frame and its gradient summed over the frames (conv_edge.cc:153-168, 223-242)."""
     can_fuse_mask = True
 
     def __init__(self, c):
@@ -363,12 +365,20 @@ class ConvEdge(EdgeWithWeight):
         d.output_channel_end = self.num_output_channels_
         self.num_modules_y_, self.num_modules_x_, self.num_modules_t_ = Edge.GetNumModules(d, y, x, t)
         if t != 1:
-            raise SystemExit("3-D convolution is out of hot-path scope")
+            if d.padding_t != 0:
+                # the reference's 3-D loops assert padding_t == 0 (cudamat_conv3d_gemm.cu:23)
+                raise SystemExit(f"Error: Edge {self.name_}: padding_t is not supported on a convolutional edge")
+            if self.num_modules_t_ < 1:
+                raise SystemExit(f"Error: Edge {self.name_}: kernel_size_t {d.kernel_size_t} exceeds the {t} frames of its source layer")
 
     def GetDescription(self):
+        # src/conv_edge.cc:41-50 and Edge::GetDescription(conv_desc), src/edge.cc:116-123
         d = self.conv_desc_
-        return (f"{self.name_} Convolutional Kernel: {d.kernel_size_y}-{d.kernel_size_x}-{d.num_input_channels} : "
-                f"{d.num_output_channels} Layer: {self.image_size_y_}-{self.image_size_x_} : {self.num_modules_y_}-{self.num_modules_x_}")
+        kt = f"-{d.kernel_size_t}" if d.kernel_size_t != 1 else ""
+        it = f"-{self.image_size_t_}" if self.image_size_t_ != 1 else ""
+        mt = f"-{self.num_modules_t_}" if self.num_modules_t_ != 1 else ""
+        return (f"{self.name_} Convolutional Kernel: {d.kernel_size_y}-{d.kernel_size_x}-{d.num_input_channels}{kt} : "
+                f"{d.num_output_channels} Layer: {self.image_size_y_}-{self.image_size_x_}{it} : {self.num_modules_y_}-{self.num_modules_x_}{mt}")
 
     def _input_size(self):
         d = self.conv_desc_
@@ -418,9 +428,26 @@ class ConvEdge(EdgeWithWeight):
         w = self.tied_edge_.GetWeight() if self.is_tied_ else self.weights_
         scale_targets = 0 if overwrite else 1
         d = self.conv_desc_
+        three_d = self.image_size_t_ != 1
         if fuse_relu is not None and (self.has_no_bias_ or self.shared_bias_):
             b = None if self.has_no_bias_ else (self.tied_edge_.GetBias() if self.is_tied_ else self.bias_)
-            Matrix.ConvUpBiasAct(input, w, b, output, d, scale_targets, fuse_relu)
+            (Matrix.Conv3DUpBiasAct if three_d else Matrix.ConvUpBiasAct)(input, w, b, output, d, scale_targets, fuse_relu)
+            return
+        if three_d:
+            # src/conv_edge.cc:153-168
+            Matrix.Conv3DUp(input, w, output, d, scale_targets)
+            if not self.has_no_bias_:
+                b = self.tied_edge_.GetBias() if self.is_tied_ else self.bias_
+                if self.shared_bias_:
+                    F = d.num_output_channels
+                    output.Reshape(-1, F * self.num_modules_t_)
+                    for m in range(self.num_modules_t_):
+                        output_slice = Matrix()
+                        output.GetSlice(output_slice, m * F, (m + 1) * F)
+                        output_slice.AddRowVec(b)
+                    output.Reshape(-1, F * self.num_modules_y_ * self.num_modules_x_ * self.num_modules_t_)
+                else:
+                    output.AddRowVec(b)
             return
         Matrix.ConvUp(input, w, output, d, scale_targets)
         if not self.has_no_bias_:
@@ -436,10 +463,12 @@ class ConvEdge(EdgeWithWeight):
         """src/conv_edge.cc:172-181.  ``fuse_mask=post_scale`` additionally applies the source layer's
         ReLU' (mask = its state, ``input``) and dropout' scale in the kernel epilogue."""
         w = self.tied_edge_.GetWeight() if self.is_tied_ else self.weights_
+        three_d = self.image_size_t_ != 1
         if fuse_mask is not None:
-            Matrix.ConvDownMask(deriv_output, w, input, deriv_input, self.conv_desc_, 0 if overwrite else 1, fuse_mask)
+            (Matrix.Conv3DDownMask if three_d else Matrix.ConvDownMask)(deriv_output, w, input, deriv_input, self.conv_desc_,
+                                                                        0 if overwrite else 1, fuse_mask)
             return
-        Matrix.ConvDown(deriv_output, w, deriv_input, self.conv_desc_, 0 if overwrite else 1)
+        (Matrix.Conv3DDown if three_d else Matrix.ConvDown)(deriv_output, w, deriv_input, self.conv_desc_, 0 if overwrite else 1)
 
     def ComputeOuter(self, input, deriv_output):
         # src/conv_edge.cc:183-245 (GEMM build: partial sums forced to one chunk, :11-17)
@@ -447,9 +476,30 @@ class ConvEdge(EdgeWithWeight):
         batch_size = input.GetRows()
         scale_targets = 1 if self.GetNumGradsReceived() > 0 else 0
         d = self.conv_desc_
+        three_d = self.image_size_t_ != 1
         if self.fused and self.shared_bias_ and not self.has_no_bias_:
             db = self.tied_edge_.GetGradBias() if self.is_tied_ else self.grad_bias_
-            Matrix.ConvOutpBias(input, deriv_output, dw, db, d, scale_targets, self.scale_gradients_ / batch_size)
+            (Matrix.Conv3DOutpBias if three_d else Matrix.ConvOutpBias)(input, deriv_output, dw, db, d, scale_targets,
+                                                                        self.scale_gradients_ / batch_size)
+            self.IncrementNumGradsReceived()
+            return
+        if three_d:
+            # src/conv_edge.cc:223-242 (db.Mult(scale_targets) folded into the first frame's SumRows)
+            Matrix.Conv3DOutp(input, deriv_output, dw, d, scale_targets, self.scale_gradients_ / batch_size)
+            if not self.has_no_bias_:
+                db = self.tied_edge_.GetGradBias() if self.is_tied_ else self.grad_bias_
+                if self.shared_bias_:
+                    F = d.num_output_channels
+                    db_temp = Matrix()
+                    Matrix.GetTemp(1, deriv_output.GetCols(), db_temp)
+                    deriv_output.SumRows(db_temp, 0, 1)
+                    db_temp.Reshape(-1, F * self.num_modules_t_)
+                    for m in range(self.num_modules_t_):
+                        db_temp_slice = Matrix()
+                        db_temp.GetSlice(db_temp_slice, m * F, (m + 1) * F)
+                        db_temp_slice.SumRows(db, scale_targets if m == 0 else 1, self.scale_gradients_ / batch_size)
+                else:
+                    deriv_output.SumRows(db, scale_targets, self.scale_gradients_ / batch_size)
             self.IncrementNumGradsReceived()
             return
         Matrix.ConvOutp(input, deriv_output, dw, d, self.num_modules_y_, self.num_modules_x_, scale_targets,
@@ -654,6 +704,9 @@ class ConvOneToOneEdge(FCEdge):
         # src/conv_onetoone_edge.cc:8-13
         Edge.SetImageSize(self, y, x, t)
         self.num_modules_y_, self.num_modules_x_, self.num_modules_t_ = y, x, t
+        if t != 1:
+            # the (N*X*Y, C) view groups by channel only for one frame: with time outermost a column would mix channels and frames
+            raise SystemExit(f"Error: Edge {self.name_}: CONV_ONETOONE is not supported on a layer with image_size_t > 1 ({t} frames)")
 
     def _input_size(self):
         return self.num_input_channels_
@@ -723,6 +776,13 @@ class _PoolEdge(Edge):
         if d.kernel_size_t <= 0:
             d.kernel_size_t = t
         self.num_modules_y_, self.num_modules_x_, self.num_modules_t_ = Edge.GetNumModules(d, y, x, t)
+        if self.num_modules_t_ < 1:
+            raise SystemExit(f"Error: Edge {self.name_}: kernel_size_t {d.kernel_size_t} exceeds the {t} frames of its source layer")
+
+    def HasTimeWindow(self):
+        """The windows are Ky x Kx x Kt boxes over the frames of a clip (include/convnet_hip.h: pooling over time)."""
+        d = self.conv_desc_
+        return self.image_size_t_ > 1 and (d.kernel_size_t > 1 or d.stride_t > 1 or d.padding_t != 0)
 
 
 _POOL_MASK = os.environ.get("CONVNET_POOL_MASK", "1") != "0"   # A/B switch (tools/profile_round.sh): 0 = the reference's call pair on the fused path too
@@ -749,7 +809,8 @@ class MaxPoolEdge(_PoolEdge):
         self.mask_refused_ = set()   # (batch, input size, output size) the mask kernel refused: no mask, no call from then on
 
     def MaskEligible(self):
-        return self.fused and self.mask_legal_ and _POOL_MASK
+        # (the mask kernels are 2-D: a window with a time extent takes the reference's call pair)
+        return self.fused and self.mask_legal_ and _POOL_MASK and not self.HasTimeWindow()
 
     def ComputeUp(self, input, output, overwrite, train=True, fuse_relu=None):
         if not overwrite:
@@ -811,9 +872,18 @@ class ResponseNormEdge(Edge):
 
     def ComputeUp(self, input, output, overwrite, train=True, fuse_relu=None):
         # fuse_relu=True: the destination layer's ReLU (layer.cc:549) is applied by the same kernel
+        if self.image_size_t_ > 1:   # src/response_norm_edge.cc:46-50: frame by frame
+            Matrix.ConvResponseNormCrossMap3D(input, output, self.num_input_channels_, self.num_filters_response_norm_,
+                                              self.add_scale_, self.pow_scale_, self.blocked_, self.image_size_t_, relu=bool(fuse_relu))
+            return
         Matrix.ConvResponseNormCrossMap(input, output, self.num_input_channels_, self.num_filters_response_norm_,
                                         self.add_scale_, self.pow_scale_, self.blocked_, relu=bool(fuse_relu))
 
     def ComputeDown(self, deriv_output, input, output, deriv_input, overwrite):
+        if self.image_size_t_ > 1:
+            Matrix.ConvResponseNormCrossMapUndo3D(deriv_output, input, output, deriv_input, self.num_input_channels_,
+                                                  self.num_filters_response_norm_, self.add_scale_, self.pow_scale_, self.blocked_,
+                                                  self.image_size_t_)
+            return
         Matrix.ConvResponseNormCrossMapUndo(deriv_output, input, output, deriv_input, self.num_input_channels_,
                                             self.num_filters_response_norm_, self.add_scale_, self.pow_scale_, self.blocked_)

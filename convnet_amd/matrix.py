@@ -451,6 +451,50 @@ class Matrix:
                          ctypes.byref(deriv_output.shape_), ctypes.byref(dw.shape_), conv_desc, float(scale_targets),
                          float(scale_outputs))
 
+    # ---- spatio-temporal (3-D) convolution: src/matrix.cc:796-857, 951-989 (include/convnet_hip.h has the layouts) ----
+    @staticmethod
+    def Conv3DUp(input, w, output, conv_desc, scale_targets):
+        lib.convUp3DGemm(input.GetMat(), w.GetMat(), output.GetMat(), ctypes.byref(input.shape_), ctypes.byref(w.shape_),
+                         ctypes.byref(output.shape_), conv_desc, float(scale_targets))
+
+    @staticmethod
+    def Conv3DUpBiasAct(input, w, bias, output, conv_desc, scale_targets, relu):
+        lib.convUp3DBiasAct(input.GetMat(), w.GetMat(), bias.GetMat() if bias is not None else None, output.GetMat(),
+                            ctypes.byref(input.shape_), ctypes.byref(w.shape_), ctypes.byref(output.shape_), conv_desc,
+                            float(scale_targets), int(relu))
+
+    @staticmethod
+    def Conv3DDown(deriv_output, w, deriv_input, conv_desc, scale_targets):
+        lib.convDown3DGemm(deriv_output.GetMat(), w.GetMat(), deriv_input.GetMat(), ctypes.byref(deriv_output.shape_),
+                           ctypes.byref(w.shape_), ctypes.byref(deriv_input.shape_), conv_desc, float(scale_targets))
+
+    @staticmethod
+    def Conv3DDownMask(deriv_output, w, state, deriv_input, conv_desc, scale_targets, post_scale=1.0):
+        lib.convDown3DMask(deriv_output.GetMat(), w.GetMat(), state.GetMat(), deriv_input.GetMat(), ctypes.byref(deriv_output.shape_),
+                           ctypes.byref(w.shape_), ctypes.byref(deriv_input.shape_), conv_desc, float(scale_targets), float(post_scale))
+
+    @staticmethod
+    def Conv3DOutp(input, deriv_output, dw, conv_desc, scale_targets, scale_outputs):
+        lib.convOutp3DGemm(input.GetMat(), deriv_output.GetMat(), dw.GetMat(), ctypes.byref(input.shape_),
+                           ctypes.byref(deriv_output.shape_), ctypes.byref(dw.shape_), conv_desc, float(scale_targets),
+                           float(scale_outputs))
+
+    @staticmethod
+    def Conv3DOutpBias(input, deriv_output, dw, db, conv_desc, scale_targets, scale_outputs):
+        lib.convOutp3DBias(input.GetMat(), deriv_output.GetMat(), dw.GetMat(), db.GetMat(), ctypes.byref(input.shape_),
+                           ctypes.byref(deriv_output.shape_), ctypes.byref(dw.shape_), conv_desc, float(scale_targets),
+                           float(scale_outputs))
+
+    @staticmethod
+    def ConvResponseNormCrossMap3D(input, output, numFilters, sizeF, addScale, powScale, blocked, image_size_t, relu=False):
+        fn = lib.ResponseNormCrossMap3DRelu if relu else lib.ResponseNormCrossMap3DGemm
+        fn(input.GetMat(), output.GetMat(), int(numFilters), int(sizeF), float(addScale), float(powScale), bool(blocked), int(image_size_t))
+
+    @staticmethod
+    def ConvResponseNormCrossMapUndo3D(outGrads, inputs, acts, targets, numFilters, sizeF, addScale, powScale, blocked, image_size_t):
+        lib.ResponseNormCrossMap3DUndoGemm(outGrads.GetMat(), inputs.GetMat(), targets.GetMat(), int(numFilters), int(sizeF),
+                                           float(addScale), float(powScale), bool(blocked), int(image_size_t))
+
     # ---- locally connected layers: src/matrix.cc:859-893 (the *Gemm names, as a USE_GEMM build of the reference calls them) ----
     @staticmethod
     def LocalUp(input, w, output, conv_desc, scale_targets):

@@ -12,6 +12,8 @@ text so they can also be written to disk and fed to the reference's own binaries
 * ``vgg_bn()``     — the same with batch normalisation on every conv layer.
 * ``small_bn()``   — a small batch-normalised net for tests: conv-BN-ReLU, avgpool, conv-BN-ReLU + dropout, FC-BN-ReLU,
                      softmax.
+* ``video_small()`` — a small spatio-temporal (3-D) net: 3-D convs, max pooling without and with a time extent, response norm,
+                     average pooling over all remaining frames.
 tests/test_models.py checks the first two against the reference's files when they are mounted.
 """
 
@@ -31,10 +33,12 @@ _OPT_W = """  weight_optimizer {{
 """
 
 
-def _layer(name, channels, activation=None, dropprob=0.0, size=None, extra=""):
+def _layer(name, channels, activation=None, dropprob=0.0, size=None, extra="", frames=None):
     s = f'layer {{\n  name: "{name}"\n  num_channels: {channels}\n'
     if size:
         s += f"  image_size_y: {size}\n  image_size_x: {size}\n"
+    if frames:
+        s += f"  image_size_t: {frames}\n"
     if activation:
         s += f"  activation: {activation}\n"
     if dropprob:
@@ -252,6 +256,32 @@ def small_bn(image_size=12, num_classes=10, dropprob=0.25, bn_f=0.9, relu=True):
     return s
 
 
+def _time(edge, kt=None, st=None):
+    """The same edge with kernel_size_t / stride_t added (a 3-D convolution, or pooling boxes over time)."""
+    extra = (f"  kernel_size_t: {kt}\n" if kt is not None else "") + (f"  stride_t: {st}\n" if st is not None else "")
+    head, sep, tail = edge.rpartition("}")
+    return head + extra + sep + tail
+
+
+def video_small(image_size=32, frames=16, num_classes=10, grad_check=False, init_wt=1.0):
+    """A small video net with every edge type that takes clips: 3 x 32 x 32 x T16 -> conv 3x3x3/64 -> max-pool 3x3x1 s2 (frames are
+    channels) -> conv 3x3x3/128 -> max-pool 3x3x2 s2, over time too -> rnorm -> conv 3x3x3/128 -> avg-pool over all remaining frames ->
+    FC -> softmax.  Sizes: 32x32xT16 -> 32x32xT14 -> 15x15xT14 -> 15x15xT12 -> 7x7xT6 -> 7x7xT4 -> 1x1xT1."""
+    gc = _gc(grad_check)
+    R = "RECTIFIED_LINEAR"
+    s = _header("video_small")
+    s += _layer("input", 3, size=image_size, frames=frames)
+    s += _layer("conv1", 64, R) + _layer("pool1", 64) + _layer("conv2", 128, R) + _layer("pool2", 128) + _layer("rnorm2", 128)
+    s += _layer("conv3", 128, R) + _layer("pool3", 128) + _layer("output", num_classes, "SOFTMAX")
+    s += _time(_conv("input", "conv1", 3, 1, 1, init_wt=init_wt, grad_check=gc), kt=3) + _pool("conv1", "pool1", 3, 2)
+    s += _time(_conv("pool1", "conv2", 3, 1, 1, init_wt=init_wt, init_bias=1.0, grad_check=gc), kt=3)
+    s += _time(_pool("conv2", "pool2", 3, 2), kt=2, st=2) + _rnorm("pool2", "rnorm2")
+    s += _time(_conv("rnorm2", "conv3", 3, 1, 1, init_wt=init_wt, grad_check=gc), kt=3)
+    s += _time(_pool("conv3", "pool3", 0, 1, kind="AVERAGE_POOL"), kt=0)   # kernel sizes <= 0: the whole map, all frames (maxpool_edge.cc:13-25)
+    s += _fc("pool3", "output", init_wt=init_wt, grad_check=gc)
+    return s
+
+
 # forward MACs per image of a built net (for roofline accounting): see bench.py
 def count_macs(net):
     """(fwd_macs, train_macs) per image following BASELINE.md §2: train = fwd + wgrad (all weighted
@@ -262,6 +292,8 @@ def count_macs(net):
         if isinstance(e, (ConvEdge, LocalEdge)):
             d = e.conv_desc_
             macs = e.num_modules_y_ * e.num_modules_x_ * d.num_output_channels * d.kernel_size_y * d.kernel_size_x * d.num_input_channels
+            if isinstance(e, ConvEdge):   # a 3-D convolution: Kt taps in each of Mt output frames
+                macs *= max(1, d.kernel_size_t) * e.num_modules_t_
         elif isinstance(e, ConvOneToOneEdge):     # 1x1 conv: C x F per pixel
             macs = e.num_modules_y_ * e.num_modules_x_ * e.num_input_channels_ * e.num_output_channels_
         elif isinstance(e, FCEdge):

@@ -271,7 +271,70 @@ void localUpBiasAct(cudamat* images, cudamat* filters, cudamat* bias, cudamat* t
                     Shape4D* images_shape, Shape4D* filters_shape, Shape4D* targets_shape,
                     ConvDesc conv_desc, float scaleTargets, int relu);
 
-/* ---- pooling: cudamat_conv_gemm.cuh:72-92 (and cudamat_conv.cuh:58-70) ------------------------------ */
+/* ---- spatio-temporal (3-D) convolution: cudamat_conv_gemm.cuh:115-138 (cudamat_conv3d_gemm.cu; src/conv_edge.cc:153-245) ----------
+ * Time is the OUTERMOST index.  Activations are (N, X*Y*C*T): element (n, x, y, c, t) at n + N*(x + W*(y + H*(c + C*t))), Shape4D
+ * (N, X, Y, C*T); frame t is the column range [t*X*Y*C, (t+1)*X*Y*C).  The bank is (F, Kx*Ky*C*Kt): element (f, kx, ky, c, kt) at
+ * f + F*(kx + Kx*(ky + Ky*(c + C*kt))), Shape4D (F, Kx, Ky, C*Kt).  C = conv_desc.num_input_channels, F = conv_desc.num_output_channels,
+ * T = images_shape[3] / C, Mt = targets_shape[3] / F = (T - Kt) / stride_t + 1.
+ *   convUp3DGemm:   output frame m = convUpGemm of input frames [m*stride_t, m*stride_t + Kt) read as C*Kt channels
+ *   convDown3DGemm: targets = scaleTargets*targets + sum over m of convDownGemm(derivs frame m) into input frames [m*st, m*st + Kt);
+ *                   overlapping windows add; input frames that no window covers become scaleTargets*targets
+ *   convOutp3DGemm: targets = scaleTargets*targets + scaleOutput * sum over m of convOutpGemm(input frames of m, derivs frame m)
+ *   ResponseNormCrossMap3D[Undo]Gemm: the 2-D operation on each of image_size_t frames
+ * Restrictions: padding_t == 0 (the reference asserts it), num_groups == 1, whole channel ranges; a violation or a shape mismatch
+ * prints "check failed: ..." and aborts, as for convUpGemm.  kernel_size_t <= 0 and stride_t <= 0 are read as 1.
+ * Unlike the reference, which moves data_device and size[1] of the caller's cudamat structs during its loops and restores them, these
+ * entries never write the caller's structs.  They are not parked as deferred epilogues.  Both matrix paths; no atomics: bit-identical
+ * from call to call.
+ * How they run: convUp3DGemm is bit-identical to the loop of convUpGemm over get_slice views; the bank's bf16 planes /
+ * tap-major copy are built once per call.  convOutp3DGemm writes dW once: the frames' split-K slabs go to one arena and a single
+ * reduction sums them in fixed order and applies scaleTargets / scaleOutput (tolerance-equal to the accumulating loop).  convDown3DGemm, when C % 16 == 0, is a gather over
+ * time: each input frame is ONE 2-D dgrad over the contiguous output frames whose windows contain it, with a bank re-laid per frame
+ * class, so every input frame is written exactly once (tolerance-equal to the reference's accumulating loop: the summation order
+ * differs); for other C it is that loop (one scale pass, then every output frame accumulates into its window).
+ * Fused variants (new), each bit-identical to the unfused sequence on every frame:
+ *   convUp3DBiasAct : convUp3DGemm + the shared bias (1, F) added to every output frame [+ max(x, 0)]   (conv_edge.cc:155-164)
+ *   convDown3DMask  : targets = (state > 0) ? post_scale * (convDown3DGemm result) : 0 — in the gather's epilogue (each frame is
+ *                     written once), as a last pass behind the loop
+ *   convOutp3DBias  : convOutp3DGemm AND bias_grad(1, F) = scaleTargets*bias_grad + scaleOutput * sum of derivs over images, pixels
+ *                     and frames (conv_edge.cc:228-238)
+ *   ResponseNormCrossMap3DRelu : ResponseNormCrossMap3DGemm + the ReLU of the destination layer */
+void convUp3DGemm(cudamat* images, cudamat* filters, cudamat* targets,
+                  Shape4D* images_shape, Shape4D* filters_shape,
+                  Shape4D* targets_shape, ConvDesc conv_desc,
+                  float scaleTargets);
+void convDown3DGemm(cudamat* derivs, cudamat* filters, cudamat* targets,
+                    Shape4D* derivs_shape, Shape4D* filters_shape,
+                    Shape4D* targets_shape, ConvDesc conv_desc,
+                    float scaleTargets);
+void convOutp3DGemm(cudamat* images, cudamat* derivs, cudamat* targets,
+                    Shape4D* images_shape, Shape4D* derivs_shape,
+                    Shape4D* targets_shape, ConvDesc conv_desc,
+                    float scaleTargets, float scaleOutput);
+void ResponseNormCrossMap3DGemm(cudamat* images, cudamat* targets, int numFilters, int sizeF, float addScale,
+                                float powScale, bool blocked, int image_size_t);
+void ResponseNormCrossMap3DUndoGemm(cudamat* outGrads, cudamat* inputs, cudamat* targets,
+                                    int numFilters, int sizeF, float addScale, float powScale, bool blocked,
+                                    int image_size_t);
+void convUp3DBiasAct(cudamat* images, cudamat* filters, cudamat* bias, cudamat* targets,
+                     Shape4D* images_shape, Shape4D* filters_shape, Shape4D* targets_shape,
+                     ConvDesc conv_desc, float scaleTargets, int relu);
+void convDown3DMask(cudamat* derivs, cudamat* filters, cudamat* state, cudamat* targets,
+                    Shape4D* derivs_shape, Shape4D* filters_shape, Shape4D* targets_shape,
+                    ConvDesc conv_desc, float scaleTargets, float post_scale);
+void convOutp3DBias(cudamat* images, cudamat* derivs, cudamat* targets, cudamat* bias_grad,
+                    Shape4D* images_shape, Shape4D* derivs_shape, Shape4D* targets_shape,
+                    ConvDesc conv_desc, float scaleTargets, float scaleOutput);
+void ResponseNormCrossMap3DRelu(cudamat* images, cudamat* targets, int numFilters, int sizeF, float addScale,
+                                float powScale, bool blocked, int image_size_t);
+
+/* ---- pooling: cudamat_conv_gemm.cuh:72-92 (and cudamat_conv.cuh:58-70) ------------------------------
+ * Pooling over time: when images_shape[3] = C*T with C = conv_desc.num_input_channels and T > 1, the tensors hold T frames (layout as
+ * for the 3-D convolution) and the windows are Ky x Kx x Kt boxes with stride_t / padding_t, clipped to the clip as they are to the
+ * image; output element (n, mx, my, c, mt), Mt = (T - 2*padding_t - Kt) / stride_t + 1.  The average (forward and undo) divides by
+ * the CLIPPED box; the max undo routes to every input of a box that equals its maximum and sums over overlapping boxes
+ * (cudamat_conv_gemm.cu:163-293).  With T == 1 nothing changes; with T > 1 and Kt <= 1, stride_t <= 1, padding_t == 0 the call is
+ * the 2-D one on C*T channels, bit for bit.  MaxPoolMask / MaxPoolUndoMask return ERROR_UNSUPPORTED for windows with a time extent. */
 void MaxPoolGemm(cudamat* images, cudamat* targets, Shape4D* images_shape,
                  Shape4D* targets_shape, ConvDesc conv_desc, float scaleTargets,
                  float scaleOutput);

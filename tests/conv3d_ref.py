@@ -1,0 +1,269 @@
+"""float64 numpy statement of the spatio-temporal (3-D) operations (include/convnet_hip.h: "spatio-temporal convolution", "pooling
+over time"), written from the contract alone.
+
+Array convention, the 2-D tests' with time in front (C order == the library's column-major bytes, time outermost):
+  activations (T, C, H, W, N)      bank (Kt, C, Ky, Kx, F)      outputs (Mt, F, My, Mx, N)      pooled (Mt, C, My, Mx, N)
+``pad*`` are the pbtxt (positive) paddings.  Everything computes in float64 whatever the input dtype."""
+from dataclasses import dataclass
+
+import numpy as np
+
+
+@dataclass(frozen=True)
+class Geom3D:
+    N: int
+    C: int
+    H: int
+    W: int
+    T: int
+    F: int
+    Ky: int
+    Kx: int
+    Kt: int = 1
+    sy: int = 1
+    sx: int = 1
+    st: int = 1
+    pady: int = 0
+    padx: int = 0
+    padt: int = 0
+
+    @property
+    def My(self):
+        return (self.H + 2 * self.pady - self.Ky) // self.sy + 1
+
+    @property
+    def Mx(self):
+        return (self.W + 2 * self.padx - self.Kx) // self.sx + 1
+
+    @property
+    def Mt(self):
+        return (self.T + 2 * self.padt - self.Kt) // self.st + 1
+
+    def in_shape(self):
+        return (self.T, self.C, self.H, self.W, self.N)
+
+    def out_shape(self):
+        return (self.Mt, self.F, self.My, self.Mx, self.N)
+
+    def filt_shape(self):
+        return (self.Kt, self.C, self.Ky, self.Kx, self.F)
+
+    def pooled_shape(self):
+        return (self.Mt, self.C, self.My, self.Mx, self.N)
+
+
+def _f64(a):
+    return np.asarray(a, np.float64)
+
+
+def _pad_xy(g, x):
+    return np.pad(x, ((0, 0), (0, 0), (g.pady, g.pady), (g.padx, g.padx), (0, 0)))
+
+
+def _taps(g):
+    for m in range(g.Mt):
+        for kt in range(g.Kt):
+            for ky in range(g.Ky):
+                for kx in range(g.Kx):
+                    yield m, kt, ky, kx, (slice(ky, ky + g.sy * (g.My - 1) + 1, g.sy), slice(kx, kx + g.sx * (g.Mx - 1) + 1, g.sx))
+
+
+def conv_up(g, x, w, targets=None, scale_targets=0.0):
+    assert g.padt == 0
+    xp, w = _pad_xy(g, _f64(x)), _f64(w)
+    out = np.zeros(g.out_shape())
+    for m, kt, ky, kx, (ys, xs) in _taps(g):
+        out[m] += np.einsum("cf,cyxn->fyxn", w[kt, :, ky, kx, :], xp[m * g.st + kt][:, ys, xs, :])
+    return out if targets is None else scale_targets * _f64(targets) + out
+
+
+def conv_down(g, dy, w, targets=None, scale_targets=0.0):
+    assert g.padt == 0
+    dy, w = _f64(dy), _f64(w)
+    dxp = np.zeros((g.T, g.C, g.H + 2 * g.pady, g.W + 2 * g.padx, g.N))
+    for m, kt, ky, kx, (ys, xs) in _taps(g):
+        dxp[m * g.st + kt][:, ys, xs, :] += np.einsum("cf,fyxn->cyxn", w[kt, :, ky, kx, :], dy[m])
+    dx = dxp[:, :, g.pady:g.pady + g.H, g.padx:g.padx + g.W, :]
+    return dx if targets is None else scale_targets * _f64(targets) + dx
+
+
+def conv_outp(g, x, dy, targets=None, scale_targets=0.0, scale_output=1.0):
+    assert g.padt == 0
+    xp, dy = _pad_xy(g, _f64(x)), _f64(dy)
+    dw = np.zeros(g.filt_shape())
+    for m, kt, ky, kx, (ys, xs) in _taps(g):
+        dw[kt, :, ky, kx, :] += np.einsum("cyxn,fyxn->cf", xp[m * g.st + kt][:, ys, xs, :], dy[m])
+    dw *= scale_output
+    return dw if targets is None else scale_targets * _f64(targets) + dw
+
+
+def _boxes(g):
+    """(mt, my, mx) and the CLIPPED input box of every pooling window."""
+    for mt in range(g.Mt):
+        t0, t1 = max(0, mt * g.st - g.padt), min(g.T, mt * g.st - g.padt + g.Kt)
+        for my in range(g.My):
+            y0, y1 = max(0, my * g.sy - g.pady), min(g.H, my * g.sy - g.pady + g.Ky)
+            for mx in range(g.Mx):
+                x0, x1 = max(0, mx * g.sx - g.padx), min(g.W, mx * g.sx - g.padx + g.Kx)
+                yield (mt, my, mx), (slice(t0, t1), slice(None), slice(y0, y1), slice(x0, x1), slice(None))
+
+
+def _bc(v):
+    return v[None, :, None, None, :]     # (C, N) against a (t, C, y, x, N) box
+
+
+def max_pool(g, x):
+    x = _f64(x)
+    out = np.zeros(g.pooled_shape())
+    for (mt, my, mx), b in _boxes(g):
+        out[mt, :, my, mx, :] = x[b].max(axis=(0, 2, 3))
+    return out
+
+
+def avg_pool(g, x):
+    x = _f64(x)
+    out = np.zeros(g.pooled_shape())
+    for (mt, my, mx), b in _boxes(g):
+        out[mt, :, my, mx, :] = x[b].mean(axis=(0, 2, 3))     # divides by the clipped box
+    return out
+
+
+def max_pool_undo(g, x, dy, y, targets=None, scale_targets=0.0):
+    """Every input of a box that equals the box's recorded maximum receives the box's derivative (all ties); boxes add."""
+    x, dy, y = _f64(x), _f64(dy), _f64(y)
+    dx = np.zeros(g.in_shape())
+    for (mt, my, mx), b in _boxes(g):
+        dx[b] += (x[b] == _bc(y[mt, :, my, mx, :])) * _bc(dy[mt, :, my, mx, :])
+    return dx if targets is None else scale_targets * _f64(targets) + dx
+
+
+def avg_pool_undo(g, dy, targets=None, scale_targets=0.0):
+    dy = _f64(dy)
+    dx = np.zeros(g.in_shape())
+    for (mt, my, mx), b in _boxes(g):
+        size = (b[0].stop - b[0].start) * (b[2].stop - b[2].start) * (b[3].stop - b[3].start)
+        dx[b] += _bc(dy[mt, :, my, mx, :] / size)
+    return dx if targets is None else scale_targets * _f64(targets) + dx
+
+
+def _rnorm_windows(C, size_f, blocked):
+    """M[j, i] = 1 when channel i lies in the window of channel j."""
+    M = np.zeros((C, C))
+    for j in range(C):
+        start = (j // size_f) * size_f if blocked else j - size_f // 2
+        M[j, max(0, start):min(C, start + size_f)] = 1.0
+    return M
+
+
+def rnorm(x, size_f, add_scale, pow_scale, blocked=False):
+    """Cross-map response norm on every frame: x (T, C, ...) -> x * (1 + a * sum over the channel window of x^2)^-b."""
+    x = _f64(x)
+    M = _rnorm_windows(x.shape[1], size_f, blocked)
+    return x * (1 + add_scale * np.einsum("ji,ti...->tj...", M, x * x)) ** (-pow_scale)
+
+
+def rnorm_undo(dy, x, size_f, add_scale, pow_scale, blocked=False):
+    dy, x = _f64(dy), _f64(x)
+    M = _rnorm_windows(x.shape[1], size_f, blocked)
+    D = 1 + add_scale * np.einsum("ji,ti...->tj...", M, x * x)
+    return dy * D ** (-pow_scale) - 2 * add_scale * pow_scale * x * np.einsum("ij,ti...->tj...", M, dy * x * D ** (-pow_scale - 1))
+
+
+# ---- whole net ----------------------------------------------------------------------------------------------------------------------
+def _edge_geom(e, src, N, pool=False):
+    d = e.conv_desc_
+    C = src.GetNumChannels()
+    return Geom3D(N, C, src.GetSizeY(), src.GetSizeX(), src.GetSizeT(), C if pool else d.num_output_channels, d.kernel_size_y,
+                  d.kernel_size_x, max(1, d.kernel_size_t), d.stride_y, d.stride_x, max(1, d.stride_t), -d.padding_y, -d.padding_x,
+                  -d.padding_t)
+
+
+def forward_backward(net, x, labels, force=None):
+    """Forward and backward pass of a built ConvNet (conv with shared bias, max / avg pooling, response norm, FC, softmax output; no
+    dropout) in float64, in ConvNet::Fprop / Bprop order.  Returns (acts, derivs, grads) keyed by layer / edge name, flat arrays.
+    ``force`` = (states, derivs) of a device run: every backward op is then fed the device's own inputs, so a ReLU unit or a pooling
+    window that gates differently within fp32 rounding does not colour everything upstream of it."""
+    from convnet_amd.edge import AvgPoolEdge, ConvEdge, FCEdge, MaxPoolEdge, ResponseNormEdge
+    N = labels.size
+    acts = {net.input_layers_[0].GetName(): _f64(x).reshape(-1)}
+
+    def frames(l, a):
+        return a.reshape(l.GetSizeT(), l.GetNumChannels(), l.GetSizeY(), l.GetSizeX(), N)
+
+    for l in net.layers_:
+        if l.IsInput():
+            continue
+        y = 0.0
+        for e in l.incoming_edge_:
+            src = e.GetSource()
+            a = acts[src.GetName()]
+            if isinstance(e, ConvEdge):
+                g = _edge_geom(e, src, N)
+                assert e.shared_bias_ and not e.has_no_bias_
+                ye = conv_up(g, a.reshape(g.in_shape()), e.GetWeight().ToNumpy().reshape(g.filt_shape()))
+                ye = ye + _f64(e.GetBias().ToNumpy()).reshape(1, g.F, 1, 1, 1)
+            elif isinstance(e, MaxPoolEdge):
+                g = _edge_geom(e, src, N, True)
+                ye = max_pool(g, a.reshape(g.in_shape()))
+            elif isinstance(e, AvgPoolEdge):
+                g = _edge_geom(e, src, N, True)
+                ye = avg_pool(g, a.reshape(g.in_shape()))
+            elif isinstance(e, ResponseNormEdge):
+                ye = rnorm(frames(src, a), e.num_filters_response_norm_, e.add_scale_, e.pow_scale_, e.blocked_)
+            elif isinstance(e, FCEdge):
+                ye = _f64(e.GetWeight().ToNumpy()).reshape(-1, l.GetNumChannels()).T @ a.reshape(-1, N)   # bytes of (F, D) column-major
+                ye = ye + _f64(e.GetBias().ToNumpy()).reshape(-1, 1)
+            else:
+                raise NotImplementedError(type(e))
+            y = y + ye.reshape(-1)
+        if l.is_relu:
+            y = np.maximum(y, 0.0)
+        assert l.dropprob_ == 0
+        if l.IsOutput():
+            z = y.reshape(l.GetNumChannels(), N)
+            z = np.exp(z - z.max(axis=0, keepdims=True))
+            y = (z / z.sum(axis=0, keepdims=True)).reshape(-1)
+        acts[l.GetName()] = y
+    out = net.output_layers_[0]
+    f_acts, f_derivs = force if force is not None else (acts, None)
+    f_acts = {k: _f64(v).reshape(-1) for k, v in f_acts.items()}
+    p = f_acts[out.GetName()].reshape(out.GetNumChannels(), N).copy()
+    p[np.asarray(labels, np.int64).reshape(-1), np.arange(N)] -= 1.0
+    derivs = {out.GetName(): p.reshape(-1)}
+    grads = {}
+    for l in reversed(net.layers_):
+        if l.IsOutput():
+            continue
+        dx = None
+        for e in l.outgoing_edge_:
+            dst = e.GetDest()
+            a, yact = f_acts[l.GetName()], f_acts[dst.GetName()]
+            dy = _f64((f_derivs or derivs)[dst.GetName()]).reshape(-1)
+            de = None
+            if isinstance(e, ConvEdge):
+                g = _edge_geom(e, l, N)
+                dw = conv_outp(g, a.reshape(g.in_shape()), dy.reshape(g.out_shape()), None, 0.0, e.scale_gradients_ / N)
+                db = dy.reshape(g.out_shape()).sum(axis=(0, 2, 3, 4)) * (e.scale_gradients_ / N)
+                grads[e.GetName()] = (dw.reshape(-1), db)
+                if not l.IsInput():
+                    de = conv_down(g, dy.reshape(g.out_shape()), e.GetWeight().ToNumpy().reshape(g.filt_shape()))
+            elif isinstance(e, FCEdge):
+                dy2, a2 = dy.reshape(-1, N), a.reshape(-1, N)
+                grads[e.GetName()] = ((a2 @ dy2.T).reshape(-1) * (e.scale_gradients_ / N), dy2.sum(axis=1) * (e.scale_gradients_ / N))
+                if not l.IsInput():
+                    de = _f64(e.GetWeight().ToNumpy()).reshape(-1, dst.GetNumChannels()) @ dy2
+            elif isinstance(e, MaxPoolEdge):
+                g = _edge_geom(e, l, N, True)
+                de = max_pool_undo(g, a.reshape(g.in_shape()), dy.reshape(g.pooled_shape()), yact.reshape(g.pooled_shape()))
+            elif isinstance(e, AvgPoolEdge):
+                g = _edge_geom(e, l, N, True)
+                de = avg_pool_undo(g, dy.reshape(g.pooled_shape()))
+            elif isinstance(e, ResponseNormEdge):
+                de = rnorm_undo(frames(dst, dy), frames(l, a), e.num_filters_response_norm_, e.add_scale_, e.pow_scale_, e.blocked_)
+            if de is not None:
+                dx = de.reshape(-1) if dx is None else dx + de.reshape(-1)
+        if dx is not None and not l.IsInput():
+            if l.is_relu:
+                dx = dx * (f_acts[l.GetName()] > 0)
+            derivs[l.GetName()] = dx
+    return acts, derivs, grads
