@@ -9,6 +9,8 @@ gradient); the unfused path issues exactly the reference's Matrix-call sequence.
 import math
 import os
 
+import numpy as np
+
 from ._lib import ConvDesc
 from .matrix import Matrix
 from .optimizer import Optimizer
@@ -97,13 +99,24 @@ class Edge:
     def SetImageSize(self, y, x, t):
         self.image_size_y_, self.image_size_x_, self.image_size_t_ = y, x, t
 
+    def _set_desc_channels(self, channel_end=True):
+        """The channel fields of conv_desc_ (src/conv_edge.cc:52-58, maxpool_edge.cc:13-19).  LocalEdge::SetImageSize leaves the two
+        *_channel_end fields as GetConvDesc made them (``channel_end=False``)."""
+        d = self.conv_desc_
+        d.num_input_channels = self.num_input_channels_
+        d.num_output_channels = self.num_output_channels_
+        if channel_end:
+            d.input_channel_end = self.num_input_channels_
+            d.output_channel_end = self.num_output_channels_
+        return d
+
     def Initialize(self):
         pass
 
     def SetMemory(self, p):
         pass
 
-    def SetGradMemory(self, p):
+    def SetGradMemory(self, p, hist=None):
         pass
 
     def GetParameterMemoryRequirement(self):
@@ -223,6 +236,23 @@ class EdgeWithWeight(Edge):
     def GetGradBias(self):
         return self.grad_bias_
 
+    # The matrices the passes work on: a tied edge uses (and accumulates into) those of the edge it is tied to
+    # (src/edge_with_weight.cc:66-90).  No bias: None.
+    def _owner(self):
+        return self.tied_edge_ if self.is_tied_ else self
+
+    def _w(self):
+        return self._owner().weights_
+
+    def _b(self):
+        return None if self.has_no_bias_ else self._owner().bias_
+
+    def _dw(self):
+        return self._owner().grad_weights_
+
+    def _db(self):
+        return None if self.has_no_bias_ else self._owner().grad_bias_
+
     def SetTiedTo(self, e):
         if not isinstance(e, EdgeWithWeight):
             raise SystemExit(f"Error: Edge {self.GetName()} cannot be tied to edge {e.GetName()} which is not of the same type.")
@@ -324,6 +354,89 @@ class EdgeWithWeight(Edge):
         temp.Sqrt()
         return temp.Sum() / num_hid
 
+    # ---- parameter slicing: src/conv_edge.cc:72-136, local_edge.cc, fc_edge.cc.  An edge's slice of the flat parameter (and gradient)
+    # buffer is a (rows, _input_size() + bias_cols) matrix: the weights first, then the bias, read as one row.  A subclass gives
+    # _input_size() and _param_layout() = (rows, bias_cols, the weights' Shape4D or None).
+    def _num_modules(self):
+        return self.num_modules_y_ * self.num_modules_x_ * self.num_modules_t_
+
+    def GetParameterMemoryRequirement(self):
+        if self.is_tied_:
+            return 0
+        rows, bias_cols, _ = self._param_layout()
+        return rows * (self._input_size() + (0 if self.has_no_bias_ else bias_cols))
+
+    def _slice_params(self, p, w, b):
+        rows, bias_cols, shape4d = self._param_layout()
+        input_size = self._input_size()
+        p.Reshape(rows, -1)
+        p.GetSlice(w, 0, input_size)
+        if shape4d is not None:
+            w.SetShape4D(*shape4d)
+        if not self.has_no_bias_:
+            p.GetSlice(b, input_size, input_size + bias_cols)
+            b.Reshape(1, -1)
+
+    def SetMemory(self, p):
+        if self.is_tied_:
+            return
+        self._slice_params(p, self.weights_, self.bias_)
+
+    def SetGradMemory(self, p, hist=None):
+        if self.is_tied_:
+            return
+        self._slice_params(p, self.grad_weights_, self.grad_bias_)
+        rows, bias_cols, _ = self._param_layout()
+        self._alloc_optimizers(rows, self._input_size(), bias_cols, hist)
+
+    # ---- the bias after the up-GEMM and its gradient after the outer-GEMM.  ``shared`` = F: a conv edge's shared bias, one value per
+    # filter, on the (N*My*Mx, F) view of a frame.  ``frames`` = None: one frame, used whole (src/conv_edge.cc:145-149, 210-221);
+    # Mt: a 3-D edge, frame by frame through column slices of the (N*My*Mx, F*Mt) view (:153-168, 223-242).
+    def _add_bias(self, output, shared=0, frames=None):
+        b = self._b()
+        if b is None:
+            return
+        if not shared:
+            output.AddRowVec(b)
+            return
+        cols = output.GetCols()
+        output.Reshape(-1, shared * (frames or 1))
+        if frames is None:
+            output.AddRowVec(b)
+        else:
+            for m in range(frames):
+                output_slice = Matrix()
+                output.GetSlice(output_slice, m * shared, (m + 1) * shared)
+                output_slice.AddRowVec(b)
+        output.Reshape(-1, cols)
+
+    def _bias_grad(self, deriv_output, scale_targets, scale_outputs, shared=0, frames=None):
+        db = self._db()
+        if db is None:
+            return
+        if not shared:
+            deriv_output.SumRows(db, scale_targets, scale_outputs)
+            return
+        if self.fused and frames is None:
+            # one pass: (N*My*Mx, F) column sums == the reference's two-step SumRows.  (Nothing reaches this today: the only caller
+            # with a shared bias, ConvEdge.ComputeOuter, takes ConvOutpBias first whenever it is fused.)
+            cols = deriv_output.GetCols()
+            deriv_output.Reshape(-1, shared)
+            deriv_output.SumRows(db, scale_targets, scale_outputs)
+            deriv_output.Reshape(-1, cols)
+            return
+        db_temp = Matrix()
+        Matrix.GetTemp(1, deriv_output.GetCols(), db_temp)
+        deriv_output.SumRows(db_temp, 0, 1)
+        db_temp.Reshape(-1, shared * (frames or 1))
+        if frames is None:
+            db_temp.SumRows(db, scale_targets, scale_outputs)
+        else:
+            for m in range(frames):   # (db.Mult(scale_targets) folded into the first frame's SumRows)
+                db_temp_slice = Matrix()
+                db_temp.GetSlice(db_temp_slice, m * shared, (m + 1) * shared)
+                db_temp_slice.SumRows(db, scale_targets if m == 0 else 1, scale_outputs)
+
     def _alloc_optimizers(self, rows, cols, bias_cols, hist):
         """Optimizer state: either separate matrices (reference) or slices of a flat history
         buffer laid out exactly like the parameter slice (``hist``)."""
@@ -358,11 +471,7 @@ class ConvEdge(EdgeWithWeight):
 
     def SetImageSize(self, y, x, t):
         super().SetImageSize(y, x, t)
-        d = self.conv_desc_
-        d.num_input_channels = self.num_input_channels_
-        d.num_output_channels = self.num_output_channels_
-        d.input_channel_end = self.num_input_channels_
-        d.output_channel_end = self.num_output_channels_
+        d = self._set_desc_channels()
         self.num_modules_y_, self.num_modules_x_, self.num_modules_t_ = Edge.GetNumModules(d, y, x, t)
         if t != 1:
             if d.padding_t != 0:
@@ -384,143 +493,59 @@ class ConvEdge(EdgeWithWeight):
         d = self.conv_desc_
         return d.kernel_size_y * d.kernel_size_x * d.kernel_size_t * d.num_input_channels
 
-    def _bias_locs(self):
-        return 1 if self.shared_bias_ else self.num_modules_y_ * self.num_modules_x_ * self.num_modules_t_
-
-    def GetParameterMemoryRequirement(self):
-        # src/conv_edge.cc:72-78
-        if self.is_tied_:
-            return 0
-        return self.conv_desc_.num_output_channels * (self._input_size() + (0 if self.has_no_bias_ else self._bias_locs()))
-
-    def SetMemory(self, p):
-        # src/conv_edge.cc:80-108
-        if self.is_tied_:
-            return
+    def _param_layout(self):
+        # src/conv_edge.cc:72-108: one bias per filter (shared) or per filter and location
         d = self.conv_desc_
-        input_size, bias_locs = self._input_size(), self._bias_locs()
-        p.Reshape(d.num_output_channels, -1)
-        p.GetSlice(self.weights_, 0, input_size)
-        self.weights_.SetShape4D(d.num_output_channels, d.kernel_size_x, d.kernel_size_y, d.num_input_channels * d.kernel_size_t)
-        if not self.has_no_bias_:
-            p.GetSlice(self.bias_, input_size, input_size + bias_locs)
-            self.bias_.Reshape(1, -1)
+        return (d.num_output_channels, 1 if self.shared_bias_ else self._num_modules(),
+                (d.num_output_channels, d.kernel_size_x, d.kernel_size_y, d.num_input_channels * d.kernel_size_t))
 
     def SetGradMemory(self, p, hist=None):
-        # src/conv_edge.cc:110-136
-        d = self.conv_desc_
-        input_size, bias_locs = self._input_size(), self._bias_locs()
-        num_locs = self.num_modules_y_ * self.num_modules_x_ * self.num_modules_t_
-        if not self.is_tied_:
-            p.Reshape(d.num_output_channels, -1)
-            p.GetSlice(self.grad_weights_, 0, input_size)
-            self.grad_weights_.SetShape4D_like(self.weights_)
-            if not self.has_no_bias_:
-                p.GetSlice(self.grad_bias_, input_size, input_size + bias_locs)
-                self.grad_bias_.Reshape(1, -1)
-                if self.shared_bias_:
-                    Matrix.RegisterTempMemory(d.num_output_channels * num_locs, "shared bias")
-            self._alloc_optimizers(d.num_output_channels, input_size, bias_locs, hist)
+        # src/conv_edge.cc:110-136: the two-step shared-bias gradient takes a temp row (host bookkeeping, no library call)
+        if not self.is_tied_ and self.shared_bias_ and not self.has_no_bias_:
+            Matrix.RegisterTempMemory(self.conv_desc_.num_output_channels * self._num_modules(), "shared bias")
+        super().SetGradMemory(p, hist)
+
+    def _bias_view(self):
+        """(shared, frames) of _add_bias / _bias_grad for this edge."""
+        return (self.conv_desc_.num_output_channels if self.shared_bias_ else 0, self.num_modules_t_ if self.image_size_t_ != 1 else None)
 
     def ComputeUp(self, input, output, overwrite, train=True, fuse_relu=None):
         """src/conv_edge.cc:138-170.  ``fuse_relu`` (None = unfused reference sequence; True/False =
         fused conv+bias[+ReLU] epilogue; the caller then skips the layer's ApplyActivation)."""
-        w = self.tied_edge_.GetWeight() if self.is_tied_ else self.weights_
         scale_targets = 0 if overwrite else 1
-        d = self.conv_desc_
         three_d = self.image_size_t_ != 1
         if fuse_relu is not None and (self.has_no_bias_ or self.shared_bias_):
-            b = None if self.has_no_bias_ else (self.tied_edge_.GetBias() if self.is_tied_ else self.bias_)
-            (Matrix.Conv3DUpBiasAct if three_d else Matrix.ConvUpBiasAct)(input, w, b, output, d, scale_targets, fuse_relu)
+            (Matrix.Conv3DUpBiasAct if three_d else Matrix.ConvUpBiasAct)(input, self._w(), self._b(), output, self.conv_desc_,
+                                                                          scale_targets, fuse_relu)
             return
-        if three_d:
-            # src/conv_edge.cc:153-168
-            Matrix.Conv3DUp(input, w, output, d, scale_targets)
-            if not self.has_no_bias_:
-                b = self.tied_edge_.GetBias() if self.is_tied_ else self.bias_
-                if self.shared_bias_:
-                    F = d.num_output_channels
-                    output.Reshape(-1, F * self.num_modules_t_)
-                    for m in range(self.num_modules_t_):
-                        output_slice = Matrix()
-                        output.GetSlice(output_slice, m * F, (m + 1) * F)
-                        output_slice.AddRowVec(b)
-                    output.Reshape(-1, F * self.num_modules_y_ * self.num_modules_x_ * self.num_modules_t_)
-                else:
-                    output.AddRowVec(b)
-            return
-        Matrix.ConvUp(input, w, output, d, scale_targets)
-        if not self.has_no_bias_:
-            b = self.tied_edge_.GetBias() if self.is_tied_ else self.bias_
-            if self.shared_bias_:
-                output.Reshape(-1, d.num_output_channels)
-                output.AddRowVec(b)
-                output.Reshape(-1, d.num_output_channels * self.num_modules_y_ * self.num_modules_x_ * self.num_modules_t_)
-            else:
-                output.AddRowVec(b)
+        (Matrix.Conv3DUp if three_d else Matrix.ConvUp)(input, self._w(), output, self.conv_desc_, scale_targets)
+        self._add_bias(output, *self._bias_view())
 
     def ComputeDown(self, deriv_output, input, output, deriv_input, overwrite, fuse_mask=None):
         """src/conv_edge.cc:172-181.  ``fuse_mask=post_scale`` additionally applies the source layer's
         ReLU' (mask = its state, ``input``) and dropout' scale in the kernel epilogue."""
-        w = self.tied_edge_.GetWeight() if self.is_tied_ else self.weights_
         three_d = self.image_size_t_ != 1
         if fuse_mask is not None:
-            (Matrix.Conv3DDownMask if three_d else Matrix.ConvDownMask)(deriv_output, w, input, deriv_input, self.conv_desc_,
+            (Matrix.Conv3DDownMask if three_d else Matrix.ConvDownMask)(deriv_output, self._w(), input, deriv_input, self.conv_desc_,
                                                                         0 if overwrite else 1, fuse_mask)
             return
-        (Matrix.Conv3DDown if three_d else Matrix.ConvDown)(deriv_output, w, deriv_input, self.conv_desc_, 0 if overwrite else 1)
+        (Matrix.Conv3DDown if three_d else Matrix.ConvDown)(deriv_output, self._w(), deriv_input, self.conv_desc_, 0 if overwrite else 1)
 
     def ComputeOuter(self, input, deriv_output):
         # src/conv_edge.cc:183-245 (GEMM build: partial sums forced to one chunk, :11-17)
-        dw = self.tied_edge_.GetGradWeight() if self.is_tied_ else self.grad_weights_
-        batch_size = input.GetRows()
+        dw = self._dw()
         scale_targets = 1 if self.GetNumGradsReceived() > 0 else 0
+        scale_outputs = self.scale_gradients_ / input.GetRows()
         d = self.conv_desc_
         three_d = self.image_size_t_ != 1
         if self.fused and self.shared_bias_ and not self.has_no_bias_:
-            db = self.tied_edge_.GetGradBias() if self.is_tied_ else self.grad_bias_
-            (Matrix.Conv3DOutpBias if three_d else Matrix.ConvOutpBias)(input, deriv_output, dw, db, d, scale_targets,
-                                                                        self.scale_gradients_ / batch_size)
-            self.IncrementNumGradsReceived()
-            return
-        if three_d:
-            # src/conv_edge.cc:223-242 (db.Mult(scale_targets) folded into the first frame's SumRows)
-            Matrix.Conv3DOutp(input, deriv_output, dw, d, scale_targets, self.scale_gradients_ / batch_size)
-            if not self.has_no_bias_:
-                db = self.tied_edge_.GetGradBias() if self.is_tied_ else self.grad_bias_
-                if self.shared_bias_:
-                    F = d.num_output_channels
-                    db_temp = Matrix()
-                    Matrix.GetTemp(1, deriv_output.GetCols(), db_temp)
-                    deriv_output.SumRows(db_temp, 0, 1)
-                    db_temp.Reshape(-1, F * self.num_modules_t_)
-                    for m in range(self.num_modules_t_):
-                        db_temp_slice = Matrix()
-                        db_temp.GetSlice(db_temp_slice, m * F, (m + 1) * F)
-                        db_temp_slice.SumRows(db, scale_targets if m == 0 else 1, self.scale_gradients_ / batch_size)
-                else:
-                    deriv_output.SumRows(db, scale_targets, self.scale_gradients_ / batch_size)
-            self.IncrementNumGradsReceived()
-            return
-        Matrix.ConvOutp(input, deriv_output, dw, d, self.num_modules_y_, self.num_modules_x_, scale_targets,
-                        self.scale_gradients_ / batch_size)
-        if not self.has_no_bias_:
-            db = self.tied_edge_.GetGradBias() if self.is_tied_ else self.grad_bias_
-            if self.shared_bias_:
-                if self.fused:
-                    # one pass: (N*My*Mx, F) column sums == the reference's two-step SumRows
-                    cols = deriv_output.GetCols()
-                    deriv_output.Reshape(-1, d.num_output_channels)
-                    deriv_output.SumRows(db, scale_targets, self.scale_gradients_ / batch_size)
-                    deriv_output.Reshape(-1, cols)
-                else:
-                    db_temp = Matrix()
-                    Matrix.GetTemp(1, deriv_output.GetCols(), db_temp)
-                    deriv_output.SumRows(db_temp, 0, 1)
-                    db_temp.Reshape(-1, d.num_output_channels)
-                    db_temp.SumRows(db, scale_targets, self.scale_gradients_ / batch_size)
+            (Matrix.Conv3DOutpBias if three_d else Matrix.ConvOutpBias)(input, deriv_output, dw, self._db(), d, scale_targets, scale_outputs)
+        else:
+            if three_d:
+                Matrix.Conv3DOutp(input, deriv_output, dw, d, scale_targets, scale_outputs)
             else:
-                deriv_output.SumRows(db, scale_targets, self.scale_gradients_ / batch_size)
+                Matrix.ConvOutp(input, deriv_output, dw, d, self.num_modules_y_, self.num_modules_x_, scale_targets, scale_outputs)
+            self._bias_grad(deriv_output, scale_targets, scale_outputs, *self._bias_view())
         self.IncrementNumGradsReceived()
 
 
@@ -550,9 +575,7 @@ class LocalEdge(EdgeWithWeight):
 
     def SetImageSize(self, y, x, t):
         super().SetImageSize(y, x, t)
-        d = self.conv_desc_
-        d.num_input_channels = self.num_input_channels_
-        d.num_output_channels = self.num_output_channels_
+        d = self._set_desc_channels(channel_end=False)
         self.num_modules_y_, self.num_modules_x_, self.num_modules_t_ = Edge.GetNumModules(d, y, x, t)
         if t != 1:
             raise SystemExit("3-D locally connected layers are out of hot-path scope")
@@ -563,67 +586,31 @@ class LocalEdge(EdgeWithWeight):
         return (f"{self.name_}  Local Kernel: {d.kernel_size_y}-{d.kernel_size_x}-{d.num_input_channels} : {d.num_output_channels}"
                 f" Layer: {self.image_size_y_}-{self.image_size_x_} : {self.num_modules_y_}-{self.num_modules_x_}")
 
-    def _num_modules(self):
-        return self.num_modules_y_ * self.num_modules_x_ * self.num_modules_t_
-
     def _input_size(self):
         d = self.conv_desc_
         return d.kernel_size_x * d.kernel_size_y * d.kernel_size_t * d.num_input_channels * self._num_modules()
 
-    def GetParameterMemoryRequirement(self):
-        if self.is_tied_:
-            return 0
-        return self.conv_desc_.num_output_channels * (self._input_size() + (0 if self.has_no_bias_ else self._num_modules()))
-
-    def SetMemory(self, p):
-        if self.is_tied_:
-            return
+    def _param_layout(self):
         d = self.conv_desc_
-        input_size, bias_locs = self._input_size(), self._num_modules()
-        p.Reshape(d.num_output_channels, -1)
-        p.GetSlice(self.weights_, 0, input_size)
-        self.weights_.SetShape4D(d.num_output_channels, d.kernel_size_x, d.kernel_size_y,
-                                 d.num_input_channels * self.num_modules_y_ * self.num_modules_x_)
-        if not self.has_no_bias_:
-            p.GetSlice(self.bias_, input_size, input_size + bias_locs)
-            self.bias_.Reshape(1, -1)
-
-    def SetGradMemory(self, p, hist=None):
-        if self.is_tied_:
-            return
-        d = self.conv_desc_
-        input_size, bias_locs = self._input_size(), self._num_modules()
-        p.Reshape(d.num_output_channels, -1)
-        p.GetSlice(self.grad_weights_, 0, input_size)
-        self.grad_weights_.SetShape4D_like(self.weights_)
-        if not self.has_no_bias_:
-            p.GetSlice(self.grad_bias_, input_size, input_size + bias_locs)
-            self.grad_bias_.Reshape(1, -1)
-        self._alloc_optimizers(d.num_output_channels, input_size, bias_locs, hist)
+        return (d.num_output_channels, self._num_modules(),
+                (d.num_output_channels, d.kernel_size_x, d.kernel_size_y, d.num_input_channels * self.num_modules_y_ * self.num_modules_x_))
 
     def ComputeUp(self, input, output, overwrite, train=True, fuse_relu=None):
-        w = self.tied_edge_.GetWeight() if self.is_tied_ else self.weights_
         scale_targets = 0 if overwrite else 1
-        b = None if self.has_no_bias_ else (self.tied_edge_.GetBias() if self.is_tied_ else self.bias_)
         if fuse_relu is not None:
-            Matrix.LocalUpBiasAct(input, w, b, output, self.conv_desc_, scale_targets, fuse_relu)
+            Matrix.LocalUpBiasAct(input, self._w(), self._b(), output, self.conv_desc_, scale_targets, fuse_relu)
             return
-        Matrix.LocalUp(input, w, output, self.conv_desc_, scale_targets)
-        if b is not None:
-            output.AddRowVec(b)
+        Matrix.LocalUp(input, self._w(), output, self.conv_desc_, scale_targets)
+        self._add_bias(output)
 
     def ComputeDown(self, deriv_output, input, output, deriv_input, overwrite):
-        w = self.tied_edge_.GetWeight() if self.is_tied_ else self.weights_
-        Matrix.LocalDown(deriv_output, w, deriv_input, self.conv_desc_, 0 if overwrite else 1)
+        Matrix.LocalDown(deriv_output, self._w(), deriv_input, self.conv_desc_, 0 if overwrite else 1)
 
     def ComputeOuter(self, input, deriv_output):
-        dw = self.tied_edge_.GetGradWeight() if self.is_tied_ else self.grad_weights_
-        batch_size = input.GetRows()
         scale_targets = 1 if self.GetNumGradsReceived() > 0 else 0
-        Matrix.LocalOutp(input, deriv_output, dw, self.conv_desc_, scale_targets, self.scale_gradients_ / batch_size)
-        if not self.has_no_bias_:
-            db = self.tied_edge_.GetGradBias() if self.is_tied_ else self.grad_bias_
-            deriv_output.SumRows(db, scale_targets, self.scale_gradients_ / batch_size)
+        scale_outputs = self.scale_gradients_ / input.GetRows()
+        Matrix.LocalOutp(input, deriv_output, self._dw(), self.conv_desc_, scale_targets, scale_outputs)
+        self._bias_grad(deriv_output, scale_targets, scale_outputs)
         self.IncrementNumGradsReceived()
 
 
@@ -634,64 +621,36 @@ class FCEdge(EdgeWithWeight):
     def _input_size(self):
         return self.image_size_y_ * self.image_size_x_ * self.image_size_t_ * self.num_input_channels_
 
-    def GetParameterMemoryRequirement(self):
-        if self.is_tied_:
-            return 0
-        return self.num_output_channels_ * (self._input_size() + (0 if self.has_no_bias_ else 1))
+    def _param_layout(self):
+        return self.num_output_channels_, 1, None
 
     def GetDescription(self):
         return f"{self.name_} Fully Connected :{self.image_size_y_}-{self.image_size_x_}-{self.num_input_channels_}:{self.num_output_channels_}"
 
-    def SetMemory(self, p):
-        if self.is_tied_:
-            return
-        input_size = self._input_size()
-        p.Reshape(self.num_output_channels_, -1)
-        p.GetSlice(self.weights_, 0, input_size)
-        if not self.has_no_bias_:
-            p.GetSlice(self.bias_, input_size, input_size + 1)
-            self.bias_.Reshape(1, -1)
-
-    def SetGradMemory(self, p, hist=None):
-        if self.is_tied_:
-            return
-        input_size = self._input_size()
-        p.Reshape(self.num_output_channels_, -1)
-        p.GetSlice(self.grad_weights_, 0, input_size)
-        if not self.has_no_bias_:
-            p.GetSlice(self.grad_bias_, input_size, input_size + 1)
-            self.grad_bias_.Reshape(1, -1)
-        self._alloc_optimizers(self.num_output_channels_, input_size, 1, hist)
-
     def ComputeUp(self, input, output, overwrite, train=True, fuse_relu=None):
         # src/fc_edge.cc:51-61
-        w = self.tied_edge_.GetWeight() if self.is_tied_ else self.weights_
         scale_targets = 0 if overwrite else 1
         if fuse_relu is not None:
-            b = None if self.has_no_bias_ else (self.tied_edge_.GetBias() if self.is_tied_ else self.bias_)
-            Matrix.DotBiasAct(input, w, b, output, scale_targets, 1, False, True, fuse_relu)
+            Matrix.DotBiasAct(input, self._w(), self._b(), output, scale_targets, 1, False, True, fuse_relu)
             return
-        Matrix.Dot(input, w, output, scale_targets, 1, False, True)
-        if not self.has_no_bias_:
-            output.AddRowVec(self.tied_edge_.GetBias() if self.is_tied_ else self.bias_)
+        Matrix.Dot(input, self._w(), output, scale_targets, 1, False, True)
+        self._add_bias(output)
 
     def ComputeDown(self, deriv_output, input, output, deriv_input, overwrite, fuse_mask=None):
         # src/fc_edge.cc:63-68
-        w = self.tied_edge_.GetWeight() if self.is_tied_ else self.weights_
         if fuse_mask is not None:
-            Matrix.DotMask(deriv_output, w, input, deriv_input, 0 if overwrite else 1, 1, fuse_mask)
+            Matrix.DotMask(deriv_output, self._w(), input, deriv_input, 0 if overwrite else 1, 1, fuse_mask)
             return
-        Matrix.Dot(deriv_output, w, deriv_input, 0 if overwrite else 1, 1)
+        Matrix.Dot(deriv_output, self._w(), deriv_input, 0 if overwrite else 1, 1)
 
-    def ComputeOuter(self, input, deriv_output):
-        # src/fc_edge.cc:70-81
-        dw = self.tied_edge_.GetGradWeight() if self.is_tied_ else self.grad_weights_
+    def ComputeOuter(self, input, deriv_output, batch_size=None):
+        # src/fc_edge.cc:70-81.  ``batch_size``: the layer's batch where ``input`` is a view with other rows (ConvOneToOneEdge)
         scale_targets = 1 if self.GetNumGradsReceived() > 0 else 0
-        batch_size = input.GetRows()
-        Matrix.Dot(deriv_output, input, dw, scale_targets, self.scale_gradients_ / batch_size, True, False)
-        if not self.has_no_bias_:
-            db = self.tied_edge_.GetGradBias() if self.is_tied_ else self.grad_bias_
-            deriv_output.SumRows(db, scale_targets, self.scale_gradients_ / batch_size)
+        if batch_size is None:
+            batch_size = input.GetRows()
+        scale_outputs = self.scale_gradients_ / batch_size
+        Matrix.Dot(deriv_output, input, self._dw(), scale_targets, scale_outputs, True, False)
+        self._bias_grad(deriv_output, scale_targets, scale_outputs)
         self.IncrementNumGradsReceived()
 
 
@@ -743,14 +702,8 @@ class ConvOneToOneEdge(FCEdge):
     def ComputeOuter(self, input, deriv_output):
         # scale_gradients / batch_size uses the layer's batch (rows before the reshape), :92-104
         batch_size = input.GetRows()
-        dw = self.tied_edge_.GetGradWeight() if self.is_tied_ else self.grad_weights_
-        scale_targets = 1 if self.GetNumGradsReceived() > 0 else 0
         with self._Flat((input, self.num_input_channels_), (deriv_output, self.num_output_channels_)):
-            Matrix.Dot(deriv_output, input, dw, scale_targets, self.scale_gradients_ / batch_size, True, False)
-            if not self.has_no_bias_:
-                db = self.tied_edge_.GetGradBias() if self.is_tied_ else self.grad_bias_
-                deriv_output.SumRows(db, scale_targets, self.scale_gradients_ / batch_size)
-        self.IncrementNumGradsReceived()
+            FCEdge.ComputeOuter(self, input, deriv_output, batch_size)
 
 
 class _PoolEdge(Edge):
@@ -764,11 +717,7 @@ class _PoolEdge(Edge):
     def SetImageSize(self, y, x, t):
         # src/maxpool_edge.cc:13-25
         super().SetImageSize(y, x, t)
-        d = self.conv_desc_
-        d.num_input_channels = self.num_input_channels_
-        d.num_output_channels = self.num_output_channels_
-        d.input_channel_end = self.num_input_channels_
-        d.output_channel_end = self.num_output_channels_
+        d = self._set_desc_channels()
         if d.kernel_size_y <= 0:
             d.kernel_size_y = y
         if d.kernel_size_x <= 0:
@@ -802,7 +751,6 @@ class MaxPoolEdge(_PoolEdge):
 
     def __init__(self, c):
         super().__init__(c)
-        self.fused = False
         self.mask_legal_ = False   # set by ConvNet.BuildNet from the destination layer (see the class docstring)
         self.mask_ = None
         self.mask_for_ = None   # (input data pointer, output data pointer, batch) of the ComputeUp that wrote mask_
@@ -867,7 +815,6 @@ class ResponseNormEdge(Edge):
         super().SetImageSize(y, x, t)
         self.num_modules_y_, self.num_modules_x_, self.num_modules_t_ = y, x, t
         # (int) truncation of a *float* product, as in C++ (src/response_norm_edge.cc:37-38)
-        import numpy as np
         self.num_filters_response_norm_ = int(np.float32(self.frac_of_filters_response_norm_) * np.float32(self.num_input_channels_))
 
     def ComputeUp(self, input, output, overwrite, train=True, fuse_relu=None):

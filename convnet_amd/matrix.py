@@ -29,6 +29,13 @@ def _chk(err_code, what):
         raise MatrixError(f"Error: {what} : {_lib.GetStringError(err_code)}")
 
 
+def _conv_call(fn, mats, conv_desc, *scalars, unshaped=None):
+    """A conv-style ABI entry: the matrices, their Shape4Ds, the ConvDesc, the scalars.  ``unshaped``: the index of the one matrix whose
+    Shape4D the entry does not take (a bias, where None = no bias; the mask's state; a bias gradient)."""
+    fn(*(m.GetMat() if m is not None else None for m in mats),
+       *(ctypes.byref(m.shape_) for i, m in enumerate(mats) if i != unshaped), conv_desc, *scalars)
+
+
 class Matrix:
     # reference statics: temp_/ones_ pools, rnd_ state (src/matrix.cc:10-16)
     _temp = None
@@ -409,25 +416,20 @@ class Matrix:
 
     @staticmethod
     def ConvUp(input, w, output, conv_desc, scale_targets):
-        lib.convUpGemm(input.GetMat(), w.GetMat(), output.GetMat(), ctypes.byref(input.shape_), ctypes.byref(w.shape_),
-                       ctypes.byref(output.shape_), conv_desc, float(scale_targets))
+        _conv_call(lib.convUpGemm, (input, w, output), conv_desc, float(scale_targets))
 
     @staticmethod
     def ConvUpBiasAct(input, w, bias, output, conv_desc, scale_targets, relu):
-        lib.convUpBiasAct(input.GetMat(), w.GetMat(), bias.GetMat() if bias is not None else None, output.GetMat(),
-                          ctypes.byref(input.shape_), ctypes.byref(w.shape_), ctypes.byref(output.shape_), conv_desc,
-                          float(scale_targets), int(relu))
+        _conv_call(lib.convUpBiasAct, (input, w, bias, output), conv_desc, float(scale_targets), int(relu), unshaped=2)
 
     @staticmethod
     def ConvDown(deriv_output, w, deriv_input, conv_desc, scale_targets):
-        lib.convDownGemm(deriv_output.GetMat(), w.GetMat(), deriv_input.GetMat(), ctypes.byref(deriv_output.shape_),
-                         ctypes.byref(w.shape_), ctypes.byref(deriv_input.shape_), conv_desc, float(scale_targets))
+        _conv_call(lib.convDownGemm, (deriv_output, w, deriv_input), conv_desc, float(scale_targets))
 
     @staticmethod
     def ConvDownMask(deriv_output, w, state, deriv_input, conv_desc, scale_targets, post_scale=1.0):
         """ConvDown with the source layer's ReLU' (and dropout' scale) fused into the epilogue."""
-        lib.convDownMask(deriv_output.GetMat(), w.GetMat(), state.GetMat(), deriv_input.GetMat(), ctypes.byref(deriv_output.shape_),
-                         ctypes.byref(w.shape_), ctypes.byref(deriv_input.shape_), conv_desc, float(scale_targets), float(post_scale))
+        _conv_call(lib.convDownMask, (deriv_output, w, state, deriv_input), conv_desc, float(scale_targets), float(post_scale), unshaped=2)
 
     @staticmethod
     def DotMask(a, b, state, c, alpha, beta, post_scale=1.0):
@@ -436,9 +438,7 @@ class Matrix:
     @staticmethod
     def ConvOutpBias(input, deriv_output, dw, db, conv_desc, scale_targets, scale_outputs):
         """ConvOutp + the shared-bias gradient (two-step SumRows of conv_edge.cc:210-221) in one library call."""
-        lib.convOutpBias(input.GetMat(), deriv_output.GetMat(), dw.GetMat(), db.GetMat(), ctypes.byref(input.shape_),
-                         ctypes.byref(deriv_output.shape_), ctypes.byref(dw.shape_), conv_desc, float(scale_targets),
-                         float(scale_outputs))
+        _conv_call(lib.convOutpBias, (input, deriv_output, dw, db), conv_desc, float(scale_targets), float(scale_outputs), unshaped=3)
 
     @staticmethod
     def ConvMaxPoolUndoRelu(input, deriv_output, output, deriv_input, conv_desc, scale_targets):
@@ -447,43 +447,32 @@ class Matrix:
 
     @staticmethod
     def ConvOutp(input, deriv_output, dw, conv_desc, partial_sum_y, partial_sum_x, scale_targets, scale_outputs):
-        lib.convOutpGemm(input.GetMat(), deriv_output.GetMat(), dw.GetMat(), ctypes.byref(input.shape_),
-                         ctypes.byref(deriv_output.shape_), ctypes.byref(dw.shape_), conv_desc, float(scale_targets),
-                         float(scale_outputs))
+        _conv_call(lib.convOutpGemm, (input, deriv_output, dw), conv_desc, float(scale_targets), float(scale_outputs))
 
     # ---- spatio-temporal (3-D) convolution: src/matrix.cc:796-857, 951-989 (include/convnet_hip.h has the layouts) ----
     @staticmethod
     def Conv3DUp(input, w, output, conv_desc, scale_targets):
-        lib.convUp3DGemm(input.GetMat(), w.GetMat(), output.GetMat(), ctypes.byref(input.shape_), ctypes.byref(w.shape_),
-                         ctypes.byref(output.shape_), conv_desc, float(scale_targets))
+        _conv_call(lib.convUp3DGemm, (input, w, output), conv_desc, float(scale_targets))
 
     @staticmethod
     def Conv3DUpBiasAct(input, w, bias, output, conv_desc, scale_targets, relu):
-        lib.convUp3DBiasAct(input.GetMat(), w.GetMat(), bias.GetMat() if bias is not None else None, output.GetMat(),
-                            ctypes.byref(input.shape_), ctypes.byref(w.shape_), ctypes.byref(output.shape_), conv_desc,
-                            float(scale_targets), int(relu))
+        _conv_call(lib.convUp3DBiasAct, (input, w, bias, output), conv_desc, float(scale_targets), int(relu), unshaped=2)
 
     @staticmethod
     def Conv3DDown(deriv_output, w, deriv_input, conv_desc, scale_targets):
-        lib.convDown3DGemm(deriv_output.GetMat(), w.GetMat(), deriv_input.GetMat(), ctypes.byref(deriv_output.shape_),
-                           ctypes.byref(w.shape_), ctypes.byref(deriv_input.shape_), conv_desc, float(scale_targets))
+        _conv_call(lib.convDown3DGemm, (deriv_output, w, deriv_input), conv_desc, float(scale_targets))
 
     @staticmethod
     def Conv3DDownMask(deriv_output, w, state, deriv_input, conv_desc, scale_targets, post_scale=1.0):
-        lib.convDown3DMask(deriv_output.GetMat(), w.GetMat(), state.GetMat(), deriv_input.GetMat(), ctypes.byref(deriv_output.shape_),
-                           ctypes.byref(w.shape_), ctypes.byref(deriv_input.shape_), conv_desc, float(scale_targets), float(post_scale))
+        _conv_call(lib.convDown3DMask, (deriv_output, w, state, deriv_input), conv_desc, float(scale_targets), float(post_scale), unshaped=2)
 
     @staticmethod
     def Conv3DOutp(input, deriv_output, dw, conv_desc, scale_targets, scale_outputs):
-        lib.convOutp3DGemm(input.GetMat(), deriv_output.GetMat(), dw.GetMat(), ctypes.byref(input.shape_),
-                           ctypes.byref(deriv_output.shape_), ctypes.byref(dw.shape_), conv_desc, float(scale_targets),
-                           float(scale_outputs))
+        _conv_call(lib.convOutp3DGemm, (input, deriv_output, dw), conv_desc, float(scale_targets), float(scale_outputs))
 
     @staticmethod
     def Conv3DOutpBias(input, deriv_output, dw, db, conv_desc, scale_targets, scale_outputs):
-        lib.convOutp3DBias(input.GetMat(), deriv_output.GetMat(), dw.GetMat(), db.GetMat(), ctypes.byref(input.shape_),
-                           ctypes.byref(deriv_output.shape_), ctypes.byref(dw.shape_), conv_desc, float(scale_targets),
-                           float(scale_outputs))
+        _conv_call(lib.convOutp3DBias, (input, deriv_output, dw, db), conv_desc, float(scale_targets), float(scale_outputs), unshaped=3)
 
     @staticmethod
     def ConvResponseNormCrossMap3D(input, output, numFilters, sizeF, addScale, powScale, blocked, image_size_t, relu=False):
@@ -498,26 +487,20 @@ class Matrix:
     # ---- locally connected layers: src/matrix.cc:859-893 (the *Gemm names, as a USE_GEMM build of the reference calls them) ----
     @staticmethod
     def LocalUp(input, w, output, conv_desc, scale_targets):
-        lib.localUpGemm(input.GetMat(), w.GetMat(), output.GetMat(), ctypes.byref(input.shape_), ctypes.byref(w.shape_),
-                        ctypes.byref(output.shape_), conv_desc, float(scale_targets))
+        _conv_call(lib.localUpGemm, (input, w, output), conv_desc, float(scale_targets))
 
     @staticmethod
     def LocalUpBiasAct(input, w, bias, output, conv_desc, scale_targets, relu):
         """LocalUp + AddRowVec(bias) [+ ReLU] in one kernel (include/convnet_hip.h: localUpBiasAct)."""
-        lib.localUpBiasAct(input.GetMat(), w.GetMat(), bias.GetMat() if bias is not None else None, output.GetMat(),
-                           ctypes.byref(input.shape_), ctypes.byref(w.shape_), ctypes.byref(output.shape_), conv_desc,
-                           float(scale_targets), int(relu))
+        _conv_call(lib.localUpBiasAct, (input, w, bias, output), conv_desc, float(scale_targets), int(relu), unshaped=2)
 
     @staticmethod
     def LocalDown(deriv_output, w, deriv_input, conv_desc, scale_targets):
-        lib.localDownGemm(deriv_output.GetMat(), w.GetMat(), deriv_input.GetMat(), ctypes.byref(deriv_output.shape_),
-                          ctypes.byref(w.shape_), ctypes.byref(deriv_input.shape_), conv_desc, float(scale_targets))
+        _conv_call(lib.localDownGemm, (deriv_output, w, deriv_input), conv_desc, float(scale_targets))
 
     @staticmethod
     def LocalOutp(input, deriv_output, dw, conv_desc, scale_targets, scale_outputs):
-        lib.localOutpGemm(input.GetMat(), deriv_output.GetMat(), dw.GetMat(), ctypes.byref(input.shape_),
-                          ctypes.byref(deriv_output.shape_), ctypes.byref(dw.shape_), conv_desc, float(scale_targets),
-                          float(scale_outputs))
+        _conv_call(lib.localOutpGemm, (input, deriv_output, dw), conv_desc, float(scale_targets), float(scale_outputs))
 
     @staticmethod
     def ConvMaxPool(input, output, conv_desc):
