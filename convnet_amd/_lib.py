@@ -218,6 +218,14 @@ def _load():
     sig("bn_bprop_fused", I, M, M, M, M, M, M, M)
     sig("sgd_momentum_step_normlimit", I, M, M, M, F, F, F, F, F, I)
     sig("sgd_momentum_step_multi", I, I, P(M), P(M), P(M), c_float_p, c_float_p, c_float_p, c_float_p)
+    # Adagrad / RMSProp (csrc/elementwise.hip): the reference's three cudamat entries and the fused steps
+    sig("adagrad", I, M, M, F)
+    sig("rms_prop", I, M, M, F)
+    sig("divide_elementwise", I, M, M, M)
+    sig("adagrad_momentum_step", I, M, M, M, M, F, F, F, F, F, F)
+    sig("rmsprop_momentum_step", I, M, M, M, M, F, F, F, F, F)
+    sig("adagrad_momentum_step_multi", I, I, P(M), P(M), P(M), P(M), *[c_float_p] * 6)
+    sig("rmsprop_momentum_step_multi", I, I, P(M), P(M), P(M), P(M), *[c_float_p] * 5)
     R = P(rnd_struct)
     sig("init_random", I, R, I)
     sig("fill_with_rand", I, R, M)

@@ -24,6 +24,7 @@ from . import pbtxt
 from .edge import AvgPoolEdge, ConvEdge, Edge, EdgeWithWeight, FCEdge, LocalEdge, MaxPoolEdge, ResponseNormEdge
 from .layer import Layer, LinearLayer, ReLULayer, SoftmaxLayer
 from .matrix import Matrix
+from .optimizer import RunFusedSteps
 from .trainer import TrainLoopMixin
 
 
@@ -92,6 +93,7 @@ class ConvNet(TrainLoopMixin):
         self.batch_size_ = 0
         self.current_iter_ = 0
         self.parameters_, self.grad_parameters_, self.history_ = Matrix(), Matrix(), Matrix()
+        self.second_history_ = Matrix()   # Adagrad / RMSProp second moments, flat like history_; allocated only if an edge optimizer keeps one
         self.edge_slices_ = {}   # edge -> (offset, length) in the flat buffers
         self.train_dataset_ = None
         self.correct_accum_ = None
@@ -244,6 +246,10 @@ class ConvNet(TrainLoopMixin):
             self.grad_parameters_.AllocateGPUMemory(1, total, "grad parameters")
             self.grad_parameters_.Set(0.0)
             self.history_.AllocateGPUMemory(1, total, "optimizer history")   # flat, same layout
+            second = any(o is not None and o.NeedsSecondHistory() for e in self.edges_ if isinstance(e, EdgeWithWeight)
+                         for o in (e.weight_optimizer_, e.bias_optimizer_))
+            if second:
+                self.second_history_.AllocateGPUMemory(1, total, "optimizer second-moment history")
         offset = 0
         for e in self.edges_:
             mem = usage[e]
@@ -253,10 +259,13 @@ class ConvNet(TrainLoopMixin):
             self.parameters_.GetSlice(s, offset, offset + mem)
             e.SetMemory(s)
             if not fprop_only:
-                g, h = Matrix(), Matrix()
+                g, h, h2 = Matrix(), Matrix(), None
                 self.grad_parameters_.GetSlice(g, offset, offset + mem)
                 self.history_.GetSlice(h, offset, offset + mem)
-                e.SetGradMemory(g, h)
+                if second:
+                    h2 = Matrix()
+                    self.second_history_.GetSlice(h2, offset, offset + mem)
+                e.SetGradMemory(g, h, h2)
             self.edge_slices_[e] = (offset, mem)
             offset += ((mem + 127) // 128) * 128
         if self.is_root_ or self.exchange_ is None:
@@ -477,7 +486,7 @@ class ConvNet(TrainLoopMixin):
             done.record(self.side_stream_)
             torch.cuda.current_stream().wait_event(done)   # weight gradients (and side-stream updates) are in
             if self.overlap_update_:
-                Matrix.SGDMomentumStepMulti(bn_steps)
+                RunFusedSteps(bn_steps)
                 return
         # fused host: the plain SGD steps of every edge (AlexNet: five convolution banks and eight biases) leave as ONE launch behind the loop
         batch = list(bn_steps) if self.fused else None   # (+ the batch-norm gamma / beta steps planned during Bprop)
@@ -491,7 +500,7 @@ class ConvNet(TrainLoopMixin):
             else:
                 e.UpdateWeights()
         if batch:
-            Matrix.SGDMomentumStepMulti(batch)
+            RunFusedSteps(batch)
 
     # ---- data -------------------------------------------------------------------------------------------
     def SetupDataset(self, dataset):

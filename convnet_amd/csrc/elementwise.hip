@@ -3,6 +3,7 @@
 // cudamat/cudamat_kernels.cu (kernels); semantics pinned by eigenmat/eigenmat.cc (the CPU oracle).
 // All kernels stream float4 per lane where the pointers allow it and grid-stride over ~2048 blocks.
 #include <cfloat>
+#include <climits>
 #include <cmath>
 
 #include "common.h"
@@ -590,48 +591,189 @@ __device__ __forceinline__ void sgd_one(float& g, float& w, float& h, float l2, 
   w = w - h;
 }
 
-__device__ __forceinline__ void sgd_range(float* __restrict__ g, float* __restrict__ w, float* __restrict__ h, size_t n, bool vec, float l2, float clip,
-                                          float eps, float mom, size_t tid, size_t stride) {
+// The two second-moment optimizers of src/optimizer.cc:202-279, one fused pass each, under the same rule as sgd_one: every reference
+// statement is one separately rounded fp32 operation.  sqrtf and / are the correctly rounded ones (hipcc's default for fp32).
+//   adagrad_one: AdagradSGDOptimizer::Optimize — a = delta + sqrt((a - delta)^2 + g^2); g /= a; g *= sqrt(step + 1); then sgd_one.
+//   rmsprop_one: RMSPropSGDOptimizer::Optimize — h *= mom; L2; clip; a = sqrt(factor*a*a + (1 - factor)*g*g) left to right with
+//                1 - factor formed in float; g /= a; h += eps*g; w -= h.
+__device__ __forceinline__ void adagrad_one(float& g, float& w, float& h, float& a, float delta, float step_scale, float l2, float clip, float eps,
+                                            float mom) {
+#pragma clang fp contract(off)
+  const float c = a - delta;
+  const float cc = c * c;
+  const float gg = g * g;
+  const float s = cc + gg;
+  a = delta + sqrtf(s);
+  g = g / a;
+  g = g * step_scale;
+  sgd_one(g, w, h, l2, clip, eps, mom);
+}
+__device__ __forceinline__ void rmsprop_one(float& g, float& w, float& h, float& a, float factor, float l2, float clip, float eps, float mom) {
+#pragma clang fp contract(off)
+  h = h * mom;
+  if (l2 > 0.f) {
+    const float t = w * l2;
+    g = g + t;
+  }
+  if (clip > 0.f) g = g > clip ? clip : (g < -clip ? -clip : g);
+  const float fa = factor * a;
+  const float faa = fa * a;
+  const float omf = 1.f - factor;
+  const float og = omf * g;
+  const float ogg = og * g;
+  const float s = faa + ogg;
+  a = sqrtf(s);
+  g = g / a;
+  const float eg = eps * g;
+  h = h + eg;
+  w = w - h;
+}
+
+// An optimizer step as data: the hyper-parameters of one tensor and the per-element update over its N arrays (gradient, parameter,
+// momentum history[, second-moment history]), every one of them read and written back.
+struct SgdOp {
+  static constexpr int N = 3;
+  static constexpr bool kRefuseHuge = false;
+  float l2, clip, eps, mom;
+  __device__ __forceinline__ void operator()(float (&v)[N]) const { sgd_one(v[0], v[1], v[2], l2, clip, eps, mom); }
+};
+struct AdagradOp {
+  static constexpr int N = 4;
+  static constexpr bool kRefuseHuge = true;   // more than INT_MAX floats: ERROR_UNSUPPORTED, like the batch-norm entries
+  float delta, step_scale, l2, clip, eps, mom;
+  __device__ __forceinline__ void operator()(float (&v)[N]) const { adagrad_one(v[0], v[1], v[2], v[3], delta, step_scale, l2, clip, eps, mom); }
+};
+struct RmsPropOp {
+  static constexpr int N = 4;
+  static constexpr bool kRefuseHuge = true;
+  float factor, l2, clip, eps, mom;
+  __device__ __forceinline__ void operator()(float (&v)[N]) const { rmsprop_one(v[0], v[1], v[2], v[3], factor, l2, clip, eps, mom); }
+};
+// One tensor of a step.  The arrays never overlap (slices of different flat buffers).
+template <typename Op>
+struct StepItem {
+  float* p[Op::N];
+  unsigned long long n;
+  Op op;
+  int vec;   // every array 16-byte aligned
+};
+// The stream skeleton every fused step shares: grid-stride over 16-byte accesses when the pointers allow it, scalar tail (or all scalar).
+template <typename Op>
+__device__ __forceinline__ void step_range(const StepItem<Op>& t, size_t tid, size_t stride) {
+  constexpr int N = Op::N;
+  const size_t n = (size_t)t.n;
   size_t done = 0;
-  if (vec) {
+  if (t.vec) {
     const size_t n4 = n >> 2;
     for (size_t i = tid; i < n4; i += stride) {
-      f32x4 gv = reinterpret_cast<f32x4*>(g)[i], wv = reinterpret_cast<f32x4*>(w)[i], hv = reinterpret_cast<f32x4*>(h)[i];
+      f32x4 x[N];
+#pragma unroll
+      for (int k = 0; k < N; ++k) x[k] = reinterpret_cast<const f32x4*>(t.p[k])[i];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        float a = gv[e], b = wv[e], c = hv[e];
-        sgd_one(a, b, c, l2, clip, eps, mom);
-        gv[e] = a; wv[e] = b; hv[e] = c;
+        float v[N];
+#pragma unroll
+        for (int k = 0; k < N; ++k) v[k] = x[k][e];
+        t.op(v);
+#pragma unroll
+        for (int k = 0; k < N; ++k) x[k][e] = v[k];
       }
-      reinterpret_cast<f32x4*>(g)[i] = gv;
-      reinterpret_cast<f32x4*>(w)[i] = wv;
-      reinterpret_cast<f32x4*>(h)[i] = hv;
+#pragma unroll
+      for (int k = 0; k < N; ++k) reinterpret_cast<f32x4*>(t.p[k])[i] = x[k];
     }
     done = n4 << 2;
   }
-  for (size_t i = done + tid; i < n; i += stride) sgd_one(g[i], w[i], h[i], l2, clip, eps, mom);
+  for (size_t i = done + tid; i < n; i += stride) {
+    float v[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = t.p[k][i];
+    t.op(v);
+#pragma unroll
+    for (int k = 0; k < N; ++k) t.p[k][i] = v[k];
+  }
 }
-__global__ void sgd_kernel(float* __restrict__ g, float* __restrict__ w, float* __restrict__ h, size_t n, bool vec, float l2, float clip,
-                           float eps, float mom) {
-  sgd_range(g, w, h, n, vec, l2, clip, eps, mom, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
-}
-// Several tensors in ONE launch (sgd_momentum_step_multi): AlexNet's step updates 13 small tensors (the convolution banks and every
-// bias) with ~7 us launches of a few MB each; blockIdx.y picks the tensor, every tensor with its own hyper-parameters.  Same sgd_one per
-// element: bit-identical to one sgd_momentum_step per tensor.
+// Several tensors in ONE launch (the *_multi entries): AlexNet's step updates 13 small tensors (the convolution banks and every bias) with
+// ~7 us launches of a few MB each; blockIdx.y picks the tensor, every tensor with its own hyper-parameters.  Same per-element update:
+// bit-identical to one single-tensor call per tensor.
 constexpr int kSgdMulti = 16;
-struct SgdItem {
-  float *g, *w, *h;
-  unsigned long long n;
-  float l2, clip, eps, mom;
-  int vec, pad_;
+template <typename Op>
+struct StepBatch {
+  StepItem<Op> it[kSgdMulti];
 };
-struct SgdBatch {
-  SgdItem it[kSgdMulti];
-};
-__global__ void sgd_multi_kernel(const SgdBatch b) {
-  const SgdItem& t = b.it[blockIdx.y];
-  sgd_range(t.g, t.w, t.h, (size_t)t.n, t.vec != 0, t.l2, t.clip, t.eps, t.mom, (size_t)blockIdx.x * blockDim.x + threadIdx.x,
-            (size_t)gridDim.x * blockDim.x);
+template <typename Op>
+__device__ __forceinline__ void step_single(const StepItem<Op>& t) {
+  step_range(t, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
+}
+__global__ void sgd_kernel(const StepItem<SgdOp> t) { step_single(t); }
+__global__ void adagrad_kernel(const StepItem<AdagradOp> t) { step_single(t); }
+__global__ void rmsprop_kernel(const StepItem<RmsPropOp> t) { step_single(t); }
+__global__ void sgd_multi_kernel(const StepBatch<SgdOp> b) { step_single(b.it[blockIdx.y]); }
+__global__ void adagrad_multi_kernel(const StepBatch<AdagradOp> b) { step_single(b.it[blockIdx.y]); }
+__global__ void rmsprop_multi_kernel(const StepBatch<RmsPropOp> b) { step_single(b.it[blockIdx.y]); }
+
+// Host side of the skeleton.  `mats`: the N cudamats of one tensor in the order of StepItem::p, the parameter second.
+template <typename Op>
+int step_check(cudamat* const (&mats)[Op::N]) {
+  const size_t n = numel(mats[1]);
+  for (cudamat* m : mats)
+    if (!m->on_device) return ERROR_NOT_ON_DEVICE;
+  for (cudamat* m : mats)
+    if (numel(m) != n) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (Op::kRefuseHuge && n > (size_t)INT_MAX) return ERROR_UNSUPPORTED;
+  return 0;
+}
+template <typename Op>
+StepItem<Op> step_item(cudamat* const (&mats)[Op::N], const Op& op) {
+  StepItem<Op> t{};
+  t.vec = 1;
+  for (int k = 0; k < Op::N; ++k) {
+    t.p[k] = mats[k]->data_device;
+    t.vec &= al16(t.p[k]) ? 1 : 0;
+  }
+  t.n = numel(mats[1]);
+  t.op = op;
+  return t;
+}
+// bytes per element for KernelTimer: every array read, every array but the gradient written (what the step needs; the gradient's
+// write-back keeps fused and unfused training comparable tensor for tensor and is not counted, as in sgd_kernel's 20 bytes)
+template <typename Op>
+constexpr double step_bytes() { return 4.0 * (2 * Op::N - 1); }
+
+template <typename Op, typename K>
+int step_launch(K kernel, const char* name, const char* family, cudamat* const (&mats)[Op::N], const Op& op) {
+  if (int rc = step_check<Op>(mats)) return rc;
+  const size_t n = numel(mats[1]);
+  if (n == 0) return 0;
+  KernelTimer timer(name, family, 0.0, step_bytes<Op>() * n);
+  hipLaunchKernelGGL(kernel, dim3(blocks_for(n / 4 + 1)), dim3(kThreads), 0, stream(), step_item<Op>(mats, op));
+  return launch_status();
+}
+// `count` tensors in ceil(count / 16) launches; tensor(i, mats, op) fills in tensor i
+template <typename Op, typename K, typename F>
+int step_launch_multi(K kernel, const char* name, const char* family, int count, F tensor) {
+  cudamat* mats[Op::N];
+  Op op;
+  for (int i = 0; i < count; ++i) {
+    tensor(i, mats, op);
+    if (int rc = step_check<Op>(mats)) return rc;
+  }
+  for (int base = 0; base < count; base += kSgdMulti) {
+    StepBatch<Op> b{};
+    int m = 0;
+    size_t most = 0, total = 0;
+    for (int i = base; i < count && i < base + kSgdMulti; ++i) {
+      tensor(i, mats, op);
+      const size_t n = numel(mats[1]);
+      if (n == 0) continue;
+      b.it[m++] = step_item<Op>(mats, op);
+      most = n > most ? n : most;
+      total += n;
+    }
+    if (m == 0) continue;
+    KernelTimer timer(name, family, 0.0, step_bytes<Op>() * total);
+    hipLaunchKernelGGL(kernel, dim3(blocks_for(most / 4 + 1), m), dim3(kThreads), 0, stream(), b);
+  }
+  return launch_status();
 }
 
 }  // namespace chip
@@ -746,7 +888,14 @@ int divide_by_scalar(cudamat* mat, float alpha, cudamat* target) {
   return map2(target, mat, nullptr, [alpha] __device__(float x, float) { return x / alpha; });
 }
 int add_mult(cudamat* mat1, cudamat* mat2, float alpha) {
-  return map2(mat1, mat1, mat2, [alpha] __device__(float x, float y) { return x + alpha * y; });
+  // Matrix::Add(m, alpha) is one statement of the optimizers' unfused sequences (g += l2*w, h += epsilon*g): product rounded, then the
+  // sum, as the reference's CPU build computes it and as sgd_one / adagrad_one / rmsprop_one do, so fused and unfused steps are equal
+  // bit for bit.  (With alpha = 1 or -1, every other use in the hosts but the batch-norm running averages, an fma gives the same.)
+  return map2(mat1, mat1, mat2, [alpha] __device__(float x, float y) {
+#pragma clang fp contract(off)
+    const float t = alpha * y;
+    return x + t;
+  });
 }
 int add_elementwise(cudamat* mat1, cudamat* mat2, cudamat* target) {
   return map2(target, mat1, mat2, [] __device__(float x, float y) { return x + y; });
@@ -817,45 +966,94 @@ int softmax_ce_grad_correct(cudamat* logits, cudamat* labels, cudamat* probs, cu
 
 // g += l2*w; clip; g *= eps; h = mom*h + g; w -= h   (src/optimizer.cc:174-200, one pass, same op order)
 int sgd_momentum_step(cudamat* grad, cudamat* param, cudamat* history, float l2_decay, float gradient_clip, float epsilon, float momentum) {
-  const size_t n = numel(param);
-  if (!grad->on_device || !param->on_device || !history->on_device) return ERROR_NOT_ON_DEVICE;
-  if (numel(grad) != n || numel(history) != n) return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if (n == 0) return 0;
-  const bool vec = al16(grad->data_device) && al16(param->data_device) && al16(history->data_device);
-  KernelTimer timer("sgd_kernel", "sgd", 0.0, 20.0 * n);   // reads g, w, h; writes h, w (>= 20 bytes per parameter)
-  hipLaunchKernelGGL(sgd_kernel, dim3(blocks_for(n / 4 + 1)), dim3(kThreads), 0, stream(), grad->data_device, param->data_device,
-                     history->data_device, n, vec, l2_decay, gradient_clip, epsilon, momentum);
-  return launch_status();
+  cudamat* const mats[] = {grad, param, history};
+  // reads g, w, h; writes h, w (>= 20 bytes per parameter)
+  return step_launch<SgdOp>(sgd_kernel, "sgd_kernel", "sgd", mats, SgdOp{l2_decay, gradient_clip, epsilon, momentum});
 }
 
 // sgd_momentum_step on `count` tensors, each with its own hyper-parameters, in ceil(count / 16) launches
 int sgd_momentum_step_multi(int count, cudamat** grads, cudamat** params, cudamat** histories, const float* l2_decay, const float* gradient_clip,
                             const float* epsilon, const float* momentum) {
   if (count < 0 || (count > 0 && (!grads || !params || !histories || !l2_decay || !gradient_clip || !epsilon || !momentum))) return ERROR_GENERIC;
-  for (int i = 0; i < count; ++i) {
-    if (!grads[i]->on_device || !params[i]->on_device || !histories[i]->on_device) return ERROR_NOT_ON_DEVICE;
-    if (numel(grads[i]) != numel(params[i]) || numel(histories[i]) != numel(params[i])) return ERROR_INCOMPATIBLE_DIMENSIONS;
-  }
-  for (int base = 0; base < count; base += kSgdMulti) {
-    SgdBatch b{};
-    int m = 0;
-    size_t most = 0, total = 0;
-    for (int i = base; i < count && i < base + kSgdMulti; ++i) {
-      const size_t n = numel(params[i]);
-      if (n == 0) continue;
-      SgdItem& t = b.it[m++];
-      t.g = grads[i]->data_device; t.w = params[i]->data_device; t.h = histories[i]->data_device;
-      t.n = n;
-      t.l2 = l2_decay[i]; t.clip = gradient_clip[i]; t.eps = epsilon[i]; t.mom = momentum[i];
-      t.vec = al16(t.g) && al16(t.w) && al16(t.h);
-      most = n > most ? n : most;
-      total += n;
-    }
-    if (m == 0) continue;
-    KernelTimer timer("sgd_multi_kernel", "sgd", 0.0, 20.0 * total);
-    hipLaunchKernelGGL(sgd_multi_kernel, dim3(blocks_for(most / 4 + 1), m), dim3(kThreads), 0, stream(), b);
-  }
-  return launch_status();
+  return step_launch_multi<SgdOp>(sgd_multi_kernel, "sgd_multi_kernel", "sgd", count, [&](int i, cudamat* (&m)[3], SgdOp& op) {
+    m[0] = grads[i]; m[1] = params[i]; m[2] = histories[i];
+    op = SgdOp{l2_decay[i], gradient_clip[i], epsilon[i], momentum[i]};
+  });
+}
+
+// ---- Adagrad and RMSProp (src/optimizer.cc:202-279): the reference's three entries and the fused steps ------------------------------------
+namespace {
+// cudamat's checks for adagrad / rms_prop / divide_elementwise (cudamat.cu:2302-2314, 3326-3337): transposedness, then element count
+int second_moment_check(const cudamat* a, const cudamat* b, const cudamat* c) {
+  if (!a->on_device || !b->on_device || (c && !c->on_device)) return ERROR_NOT_ON_DEVICE;
+  if (a->is_trans != b->is_trans) return ERROR_TRANSPOSEDNESS;
+  if (numel(a) != numel(b) || (c && numel(a) != numel(c))) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  return 0;
+}
+}  // namespace
+
+int adagrad(cudamat* history, cudamat* grad, float delta) {
+  if (int rc = second_moment_check(history, grad, nullptr)) return rc;
+  return map2(history, history, grad, [delta] __device__(float h, float g) {
+#pragma clang fp contract(off)
+    const float c = h - delta;
+    const float cc = c * c;
+    const float gg = g * g;
+    const float s = cc + gg;
+    return delta + sqrtf(s);
+  });
+}
+int rms_prop(cudamat* history, cudamat* grad, float factor) {
+  if (int rc = second_moment_check(history, grad, nullptr)) return rc;
+  return map2(history, history, grad, [factor] __device__(float h, float g) {
+#pragma clang fp contract(off)
+    const float fh = factor * h;
+    const float fhh = fh * h;
+    const float omf = 1.f - factor;
+    const float og = omf * g;
+    const float ogg = og * g;
+    const float s = fhh + ogg;
+    return sqrtf(s);
+  });
+}
+int divide_elementwise(cudamat* mat1, cudamat* mat2, cudamat* target) {
+  if (int rc = second_moment_check(mat1, mat2, target)) return rc;
+  return map2(target, mat1, mat2, [] __device__(float x, float y) { return x / y; });
+}
+
+// AdagradSGDOptimizer::Optimize (src/optimizer.cc:226-231, then :174-200, non-Nesterov) in one pass; step_scale = (float)sqrt(step + 1)
+int adagrad_momentum_step(cudamat* grad, cudamat* param, cudamat* history, cudamat* adagrad_history, float delta, float step_scale, float l2_decay,
+                          float gradient_clip, float epsilon, float momentum) {
+  cudamat* const mats[] = {grad, param, history, adagrad_history};
+  // reads g, w, h, a; writes h, a, w
+  return step_launch<AdagradOp>(adagrad_kernel, "adagrad_kernel", "adagrad", mats,
+                                AdagradOp{delta, step_scale, l2_decay, gradient_clip, epsilon, momentum});
+}
+// RMSPropSGDOptimizer::Optimize (src/optimizer.cc:257-279) in one pass
+int rmsprop_momentum_step(cudamat* grad, cudamat* param, cudamat* history, cudamat* rms_history, float factor, float l2_decay, float gradient_clip,
+                          float epsilon, float momentum) {
+  cudamat* const mats[] = {grad, param, history, rms_history};
+  return step_launch<RmsPropOp>(rmsprop_kernel, "rmsprop_kernel", "rmsprop", mats, RmsPropOp{factor, l2_decay, gradient_clip, epsilon, momentum});
+}
+int adagrad_momentum_step_multi(int count, cudamat** grads, cudamat** params, cudamat** histories, cudamat** adagrad_histories, const float* delta,
+                                const float* step_scale, const float* l2_decay, const float* gradient_clip, const float* epsilon,
+                                const float* momentum) {
+  if (count < 0 || (count > 0 && (!grads || !params || !histories || !adagrad_histories || !delta || !step_scale || !l2_decay || !gradient_clip ||
+                                  !epsilon || !momentum)))
+    return ERROR_GENERIC;
+  return step_launch_multi<AdagradOp>(adagrad_multi_kernel, "adagrad_multi_kernel", "adagrad", count, [&](int i, cudamat* (&m)[4], AdagradOp& op) {
+    m[0] = grads[i]; m[1] = params[i]; m[2] = histories[i]; m[3] = adagrad_histories[i];
+    op = AdagradOp{delta[i], step_scale[i], l2_decay[i], gradient_clip[i], epsilon[i], momentum[i]};
+  });
+}
+int rmsprop_momentum_step_multi(int count, cudamat** grads, cudamat** params, cudamat** histories, cudamat** rms_histories, const float* factor,
+                                const float* l2_decay, const float* gradient_clip, const float* epsilon, const float* momentum) {
+  if (count < 0 || (count > 0 && (!grads || !params || !histories || !rms_histories || !factor || !l2_decay || !gradient_clip || !epsilon || !momentum)))
+    return ERROR_GENERIC;
+  return step_launch_multi<RmsPropOp>(rmsprop_multi_kernel, "rmsprop_multi_kernel", "rmsprop", count, [&](int i, cudamat* (&m)[4], RmsPropOp& op) {
+    m[0] = grads[i]; m[1] = params[i]; m[2] = histories[i]; m[3] = rms_histories[i];
+    op = RmsPropOp{factor[i], l2_decay[i], gradient_clip[i], epsilon[i], momentum[i]};
+  });
 }
 
 int init_random(rnd_struct* rnd_state, int seed) {

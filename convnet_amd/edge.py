@@ -116,7 +116,7 @@ class Edge:
     def SetMemory(self, p):
         pass
 
-    def SetGradMemory(self, p, hist=None):
+    def SetGradMemory(self, p, hist=None, hist2=None):
         pass
 
     def GetParameterMemoryRequirement(self):
@@ -300,7 +300,7 @@ class EdgeWithWeight(Edge):
 
     def UpdateWeights(self, batch=None):
         # src/edge_with_weight.cc:96-106.  `batch`: a list that collects the plain fused SGD steps of a whole net for ONE launch
-        # (ConvNet.UpdateWeights -> Matrix.SGDMomentumStepMulti); steps that are not plain run here as before.
+        # (ConvNet.UpdateWeights -> optimizer.RunFusedSteps, one multi launch per optimizer kind); steps that are not plain run here as before.
         if self.is_tied_:
             return
         if self.num_grads_received_ < self.num_shares_:
@@ -382,12 +382,12 @@ class EdgeWithWeight(Edge):
             return
         self._slice_params(p, self.weights_, self.bias_)
 
-    def SetGradMemory(self, p, hist=None):
+    def SetGradMemory(self, p, hist=None, hist2=None):
         if self.is_tied_:
             return
         self._slice_params(p, self.grad_weights_, self.grad_bias_)
         rows, bias_cols, _ = self._param_layout()
-        self._alloc_optimizers(rows, self._input_size(), bias_cols, hist)
+        self._alloc_optimizers(rows, self._input_size(), bias_cols, hist, hist2)
 
     # ---- the bias after the up-GEMM and its gradient after the outer-GEMM.  ``shared`` = F: a conv edge's shared bias, one value per
     # filter, on the (N*My*Mx, F) view of a frame.  ``frames`` = None: one frame, used whole (src/conv_edge.cc:145-149, 210-221);
@@ -437,22 +437,24 @@ class EdgeWithWeight(Edge):
                 db_temp.GetSlice(db_temp_slice, m * shared, (m + 1) * shared)
                 db_temp_slice.SumRows(db, scale_targets if m == 0 else 1, scale_outputs)
 
-    def _alloc_optimizers(self, rows, cols, bias_cols, hist):
+    def _alloc_optimizers(self, rows, cols, bias_cols, hist, hist2=None):
         """Optimizer state: either separate matrices (reference) or slices of a flat history
-        buffer laid out exactly like the parameter slice (``hist``)."""
-        if hist is not None:
-            hist.Reshape(rows, -1)
-            hw = Matrix()
-            hist.GetSlice(hw, 0, cols)
-            self.weight_optimizer_.AllocateMemory(rows, cols, hw)
-            if not self.has_no_bias_:
-                hb = Matrix()
-                hist.GetSlice(hb, cols, cols + bias_cols)
-                self.bias_optimizer_.AllocateMemory(1, rows * bias_cols, hb)
-        else:
-            self.weight_optimizer_.AllocateMemory(rows, cols)
-            if not self.has_no_bias_:
-                self.bias_optimizer_.AllocateMemory(1, rows * bias_cols)
+        buffer laid out exactly like the parameter slice (``hist``; ``hist2``: the same for the
+        second-moment history, sliced for the optimizers that keep one)."""
+        for h in (hist, hist2):
+            if h is not None:
+                h.Reshape(rows, -1)
+
+        def part(h, opt, start, end):
+            if h is None or (h is hist2 and not opt.NeedsSecondHistory()):
+                return None
+            m = Matrix()
+            h.GetSlice(m, start, end)
+            return m
+        w_opt, b_opt = self.weight_optimizer_, self.bias_optimizer_
+        w_opt.AllocateMemory(rows, cols, part(hist, w_opt, 0, cols), part(hist2, w_opt, 0, cols))
+        if not self.has_no_bias_:
+            b_opt.AllocateMemory(1, rows * bias_cols, part(hist, b_opt, cols, cols + bias_cols), part(hist2, b_opt, cols, cols + bias_cols))
 
 
 class ConvEdge(EdgeWithWeight):
@@ -499,11 +501,11 @@ class ConvEdge(EdgeWithWeight):
         return (d.num_output_channels, 1 if self.shared_bias_ else self._num_modules(),
                 (d.num_output_channels, d.kernel_size_x, d.kernel_size_y, d.num_input_channels * d.kernel_size_t))
 
-    def SetGradMemory(self, p, hist=None):
+    def SetGradMemory(self, p, hist=None, hist2=None):
         # src/conv_edge.cc:110-136: the two-step shared-bias gradient takes a temp row (host bookkeeping, no library call)
         if not self.is_tied_ and self.shared_bias_ and not self.has_no_bias_:
             Matrix.RegisterTempMemory(self.conv_desc_.num_output_channels * self._num_modules(), "shared bias")
-        super().SetGradMemory(p, hist)
+        super().SetGradMemory(p, hist, hist2)
 
     def _bias_view(self):
         """(shared, frames) of _add_bias / _bias_grad for this edge."""

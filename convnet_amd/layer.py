@@ -191,7 +191,7 @@ class Layer:
 
     def ApplyDerivativeofBatchNormalization(self, fused_steps=None):
         """The derivative and, as in the reference, the gamma / beta optimizer steps.  Fused: bn_bprop_fused (the state is only read);
-        with ``fused_steps`` (a list) the plain SGD steps are appended to it as data for the host's one sgd_momentum_step_multi launch
+        with ``fused_steps`` (a list) the plain steps are appended to it as data for the host's multi launch (optimizer.RunFusedSteps)
         instead of running here — nothing reads gamma or beta between here and the end of the step."""
         if self.fused:
             Matrix.BNBpropFused(self.deriv_, self.state_, self.gamma_, self.beta_, self.batch_sigma_, self.grad_gamma_, self.grad_beta_)

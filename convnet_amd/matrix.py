@@ -328,7 +328,10 @@ class Matrix:
             _chk(lib.mult_by_scalar(self.GetMat(), float(val), self.GetMat(), 0.0), "mult_by_scalar")
 
     def Divide(self, val):
-        _chk(lib.divide_by_scalar(self.GetMat(), float(val), self.GetMat()), "divide_by_scalar")
+        if isinstance(val, Matrix):
+            _chk(lib.divide_elementwise(self.GetMat(), val.GetMat(), self.GetMat()), "divide")
+        else:
+            _chk(lib.divide_by_scalar(self.GetMat(), float(val), self.GetMat()), "divide_by_scalar")
 
     def Subtract(self, m, target):
         _chk(lib.subtract_elementwise(self.GetMat(), m.GetMat(), target.GetMat()), "subtract")
@@ -581,6 +584,50 @@ class Matrix:
         arr = lambda k: (MP * n)(*[ctypes.pointer(it[k].mat_) for it in items])   # noqa: E731
         flt = lambda k: (ctypes.c_float * n)(*[float(it[k]) for it in items])    # noqa: E731
         _chk(lib.sgd_momentum_step_multi(n, arr(0), arr(1), arr(2), flt(3), flt(4), flt(5), flt(6)), "sgd step (multi)")
+
+    # ---- Adagrad / RMSProp (src/matrix.cc:1061-1075; fused entries: include/convnet_hip.h) ---------------------------------
+    @staticmethod
+    def AdagradUpdate(adagrad_history, gradient, delta):
+        _chk(lib.adagrad(adagrad_history.GetMat(), gradient.GetMat(), float(delta)), "adagrad update")
+
+    @staticmethod
+    def RMSPropUpdate(rms_history, gradient, factor):
+        _chk(lib.rms_prop(rms_history.GetMat(), gradient.GetMat(), float(factor)), "rms update")
+
+    @staticmethod
+    def AdagradMomentumStep(grad, param, history, adagrad_history, delta, step_scale, l2_decay, gradient_clip, epsilon, momentum):
+        _chk(lib.adagrad_momentum_step(grad.GetMat(), param.GetMat(), history.GetMat(), adagrad_history.GetMat(), float(delta), float(step_scale),
+                                       float(l2_decay), float(gradient_clip), float(epsilon), float(momentum)), "adagrad step")
+
+    @staticmethod
+    def RMSPropMomentumStep(grad, param, history, rms_history, factor, l2_decay, gradient_clip, epsilon, momentum):
+        _chk(lib.rmsprop_momentum_step(grad.GetMat(), param.GetMat(), history.GetMat(), rms_history.GetMat(), float(factor), float(l2_decay),
+                                       float(gradient_clip), float(epsilon), float(momentum)), "rmsprop step")
+
+    @staticmethod
+    def _second_moment_multi(fn, items, what):
+        # items: four matrices then the floats, per tensor, in the entry's argument order
+        n = len(items)
+        MP = ctypes.POINTER(_lib.cudamat)
+        mats = [(MP * n)(*[ctypes.pointer(it[k].mat_) for it in items]) for k in range(4)]
+        flts = [(ctypes.c_float * n)(*[float(it[k]) for it in items]) for k in range(4, len(items[0]))]
+        _chk(fn(n, *mats, *flts), what)
+
+    @staticmethod
+    def AdagradMomentumStepMulti(items):
+        """items: the arguments of AdagradMomentumStep per tensor — all of them in one launch per 16 (adagrad_momentum_step_multi)."""
+        if len(items) == 1:
+            Matrix.AdagradMomentumStep(*items[0])
+        elif items:
+            Matrix._second_moment_multi(lib.adagrad_momentum_step_multi, items, "adagrad step (multi)")
+
+    @staticmethod
+    def RMSPropMomentumStepMulti(items):
+        """items: the arguments of RMSPropMomentumStep per tensor — all of them in one launch per 16 (rmsprop_momentum_step_multi)."""
+        if len(items) == 1:
+            Matrix.RMSPropMomentumStep(*items[0])
+        elif items:
+            Matrix._second_moment_multi(lib.rmsprop_momentum_step_multi, items, "rmsprop step (multi)")
 
     @staticmethod
     def SGDMomentumStepNormLimit(grad, param, history, l2_decay, gradient_clip, epsilon, momentum, norm, constraint):

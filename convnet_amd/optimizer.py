@@ -1,5 +1,7 @@
-"""Optimizers — mirror of src/optimizer.{h,cc} for the hot path (SGD + momentum, the only optimizer
-the target configs use; Adagrad/RMSProp/LBFGS are out of scope)."""
+"""Optimizers — mirror of src/optimizer.{h,cc}: SGD + momentum (the optimizer of the target configs) and the two second-moment
+optimizers built on it, Adagrad and RMSProp, each with a one-pass fused step (include/convnet_hip.h).  LBFGS and shared_prior are out of
+scope."""
+import collections
 import ctypes
 import math
 
@@ -35,7 +37,11 @@ class Optimizer:
         # src/optimizer.cc:8-29
         if config.optimizer_type == "STOCHASTIC_GRADIENT_DESCENT":
             return SGDOptimizer(config)
-        raise SystemExit(f"Undefined optimizer {config.optimizer_type} (only SGD is on the hot path).")
+        if config.optimizer_type == "ADAGRAD_SGD":
+            return AdagradSGDOptimizer(config)
+        if config.optimizer_type == "RMSPROP_SGD":
+            return RMSPropSGDOptimizer(config)
+        raise SystemExit(f"Undefined optimizer {config.optimizer_type} (SGD, Adagrad and RMSProp are built; LBFGS is out of scope).")
 
     def __init__(self, c):
         self.epsilon_decay_type_ = c.epsilon_decay
@@ -87,8 +93,11 @@ class Optimizer:
     def NotifyStart(self, parameter):
         pass
 
-    def AllocateMemory(self, rows, cols):
+    def AllocateMemory(self, rows, cols, storage=None, storage2=None):
         pass
+
+    def NeedsSecondHistory(self):
+        return False
 
     def IsAllocated(self):
         return False
@@ -98,6 +107,31 @@ class Optimizer:
 
     def SaveParameters(self, file, prefix):
         pass
+
+
+# A plain fused step as DATA, per optimizer kind: the arguments of the kind's Matrix.*MomentumStep, and `multi`, the launch that runs a
+# list of them (one launch per 16 tensors).  PlanFusedStep returns one; RunFusedSteps launches a step's collection, one multi launch per kind.
+class SGDStep(collections.namedtuple("SGDStep", "gradient parameter history l2_decay gradient_clip epsilon momentum")):
+    multi = staticmethod(lambda items: Matrix.SGDMomentumStepMulti(items))
+
+
+class AdagradStep(collections.namedtuple("AdagradStep", "gradient parameter history adagrad_history delta step_scale l2_decay gradient_clip "
+                                                        "epsilon momentum")):
+    multi = staticmethod(lambda items: Matrix.AdagradMomentumStepMulti(items))
+
+
+class RMSPropStep(collections.namedtuple("RMSPropStep", "gradient parameter history rms_history factor l2_decay gradient_clip epsilon momentum")):
+    multi = staticmethod(lambda items: Matrix.RMSPropMomentumStepMulti(items))
+
+
+def RunFusedSteps(items):
+    """The planned steps of one training step (PlanFusedStep items of any kind): one multi launch per optimizer kind.  A net with only
+    SGD optimizers makes the one Matrix.SGDMomentumStepMulti call it always made."""
+    by_kind = {}
+    for it in items:
+        by_kind.setdefault(type(it), []).append(it)
+    for kind, group in by_kind.items():
+        kind.multi(group)
 
 
 class SGDOptimizer(Optimizer):
@@ -111,9 +145,10 @@ class SGDOptimizer(Optimizer):
         self.gradient_history_ = Matrix()
         self.fused = False
 
-    def AllocateMemory(self, rows, cols, storage=None):
+    def AllocateMemory(self, rows, cols, storage=None, storage2=None):
         """``storage``: optional Matrix slice of a flat history buffer (the reference allocates one
-        matrix per tensor, src/optimizer.cc:131-134; a flat buffer makes the state contiguous)."""
+        matrix per tensor, src/optimizer.cc:131-134; a flat buffer makes the state contiguous).  ``storage2``: the same for the
+        second-moment history of the subclasses that keep one."""
         if storage is not None:
             self.gradient_history_ = storage
             self.gradient_history_.Reshape(rows, cols)
@@ -148,15 +183,19 @@ class SGDOptimizer(Optimizer):
             parameter.Add(self.gradient_history_, -1)
 
     def PlanFusedStep(self, gradient, parameter):
-        """The plain fused step of Optimize as DATA — (gradient, parameter, history, l2, clip, epsilon, momentum) for
-        Matrix.SGDMomentumStepMulti — with the step counter advanced exactly as Optimize would; None when this optimizer's step is not the
-        plain one (unfused host, Nesterov, a norm limit / constraint, still before start_optimization_after): the caller runs Optimize."""
+        """The plain fused step of Optimize as DATA — an SGDStep (gradient, parameter, history, l2, clip, epsilon, momentum) for
+        Matrix.SGDMomentumStepMulti, or the subclass's kind, for RunFusedSteps — with the step counter advanced exactly as Optimize would;
+        None when this optimizer's step is not the plain one (unfused host, Nesterov, a norm limit / constraint, still before start_optimization_after): the caller runs Optimize."""
         if (not self.fused or self.nesterov_momentum_ or self.weight_norm_constraint_ > 0 or self.weight_norm_limit_ > 0 or
                 self.step_ < self.start_optimization_after_):
             return None
-        item = (gradient, parameter, self.gradient_history_, self.l2_decay_, self.gradient_clip_, self.GetDecayedEpsilon(), self.GetMomentum())
+        item = self._fused_item(gradient, parameter)
         self.step_ += 1
         return item
+
+    def _fused_item(self, gradient, parameter):
+        """This optimizer kind's plain fused step at the current step count: the subclasses' part of PlanFusedStep."""
+        return SGDStep(gradient, parameter, self.gradient_history_, self.l2_decay_, self.gradient_clip_, self.GetDecayedEpsilon(), self.GetMomentum())
 
     def Optimize(self, gradient, parameter):
         # src/optimizer.cc:174-200
@@ -186,5 +225,112 @@ class SGDOptimizer(Optimizer):
                     parameter.Add(gradient, -1)
                 else:
                     parameter.Add(self.gradient_history_, -1)
+            self.ApplyConstraints(parameter)
+        self.step_ += 1
+
+
+class _SecondMomentSGDOptimizer(SGDOptimizer):
+    """What AdagradSGDOptimizer and RMSPropSGDOptimizer share (src/optimizer.cc:202-255): a second history beside the momentum one, with
+    its initial value and its dataset name in a checkpoint."""
+    history_name_ = None
+
+    def __init__(self, c, initial):
+        super().__init__(c)
+        self.second_history_ = Matrix()
+        self.second_history_initial_ = initial
+
+    def NeedsSecondHistory(self):
+        return True
+
+    def AllocateMemory(self, rows, cols, storage=None, storage2=None):
+        super().AllocateMemory(rows, cols, storage)
+        if storage2 is not None:
+            self.second_history_ = storage2
+            self.second_history_.Reshape(rows, cols)
+        else:
+            self.second_history_.AllocateGPUMemory(rows, cols, "optimizer")
+        self.second_history_.Set(self.second_history_initial_)
+
+    def IsAllocated(self):
+        return self.second_history_.GetNumEls() > 0
+
+    def LoadParameters(self, file, prefix):
+        super().LoadParameters(file, prefix)
+        self.second_history_.ReadHDF5(file, f"{prefix}_{self.history_name_}")
+
+    def SaveParameters(self, file, prefix):
+        # The reference writes gradient_history_ a second time under this name (src/optimizer.cc:219-224, 250-255) and reads the
+        # dataset back into the second-moment history: its own checkpoints do not resume.  Here the dataset holds what is read back.
+        super().SaveParameters(file, prefix)
+        self.second_history_.WriteHDF5(file, f"{prefix}_{self.history_name_}")
+
+    def _fuses_now(self):
+        return self.fused and not self.nesterov_momentum_ and self.step_ >= self.start_optimization_after_
+
+    def _run_fused(self, gradient, parameter):
+        item = self._fused_item(gradient, parameter)
+        item.multi([item])
+        self.ApplyConstraints(parameter)
+        self.step_ += 1
+
+
+class AdagradSGDOptimizer(_SecondMomentSGDOptimizer):
+    history_name_ = "adagrad_history"
+
+    def __init__(self, c):
+        super().__init__(c, c.adagrad_delta)      # src/optimizer.cc:206-210: the history starts at delta
+        self.adagrad_delta_ = c.adagrad_delta
+
+    adagrad_history_ = property(lambda self: self.second_history_)
+
+    def _step_scale(self):
+        return float(np.float32(math.sqrt(self.step_ + 1)))   # sqrt(int) is the double one; Mult(float) rounds it once
+
+    def _fused_item(self, gradient, parameter):
+        return AdagradStep(gradient, parameter, self.gradient_history_, self.second_history_, self.adagrad_delta_, self._step_scale(),
+                           self.l2_decay_, self.gradient_clip_, self.GetDecayedEpsilon(), self.GetMomentum())
+
+    def Optimize(self, gradient, parameter):
+        # src/optimizer.cc:226-231.  The history update and the rescaling run on every call, also before start_optimization_after.
+        if self._fuses_now():
+            self._run_fused(gradient, parameter)
+            return
+        h = self.second_history_
+        h.AdagradUpdate(h, gradient, self.adagrad_delta_)      # Matrix::AdagradUpdate, a static of the history's class
+        gradient.Divide(self.second_history_)
+        gradient.Mult(self._step_scale())
+        super().Optimize(gradient, parameter)       # Nesterov, the unfused host or before the start: the reference's sequence there too
+
+
+class RMSPropSGDOptimizer(_SecondMomentSGDOptimizer):
+    history_name_ = "rms_history"
+
+    def __init__(self, c):
+        super().__init__(c, 1.0)                  # src/optimizer.cc:237-241
+        self.factor_ = c.rms_prop_factor
+
+    rms_history_ = property(lambda self: self.second_history_)
+
+    def _fused_item(self, gradient, parameter):
+        return RMSPropStep(gradient, parameter, self.gradient_history_, self.second_history_, self.factor_, self.l2_decay_, self.gradient_clip_,
+                           self.GetDecayedEpsilon(), self.GetMomentum())
+
+    def Optimize(self, gradient, parameter):
+        # src/optimizer.cc:257-279.  nesterov_momentum plays no part in here (the inherited NotifyStart still acts on it).
+        if self._fuses_now():
+            self._run_fused(gradient, parameter)
+            return
+        if self.step_ >= self.start_optimization_after_:
+            epsilon, momentum = self.GetDecayedEpsilon(), self.GetMomentum()
+            self.gradient_history_.Mult(momentum)
+            if self.l2_decay_ > 0:
+                gradient.Add(parameter, self.l2_decay_)
+            if self.gradient_clip_ > 0:
+                gradient.UpperBoundMod(self.gradient_clip_)
+            h = self.second_history_
+            h.RMSPropUpdate(h, gradient, self.factor_)             # Matrix::RMSPropUpdate, a static of the history's class
+            gradient.Divide(self.second_history_)
+            self.gradient_history_.Add(gradient, epsilon)
+            parameter.Add(self.gradient_history_, -1)
             self.ApplyConstraints(parameter)
         self.step_ += 1

@@ -390,11 +390,21 @@ int assign_scalar(cudamat* mat, float alpha);
 int add_scalar(cudamat* mat, float alpha, cudamat* target);
 int mult_by_scalar(cudamat* mat, float alpha, cudamat* target, float scale_targets);
 int divide_by_scalar(cudamat* mat, float alpha, cudamat* target);
-int add_mult(cudamat* mat1, cudamat* mat2, float alpha);                         /* mat1 += alpha*mat2 */
+int add_mult(cudamat* mat1, cudamat* mat2, float alpha);                         /* mat1 += alpha*mat2, product rounded first */
 int add_elementwise(cudamat* mat1, cudamat* mat2, cudamat* target);
 int subtract_elementwise(cudamat* mat1, cudamat* mat2, cudamat* target);
 int mult_elementwise(cudamat* mat1, cudamat* mat2, cudamat* target, float scale_targets);
 int apply_sqrt(cudamat* mat, cudamat* target);
+
+/* ---- Adagrad / RMSProp: cudamat.cuh:229,275-276 (src/optimizer.cc:226-231,257-279; csrc/elementwise.hip) --------------------------------
+ * The three entries behind AdagradSGDOptimizer and RMSPropSGDOptimizer.  Checks as in cudamat: ERROR_TRANSPOSEDNESS when the operands
+ * differ in is_trans, then ERROR_INCOMPATIBLE_DIMENSIONS when they differ in element count; views (slices of a flat buffer) are fine.
+ * Every statement is one separately rounded fp32 operation, square root and division the correctly rounded ones.
+ *  adagrad : history = delta + sqrt((history - delta)^2 + grad^2)
+ *  rms_prop: history = sqrt(factor*history*history + (1 - factor)*grad*grad), left to right, 1 - factor formed in float */
+int adagrad(cudamat* history, cudamat* grad, float delta);
+int rms_prop(cudamat* history, cudamat* grad, float factor);
+int divide_elementwise(cudamat* mat1, cudamat* mat2, cudamat* target);
 
 /* ---- batch normalisation: cudamat.cuh:298-303 (src/matrix.cc:1077-1102; csrc/batch_norm.hip) ------------------------------------
  * Column c of the (h, w) matrices is one channel's contiguous run (Layer::ApplyBatchNormalization reshapes the state to (-1, C)); the
@@ -455,6 +465,25 @@ int sgd_momentum_step_normlimit(cudamat* grad, cudamat* param, cudamat* history,
  * calls of sgd_momentum_step. */
 int sgd_momentum_step_multi(int count, cudamat** grads, cudamat** params, cudamat** histories, const float* l2_decay,
                             const float* gradient_clip, const float* epsilon, const float* momentum);   /* + ApplyConstraints (src/optimizer.cc:75-81), axis=1 */
+/* The second-moment optimizers in one pass over gradient, parameter and both histories, bit-identical to the reference's call sequences
+ * (and, like sgd_momentum_step, leaving in `grad` what that sequence leaves there):
+ *  adagrad_momentum_step: AdagradSGDOptimizer::Optimize (src/optimizer.cc:226-231, then :174-200, non-Nesterov) — adagrad(a, g, delta);
+ *                         g /= a; g *= step_scale; g += l2*w; clip; g *= epsilon; h = momentum*h + g; w -= h.  step_scale is the host's
+ *                         sqrt(step + 1), rounded to float once.  Replaces 9 passes.
+ *  rmsprop_momentum_step: RMSPropSGDOptimizer::Optimize (:257-279) — h *= momentum; g += l2*w; clip; rms_prop(a, g, factor); g /= a;
+ *                         h += epsilon*g; w -= h.
+ * The *_multi forms are the same steps on `count` tensors in one launch per 16 of them, like sgd_momentum_step_multi: bit-identical to
+ * `count` single calls.  ERROR_INCOMPATIBLE_DIMENSIONS on differing element counts, ERROR_UNSUPPORTED above INT_MAX (2^31 - 1) floats. */
+int adagrad_momentum_step(cudamat* grad, cudamat* param, cudamat* history, cudamat* adagrad_history, float delta, float step_scale,
+                          float l2_decay, float gradient_clip, float epsilon, float momentum);
+int rmsprop_momentum_step(cudamat* grad, cudamat* param, cudamat* history, cudamat* rms_history, float factor, float l2_decay,
+                          float gradient_clip, float epsilon, float momentum);
+int adagrad_momentum_step_multi(int count, cudamat** grads, cudamat** params, cudamat** histories, cudamat** adagrad_histories,
+                                const float* delta, const float* step_scale, const float* l2_decay, const float* gradient_clip,
+                                const float* epsilon, const float* momentum);
+int rmsprop_momentum_step_multi(int count, cudamat** grads, cudamat** params, cudamat** histories, cudamat** rms_histories,
+                                const float* factor, const float* l2_decay, const float* gradient_clip, const float* epsilon,
+                                const float* momentum);
 int softmax_ce_grad_correct(cudamat* logits, cudamat* labels, cudamat* probs, cudamat* deriv,
                             cudamat* correct_accum, float deriv_scale);
 int relu_dropout(rnd_struct* rnd_state, cudamat* mat, float dropprob, float scale);
