@@ -1,5 +1,6 @@
 """ctypes binding of libconvnet_hip.so — the same kind of binding the reference ships for its own
-C ABI (cudamat/cudamat.py:9-135, cudamat/cudamat_conv_gemm.py:4-117).
+C ABI (cudamat/cudamat.py:9-135, cudamat/cudamat_conv_gemm.py:4-117), with every restype / argtypes read from the prototypes of
+include/convnet_hip.h: a new entry needs its prototype there and nothing here, unless it brings a new type (_CTYPES).
 
 The product path has NO CPU fallback: if the HIP library is missing, import raises."""
 import ctypes
@@ -55,13 +56,46 @@ class KernelInfo(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("flops", ctypes.c_double), ("grid_blocks", ctypes.c_int), ("split_k", ctypes.c_int)]
 
 
+# C type spelling (whitespace normalised, `*` attached to the type) -> ctypes type: the whole type vocabulary of include/convnet_hip.h.
+# A prototype that uses a spelling missing here fails the import (header_signatures): there is no default.
+_CTYPES = {
+    "void": None, "int": ctypes.c_int, "unsigned int": ctypes.c_uint, "long": ctypes.c_long, "size_t": ctypes.c_size_t,
+    "float": ctypes.c_float, "double": ctypes.c_double, "bool": ctypes.c_bool,
+    "void*": ctypes.c_void_p, "void**": ctypes.POINTER(ctypes.c_void_p), "char*": ctypes.c_char_p, "const char*": ctypes.c_char_p,
+    "int*": ctypes.POINTER(ctypes.c_int), "float*": c_float_p, "const float*": c_float_p, "double*": ctypes.POINTER(ctypes.c_double),
+    "cudamat*": ctypes.POINTER(cudamat), "cudamat**": ctypes.POINTER(ctypes.POINTER(cudamat)), "Shape4D*": ctypes.POINTER(Shape4D),
+    "ConvDesc": ConvDesc, "rnd_struct*": ctypes.POINTER(rnd_struct), "ConvnetHipKernelInfo*": ctypes.POINTER(KernelInfo)}
+
+
+def _ctype(decl, named, proto):
+    """The ctypes type of a return type (named=False) or of a parameter declaration.  A parameter's type is the text before its
+    trailing identifier.  An unnamed parameter has none, so the last token is dropped only when it can be a name: when there is more
+    than one token, the text does not end in `*`, and the whole text is not itself a known type (`unsigned int`)."""
+    tok = decl.replace("*", " * ").split()
+    spell = lambda t: " ".join(t).replace(" *", "*")   # noqa: E731
+    if named and len(tok) > 1 and tok[-1] != "*" and spell(tok) not in _CTYPES:
+        tok = tok[:-1]
+    if spell(tok) not in _CTYPES:
+        raise ImportError(f"include/convnet_hip.h: '{proto}' uses the type '{spell(tok)}', which convnet_amd/_lib.py (_CTYPES) does not map")
+    return _CTYPES[spell(tok)]
+
+
+def header_signatures(text):
+    """{name: (restype, [argtypes])} of every prototype in the extern "C" block of a header like include/convnet_hip.h, whose prototypes
+    hold no function pointers, arrays or macros."""
+    body = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    body = body[body.index('extern "C" {'):]
+    sigs = {}
+    for res, name, args in re.findall(r"^[ \t]*([A-Za-z_][\w \t*]*?)\s*\b(\w+)\s*\(([^();{}]*)\)\s*;", body, flags=re.M):
+        proto = f"{' '.join(res.split())} {name}({' '.join(args.split())})"
+        args = [a for a in args.split(",") if a.split() not in ([], ["void"])]
+        sigs[name] = (_ctype(res, False, proto), [_ctype(a, True, proto) for a in args])
+    return sigs
+
+
 def declared_symbols(header_path=HEADER_PATH):
     """Every function name declared in include/convnet_hip.h."""
-    text = open(header_path).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    body = text[text.index('extern "C" {'):]
-    names = re.findall(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*\([^;{]*\)\s*;", body)
-    return sorted(set(n for n in names if n not in ("defined",)))
+    return sorted(header_signatures(open(header_path).read()))
 
 
 def _load():
@@ -75,164 +109,12 @@ def _load():
     # /opt/rocm's copy and hipSetDevice later fails with two runtimes in the process.
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    P, F, I = ctypes.POINTER, ctypes.c_float, ctypes.c_int
-    M, S = P(cudamat), P(Shape4D)
-
-    def sig(name, res, *args):
+    for name, (res, args) in header_signatures(open(HEADER_PATH).read()).items():
         if _ALT_LIB and not hasattr(lib, name):
-            return
+            continue
         fn = getattr(lib, name)
         fn.restype = res
-        fn.argtypes = list(args)
-
-    sig("convnet_hip_init", I, I)
-    sig("convnet_hip_shutdown", None)
-    sig("convnet_hip_set_stream", None, ctypes.c_void_p)
-    sig("convnet_hip_get_stream", ctypes.c_void_p)
-    sig("convnet_hip_reserve_workspace", I, ctypes.c_size_t)
-    sig("convnet_hip_version", ctypes.c_char_p)
-    sig("convnet_hip_set_matrix_path", None, I)
-    sig("convnet_hip_get_matrix_path", I)
-    sig("convnet_hip_set_patch_mode", None, I)
-    sig("convnet_hip_get_patch_mode", I)
-    sig("convnet_hip_set_deferred_epilogues", None, I)
-    sig("convnet_hip_get_deferred_epilogues", I)
-    sig("convnet_hip_deferred_absorbed", ctypes.c_long)
-    sig("convnet_hip_set_wgrad_tile", None, I)
-    sig("convnet_hip_get_wgrad_tile", I)
-    sig("get_last_cuda_error", ctypes.c_char_p)
-    sig("cuda_set_device", I, I)
-    sig("cuda_sync_threads", None)
-    for ev_fn in ("cuda_create_event", "cuda_record_event", "cuda_synchronize_event"):
-        sig(ev_fn, I, P(ctypes.c_void_p))
-    sig("cublas_init", I)
-    sig("cublas_shutdown", I)
-    sig("destroy_tex", I, M)
-    sig("convnet_hip_last_kernel_info", None, P(KernelInfo))
-    sig("convnet_hip_profile_enable", None, I)
-    sig("convnet_hip_profile_report", ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t)
-    sig("convnet_hip_probe_matrix_pipe", I, I, ctypes.c_double, ctypes.POINTER(ctypes.c_double))
-    # data-parallel exchange (csrc/comm.hip)
-    sig("convnet_hip_comm_unique_id", I, ctypes.c_char_p)
-    sig("convnet_hip_comm_init", I, I, I, ctypes.c_char_p)
-    sig("convnet_hip_comm_rank", I)
-    sig("convnet_hip_comm_size", I)
-    sig("convnet_hip_comm_max_slots", I)
-    sig("convnet_hip_comm_broadcast", I, P(cudamat), I)
-    sig("convnet_hip_comm_allreduce_avg", I, P(cudamat), ctypes.c_size_t, ctypes.c_size_t, I)
-    sig("convnet_hip_comm_wait", I, I)
-    sig("convnet_hip_comm_sync", I)
-    sig("convnet_hip_comm_destroy", I)
-    for n in ("allocate_device_memory", "free_device_memory", "copy_to_host", "copy_to_device"):
-        sig(n, I, M)
-    sig("copy_to_host_slice", I, M, ctypes.c_size_t, ctypes.c_size_t)
-    sig("copy_to_device_slice", I, M, ctypes.c_size_t, ctypes.c_size_t)
-    sig("copy_on_device", I, M, M)
-    sig("copy_transpose", I, M, M)
-    sig("reshape", I, M, I, I)
-    sig("get_slice", I, M, M, ctypes.c_uint, ctypes.c_uint)
-    sig("init_from_array", None, M, c_float_p, I, I)
-    sig("init_empty", I, M, I, I)
-    sig("write_at", I, M, I, I, F)
-    sig("read_from", F, M, I, I, P(I))
-    sig("extract_patches", I, M, M, M, M, M, I, I, I, I)
-    sig("shuffleColumns", I, M, M)
-    for n in ("add_col_vec", "div_by_col_vec", "mult_by_row_vec", "div_by_row_vec"):
-        sig(n, I, M, M, M)
-    sig("add_col_mult", I, M, M, M, F)
-    sig("add_to_each_pixel", I, M, M, M, F)
-    sig("normalize_by_axis", I, M, M, I)
-    for n in ("convUpGemm", "convDownGemm", "convUp", "convDown"):
-        sig(n, None, M, M, M, S, S, S, ConvDesc, F)
-    sig("convOutpGemm", None, M, M, M, S, S, S, ConvDesc, F, F)
-    sig("convOutp", None, M, M, M, S, S, S, ConvDesc, I, I, F, F)
-    sig("convUpBiasAct", None, M, M, M, M, S, S, S, ConvDesc, F, I)
-    # locally connected layers (csrc/local_conv.hip)
-    for n in ("localUp", "localDown", "localUpGemm", "localDownGemm"):
-        sig(n, None, M, M, M, S, S, S, ConvDesc, F)
-    for n in ("localOutp", "localOutpGemm"):
-        sig(n, None, M, M, M, S, S, S, ConvDesc, F, F)
-    sig("localUpBiasAct", None, M, M, M, M, S, S, S, ConvDesc, F, I)
-    # spatio-temporal (3-D) convolution and response norm (csrc/conv3d.hip): the reference's five entries and the fused ones
-    for n in ("convUp3DGemm", "convDown3DGemm"):
-        sig(n, None, M, M, M, S, S, S, ConvDesc, F)
-    sig("convOutp3DGemm", None, M, M, M, S, S, S, ConvDesc, F, F)
-    for n in ("ResponseNormCrossMap3DGemm", "ResponseNormCrossMap3DRelu"):
-        sig(n, None, M, M, I, I, F, F, ctypes.c_bool, I)
-    sig("ResponseNormCrossMap3DUndoGemm", None, M, M, M, I, I, F, F, ctypes.c_bool, I)
-    sig("convUp3DBiasAct", None, M, M, M, M, S, S, S, ConvDesc, F, I)
-    sig("convDown3DMask", None, M, M, M, M, S, S, S, ConvDesc, F, F)
-    sig("convOutp3DBias", None, M, M, M, M, S, S, S, ConvDesc, F, F)
-    sig("convDownMask", None, M, M, M, M, S, S, S, ConvDesc, F, F)
-    sig("dotMask", I, M, M, M, M, F, F, F)
-    sig("MaxPoolUndoRelu", None, M, M, M, M, S, S, ConvDesc, F)
-    sig("MaxPoolMask", I, M, M, M, S, S, ConvDesc)
-    sig("MaxPoolUndoMask", I, M, M, M, S, S, ConvDesc, F, I)
-    sig("convOutpBias", None, M, M, M, M, S, S, S, ConvDesc, F, F)
-    for n in ("MaxPoolGemm", "AvgPoolGemm"):
-        sig(n, None, M, M, S, S, ConvDesc, F, F)
-    for n in ("MaxPool", "AvgPool"):
-        sig(n, None, M, M, S, S, ConvDesc)
-    for n in ("MaxPoolUndoGemm", "MaxPoolUndo"):
-        sig(n, None, M, M, M, M, S, S, ConvDesc, F)
-    for n in ("AvgPoolUndoGemm", "AvgPoolUndo"):
-        sig(n, None, M, M, S, S, ConvDesc, F)
-    for n in ("ResponseNormCrossMapGemm", "ResponseNormCrossMap", "ResponseNormCrossMapRelu"):
-        sig(n, None, M, M, I, I, F, F, ctypes.c_bool)
-    sig("ResponseNormCrossMapUndoGemm", None, M, M, M, I, I, F, F, ctypes.c_bool)
-    sig("ResponseNormCrossMapUndo", None, M, M, M, M, I, I, F, F, ctypes.c_bool)
-    sig("dot", I, M, M, M, F, F)
-    sig("dotBiasAct", I, M, M, M, M, F, F, I)
-    sig("vdot", F, M, M, P(I))
-    sig("add_row_vec", I, M, M, M)
-    sig("add_row_mult", I, M, M, M, F)
-    sig("sum_by_axis", I, M, M, I, F, F)
-    sig("sqsum_by_axis", I, M, M, I, F, F)
-    sig("sum_all", F, M, P(I))
-    sig("euclid_norm", F, M, P(I))
-    sig("normlimit_by_axis", I, M, M, I, F, I)
-    sig("lower_bound_scalar", I, M, F, M)
-    sig("upper_bound_mod_scalar", I, M, F, M)
-    sig("apply_rectified_linear_deriv", I, M, M, M)
-    sig("assign_scalar", I, M, F)
-    sig("add_scalar", I, M, F, M)
-    sig("mult_by_scalar", I, M, F, M, F)
-    sig("divide_by_scalar", I, M, F, M)
-    sig("add_mult", I, M, M, F)
-    sig("add_elementwise", I, M, M, M)
-    sig("subtract_elementwise", I, M, M, M)
-    sig("mult_elementwise", I, M, M, M, F)
-    sig("apply_sqrt", I, M, M)
-    sig("softmax_row_major", I, M, M)
-    sig("softmax_row_major_multi", I, M, I, M)
-    sig("apply_softmax_grad_row_major", I, M, M, M)
-    sig("get_softmax_correct_row_major", I, M, M, M)
-    sig("get_softmax_cross_entropy_row_major", I, M, M, M, F)
-    sig("softmax_ce_grad_correct", I, M, M, M, M, M, F)
-    sig("sgd_momentum_step", I, M, M, M, F, F, F, F)
-    # batch normalisation (csrc/batch_norm.hip): the reference's three cudamat entries and the two fused ones
-    sig("bn_bprop_inplace", I, M, M, M)
-    sig("bn_bprop", I, M, M, M, M, M, M, F)
-    sig("bn_grad", I, M, M, M, M, M, M)
-    sig("bn_fprop_act", I, M, M, M, M, M, M, M, F, F, I, I)
-    sig("bn_bprop_fused", I, M, M, M, M, M, M, M)
-    sig("sgd_momentum_step_normlimit", I, M, M, M, F, F, F, F, F, I)
-    sig("sgd_momentum_step_multi", I, I, P(M), P(M), P(M), c_float_p, c_float_p, c_float_p, c_float_p)
-    # Adagrad / RMSProp (csrc/elementwise.hip): the reference's three cudamat entries and the fused steps
-    sig("adagrad", I, M, M, F)
-    sig("rms_prop", I, M, M, F)
-    sig("divide_elementwise", I, M, M, M)
-    sig("adagrad_momentum_step", I, M, M, M, M, F, F, F, F, F, F)
-    sig("rmsprop_momentum_step", I, M, M, M, M, F, F, F, F, F)
-    sig("adagrad_momentum_step_multi", I, I, P(M), P(M), P(M), P(M), *[c_float_p] * 6)
-    sig("rmsprop_momentum_step_multi", I, I, P(M), P(M), P(M), P(M), *[c_float_p] * 5)
-    R = P(rnd_struct)
-    sig("init_random", I, R, I)
-    sig("fill_with_rand", I, R, M)
-    sig("fill_with_randn", I, R, M)
-    sig("sample_bernoulli", I, R, M, M)
-    sig("dropout", I, R, M, F, F, F)
-    sig("relu_dropout", I, R, M, F, F)
+        fn.argtypes = args
     return lib
 
 

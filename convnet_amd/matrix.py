@@ -573,17 +573,20 @@ class Matrix:
     def SGDMomentumStepMulti(items):
         """items: (grad, param, history, l2_decay, gradient_clip, epsilon, momentum) per tensor — sgd_momentum_step on all of them in one
         launch per 16 (include/convnet_hip.h: sgd_momentum_step_multi); an older build of the library gets one call per tensor."""
-        if not items:
-            return
         if not hasattr(lib, "sgd_momentum_step_multi") or len(items) == 1:
             for it in items:
                 Matrix.SGDMomentumStep(*it)
-            return
+        elif items:
+            Matrix._step_multi(lib.sgd_momentum_step_multi, items, 3, "sgd step (multi)")
+
+    @staticmethod
+    def _step_multi(fn, items, n_mats, what):
+        # items: n_mats matrices then the floats, per tensor, in the entry's argument order
         n = len(items)
         MP = ctypes.POINTER(_lib.cudamat)
-        arr = lambda k: (MP * n)(*[ctypes.pointer(it[k].mat_) for it in items])   # noqa: E731
-        flt = lambda k: (ctypes.c_float * n)(*[float(it[k]) for it in items])    # noqa: E731
-        _chk(lib.sgd_momentum_step_multi(n, arr(0), arr(1), arr(2), flt(3), flt(4), flt(5), flt(6)), "sgd step (multi)")
+        mats = [(MP * n)(*[ctypes.pointer(it[k].mat_) for it in items]) for k in range(n_mats)]
+        flts = [(ctypes.c_float * n)(*[float(it[k]) for it in items]) for k in range(n_mats, len(items[0]))]
+        _chk(fn(n, *mats, *flts), what)
 
     # ---- Adagrad / RMSProp (src/matrix.cc:1061-1075; fused entries: include/convnet_hip.h) ---------------------------------
     @staticmethod
@@ -605,21 +608,12 @@ class Matrix:
                                        float(gradient_clip), float(epsilon), float(momentum)), "rmsprop step")
 
     @staticmethod
-    def _second_moment_multi(fn, items, what):
-        # items: four matrices then the floats, per tensor, in the entry's argument order
-        n = len(items)
-        MP = ctypes.POINTER(_lib.cudamat)
-        mats = [(MP * n)(*[ctypes.pointer(it[k].mat_) for it in items]) for k in range(4)]
-        flts = [(ctypes.c_float * n)(*[float(it[k]) for it in items]) for k in range(4, len(items[0]))]
-        _chk(fn(n, *mats, *flts), what)
-
-    @staticmethod
     def AdagradMomentumStepMulti(items):
         """items: the arguments of AdagradMomentumStep per tensor — all of them in one launch per 16 (adagrad_momentum_step_multi)."""
         if len(items) == 1:
             Matrix.AdagradMomentumStep(*items[0])
         elif items:
-            Matrix._second_moment_multi(lib.adagrad_momentum_step_multi, items, "adagrad step (multi)")
+            Matrix._step_multi(lib.adagrad_momentum_step_multi, items, 4, "adagrad step (multi)")
 
     @staticmethod
     def RMSPropMomentumStepMulti(items):
@@ -627,7 +621,7 @@ class Matrix:
         if len(items) == 1:
             Matrix.RMSPropMomentumStep(*items[0])
         elif items:
-            Matrix._second_moment_multi(lib.rmsprop_momentum_step_multi, items, "rmsprop step (multi)")
+            Matrix._step_multi(lib.rmsprop_momentum_step_multi, items, 4, "rmsprop step (multi)")
 
     @staticmethod
     def SGDMomentumStepNormLimit(grad, param, history, l2_decay, gradient_clip, epsilon, momentum, norm, constraint):

@@ -229,7 +229,7 @@ void convOutp(cudamat* images, cudamat* derivs, cudamat* targets,
               ConvDesc conv_desc, int partialSumY, int partialSumX, float scaleTargets,
               float scaleOutput);
 
-/* ---- locally connected layers: cudamat_conv.cuh:14-33 and cudamat_conv_gemm.cuh:56-69 (src/local_edge.cc) -------------------------
+/* ---- locally connected layers: cudamat_conv.cuh:14-33 and cudamat_conv_gemm.cuh:56-69 (src/local_edge.cc; csrc/local_conv.hip) ----
  * A convolution whose every module (output pixel m = my*Mx + mx, M = My*Mx) has its own filter bank.  Layouts as above; the bank is
  * (F, Kx*Ky*C*M) column-major: module m owns the F*K floats (K = Kx*Ky*C) at offset m*F*K, and element (f, c, ky, kx) of that block sits at
  * f + F*(kx + Kx*(ky + Ky*c)) — exactly a conv bank.  Its Shape4D is (F, Kx, Ky, C*My*Mx) (local_edge.cc SetMemory).
@@ -271,7 +271,7 @@ void localUpBiasAct(cudamat* images, cudamat* filters, cudamat* bias, cudamat* t
                     Shape4D* images_shape, Shape4D* filters_shape, Shape4D* targets_shape,
                     ConvDesc conv_desc, float scaleTargets, int relu);
 
-/* ---- spatio-temporal (3-D) convolution: cudamat_conv_gemm.cuh:115-138 (cudamat_conv3d_gemm.cu; src/conv_edge.cc:153-245) ----------
+/* ---- spatio-temporal (3-D) convolution: cudamat_conv_gemm.cuh:115-138 (cudamat_conv3d_gemm.cu; src/conv_edge.cc:153-245; csrc/conv3d.hip)
  * Time is the OUTERMOST index.  Activations are (N, X*Y*C*T): element (n, x, y, c, t) at n + N*(x + W*(y + H*(c + C*t))), Shape4D
  * (N, X, Y, C*T); frame t is the column range [t*X*Y*C, (t+1)*X*Y*C).  The bank is (F, Kx*Ky*C*Kt): element (f, kx, ky, c, kt) at
  * f + F*(kx + Kx*(ky + Ky*(c + C*kt))), Shape4D (F, Kx, Ky, C*Kt).  C = conv_desc.num_input_channels, F = conv_desc.num_output_channels,

@@ -5,17 +5,53 @@ import numpy as np
 from convnet_amd.matrix import Matrix, make_conv_desc
 
 
-def _mat(arr, rows, cols, shape4=None):
-    m = Matrix()
-    m.AllocateGPUMemory(rows, cols)
-    m.FromNumpy(arr)
+def _mat(arr, rows, cols, shape4=None, guard=(0, 0)):
+    """numpy -> device Matrix (rows, cols), with its Shape4D when given.  guard = (columns before, columns after): the tensor then sits
+    between that many columns of 7.0 in one allocation, and (the view handed to the library, the owning matrix) is returned."""
+    before, after = guard
+    assert np.size(arr) == rows * cols, (np.shape(arr), rows, cols)
+    full = Matrix()
+    full.AllocateGPUMemory(rows, before + cols + after)
+    full.FromNumpy(np.concatenate([np.full(before * rows, 7.0, np.float32), np.asarray(arr, np.float32).reshape(-1),
+                                   np.full(after * rows, 7.0, np.float32)]))
+    m = full
+    if before or after:
+        m = Matrix()
+        full.GetSlice(m, before, before + cols)
     if shape4:
         m.SetShape4D(*shape4)
-    return m
+    return (m, full) if before or after else m
 
 
 def _desc(g, pool=False):
-    return make_conv_desc(g.C, g.C if pool else g.F, g.Ky, g.Kx, g.sy, g.sx, g.pady, g.padx)
+    d = make_conv_desc(g.C, g.C if pool else g.F, g.Ky, g.Kx, g.sy, g.sx, g.pady, g.padx)
+    if hasattr(g, "Kt"):
+        d.kernel_size_t, d.stride_t, d.padding_t = g.Kt, g.st, -g.padt
+    return d
+
+
+# A geometry's tensors as device matrices.  Activations are CHWN with time outermost (include/convnet_hip.h): T (Mt) frames for a 3-D
+# geometry, one for the 2-D and LOCAL ones.  The family is read off the geometry: T / Mt / Kt / st / padt exist on conv3d_ref.Geom3D
+# only, M on local_ref.LocalGeom only; a 2-D geometry that grew one of these names would change family here.
+def _x(g, a, guard=(0, 0)):
+    T = getattr(g, "T", 1)
+    return _mat(a, g.N, g.W * g.H * g.C * T, (g.N, g.W, g.H, g.C * T), guard)
+
+
+def _y(g, a, guard=(0, 0), pool=False):
+    F = (g.C if pool else g.F) * getattr(g, "Mt", 1)
+    return _mat(a, g.N, g.Mx * g.My * F, (g.N, g.Mx, g.My, F), guard)
+
+
+def _w(g, a, guard=(0, 0)):
+    """a convolution's bank, with Kt taps in time for a 3-D geometry"""
+    C = g.C * getattr(g, "Kt", 1)
+    return _mat(a, g.F, g.Kx * g.Ky * C, (g.F, g.Kx, g.Ky, C), guard)
+
+
+def _w_local(g, a, guard=(0, 0)):
+    """a LOCAL edge's bank: one convolution bank per module"""
+    return _mat(a, g.F, g.K * g.M, (g.F, g.Kx, g.Ky, g.C * g.M), guard)
 
 
 class HipImpl:

@@ -32,17 +32,15 @@ def M():
     return Matrix
 
 
-def _mat(M, a):
+def _mat(a):
     """(C, H) array -> device Matrix (H, C): column c is row c of `a`."""
+    from hip_adapter import _mat as device_mat
     a = np.asarray(a, np.float32)
-    m = M()
-    m.AllocateGPUMemory(a.shape[1], a.shape[0])
-    m.FromNumpy(a.reshape(-1))
-    return m
+    return device_mat(a, a.shape[1], a.shape[0])
 
 
-def _vec(M, v):
-    return _mat(M, np.asarray(v, np.float32).reshape(-1, 1))
+def _vec(v):
+    return _mat(np.asarray(v, np.float32).reshape(-1, 1))
 
 
 def _host(m, C):
@@ -70,7 +68,7 @@ def _inputs(C, H, seed):
 @pytest.mark.parametrize("train, relu", [(1, 0), (1, 1), (0, 0), (0, 1)])
 def test_fused_forward_matches_bn_ref(M, C, H, train, relu):
     _, x, gamma, beta, mu, sigma = _inputs(C, H, C + H)
-    st, g, b, m, s, bm, bs = _mat(M, x), _vec(M, gamma), _vec(M, beta), _vec(M, mu), _vec(M, sigma), _vec(M, np.zeros(C)), _vec(M, np.zeros(C))
+    st, g, b, m, s, bm, bs = _mat(x), _vec(gamma), _vec(beta), _vec(mu), _vec(sigma), _vec(np.zeros(C)), _vec(np.zeros(C))
     M.BNFpropAct(st, g, b, m, s, bm, bs, 0.9, 1e-5, train, relu)
     y, mu_r, sigma_r, mb, sb = bn_ref.fprop(x, gamma, beta, mu, sigma, 0.9, 1e-5, train, relu=bool(relu))
     assert _err(_host(st, C), y) < 2e-5
@@ -89,8 +87,8 @@ def test_fused_backward_matches_bn_ref(M, C, H, relu):
     if relu:
         d = np.where(state > 0, d, 0).astype(np.float32)   # ReLU' (applied before BN', by the edge's epilogue or the layer)
     sb = sb.astype(np.float32)
-    dv, sv, dg, db = _mat(M, d), _mat(M, state), _vec(M, np.zeros(C)), _vec(M, np.zeros(C))
-    M.BNBpropFused(dv, sv, _vec(M, gamma), _vec(M, beta), _vec(M, sb), dg, db)
+    dv, sv, dg, db = _mat(d), _mat(state), _vec(np.zeros(C)), _vec(np.zeros(C))
+    M.BNBpropFused(dv, sv, _vec(gamma), _vec(beta), _vec(sb), dg, db)
     ref, dgamma, dbeta = bn_ref.bprop(d, state, gamma, beta, sb)
     assert _err(_host(dv, C), ref) < 2e-5
     assert _err(_v(dg), dgamma) < 1e-5 and _err(_v(db), dbeta) < 1e-5
@@ -127,8 +125,8 @@ def test_cudamat_entries_match_eigenmat(M, C, H):
         fn = lib._Z8bn_bpropP8eigenmatS0_S0_S0_S0_S0_f
         assert fn(*[ctypes.byref(e) for _, e in t_host], ctypes.c_float(st)) == 0
         want = t_host[5][0]
-        t = _mat(M, tgt)
-        M.BNBprop(_mat(M, d), _mat(M, x), _vec(M, gamma), _vec(M, mu), _vec(M, sigma), t, st)
+        t = _mat(tgt)
+        M.BNBprop(_mat(d), _mat(x), _vec(gamma), _vec(mu), _vec(sigma), t, st)
         assert _err(_host(t, C), want) < 1e-4
         assert _err(want, bn_ref.bn_bprop(d, x, gamma, mu, sigma, tgt, st)) < 1e-4
     # bn_grad
@@ -137,25 +135,25 @@ def test_cudamat_entries_match_eigenmat(M, C, H):
     dg, db = args[4][0], args[5][0]
     fn = lib._Z7bn_gradP8eigenmatS0_S0_S0_S0_S0_
     assert fn(*[ctypes.byref(e) for _, e in args]) == 0
-    gg, gb = _vec(M, np.zeros(C)), _vec(M, np.zeros(C))
-    M.BNGrad(_mat(M, d), _mat(M, x), _vec(M, mu), _vec(M, sigma), gg, gb)
+    gg, gb = _vec(np.zeros(C)), _vec(np.zeros(C))
+    M.BNGrad(_mat(d), _mat(x), _vec(mu), _vec(sigma), gg, gb)
     scale_g = np.abs((x - mu[:, None]) / sigma[:, None] * d).sum(axis=1)
     assert (np.abs(_v(gg) - dg.reshape(-1)) / scale_g).max() < 1e-5
     assert (np.abs(_v(gb) - db.reshape(-1)) / np.abs(d).sum(axis=1)).max() < 1e-5
     # bn_bprop_inplace: eigenmat's has no return path (module docstring); against its restatement
-    dv, dgm = _mat(M, d), _vec(M, np.zeros(C))
-    M.BNBpropInplace(dv, _mat(M, x), dgm)
+    dv, dgm = _mat(d), _vec(np.zeros(C))
+    M.BNBpropInplace(dv, _mat(x), dgm)
     want, wdg = bn_ref.bn_bprop_inplace(d, x)
     assert _err(_host(dv, C), want) < 2e-5 and _err(_v(dgm), wdg) < 1e-5
 
 
 def test_cudamat_entries_check_dimensions(M):
     from convnet_amd.matrix import MatrixError
-    a, b = _mat(M, np.zeros((3, 10))), _mat(M, np.zeros((4, 10)))
+    a, b = _mat(np.zeros((3, 10))), _mat(np.zeros((4, 10)))
     with pytest.raises(MatrixError, match="dimensions"):
-        M.BNBpropInplace(a, b, _vec(M, np.zeros(3)))
+        M.BNBpropInplace(a, b, _vec(np.zeros(3)))
     with pytest.raises(MatrixError, match="dimensions"):
-        M.BNGrad(a, a, _vec(M, np.zeros(3)), _vec(M, np.zeros(2)), _vec(M, np.zeros(3)), _vec(M, np.zeros(3)))
+        M.BNGrad(a, a, _vec(np.zeros(3)), _vec(np.zeros(2)), _vec(np.zeros(3)), _vec(np.zeros(3)))
 
 
 def test_bn_calls_are_bit_reproducible(M):
@@ -164,10 +162,10 @@ def test_bn_calls_are_bit_reproducible(M):
     d = rng.standard_normal((C, H)).astype(np.float32)
     outs = []
     for _ in range(2):
-        st, m, s, bm, bs = _mat(M, x), _vec(M, mu), _vec(M, sigma), _vec(M, np.zeros(C)), _vec(M, np.zeros(C))
-        M.BNFpropAct(st, _vec(M, gamma), _vec(M, beta), m, s, bm, bs, 0.9, 1e-5, 1, 1)
-        dv, dg, db = _mat(M, d), _vec(M, np.zeros(C)), _vec(M, np.zeros(C))
-        M.BNBpropFused(dv, st, _vec(M, gamma), _vec(M, beta), bs, dg, db)
+        st, m, s, bm, bs = _mat(x), _vec(mu), _vec(sigma), _vec(np.zeros(C)), _vec(np.zeros(C))
+        M.BNFpropAct(st, _vec(gamma), _vec(beta), m, s, bm, bs, 0.9, 1e-5, 1, 1)
+        dv, dg, db = _mat(d), _vec(np.zeros(C)), _vec(np.zeros(C))
+        M.BNBpropFused(dv, st, _vec(gamma), _vec(beta), bs, dg, db)
         outs.append([t.ToNumpy() for t in (st, m, s, bm, bs, dv, dg, db)])
     for a, b in zip(*outs):
         assert np.array_equal(a, b)

@@ -34,53 +34,12 @@ def matrix_path(request, gpu):
 
 
 GUARD = 3   # guard columns before and after a guarded tensor
-
-
-def _mat(arr, rows, cols, shape4=None, guard=False):
-    """(view handed to the library, owning matrix).  guard: the view sits between GUARD columns of 7.0 on either side."""
-    from convnet_amd.matrix import Matrix
-    a = np.ascontiguousarray(arr, np.float32).reshape(-1)
-    assert a.size == rows * cols
-    full = Matrix()
-    if guard:
-        pad = np.full(GUARD * rows, 7.0, np.float32)
-        full.AllocateGPUMemory(rows, cols + 2 * GUARD)
-        full.FromNumpy(np.concatenate([pad, a, pad]))
-        m = Matrix()
-        full.GetSlice(m, GUARD, GUARD + cols)
-    else:
-        full.AllocateGPUMemory(rows, cols)
-        full.FromNumpy(a)
-        m = full
-    if shape4:
-        m.SetShape4D(*shape4)
-    return m, full
+GUARDED = (GUARD, GUARD)
 
 
 def _guards_intact(full, rows):
     a = full.ToNumpy().reshape(-1)
     return bool(np.all(a[:GUARD * rows] == 7.0) and np.all(a[-GUARD * rows:] == 7.0))
-
-
-def _desc(g, pool=False):
-    from convnet_amd.matrix import make_conv_desc
-    d = make_conv_desc(g.C, g.C if pool else g.F, g.Ky, g.Kx, g.sy, g.sx, g.pady, g.padx)
-    d.kernel_size_t, d.stride_t, d.padding_t = g.Kt, g.st, -g.padt
-    return d
-
-
-def _x(g, a, guard=False, T=None):
-    T = T or g.T
-    return _mat(a, g.N, g.H * g.W * g.C * T, (g.N, g.W, g.H, g.C * T), guard)
-
-
-def _y(g, a, guard=False, pool=False):
-    F = g.C if pool else g.F
-    return _mat(a, g.N, g.My * g.Mx * F * g.Mt, (g.N, g.Mx, g.My, F * g.Mt), guard)
-
-
-def _w(g, a, guard=False):
-    return _mat(a, g.F, g.Kx * g.Ky * g.C * g.Kt, (g.F, g.Kx, g.Ky, g.C * g.Kt), guard)
 
 
 def _bytes(*ms):
@@ -133,30 +92,31 @@ def _data(g, seed=0):
 @pytest.mark.parametrize("shape,N", CASES, ids=[f"{s}-N{n}" for s, n in CASES])
 def test_conv3d_entries_against_ref_and_2d_loop(matrix_path, shape, N):
     from convnet_amd.matrix import Matrix
+    from hip_adapter import _desc, _w, _x, _y
     g = Geom3D(N=N, **SHAPES[shape])
     x, w, dy = _data(g, seed=N)
     rng = np.random.default_rng(1)
     t_up, t_dn, t_w = (rng.standard_normal(s).astype(np.float32) for s in (g.out_shape(), g.in_shape(), g.filt_shape()))
     ref_up, ref_dn, ref_w = R.conv_up(g, x, w), R.conv_down(g, dy, w), R.conv_outp(g, x, dy, None, 0.0, 0.5)
     d = _desc(g)
-    (X, _), (W, _), (DY, _) = _x(g, x), _w(g, w), _y(g, dy)
+    X, W, DY = _x(g, x), _w(g, w), _y(g, dy)
     before = _bytes(X, W, DY)
     for st in (0.0, 1.0):
         # forward: against the float64 statement, and bit for bit the 2-D loop
-        T1, F1 = _y(g, t_up, guard=True)
+        T1, F1 = _y(g, t_up, guard=GUARDED)
         Matrix.Conv3DUp(X, W, T1, d, st)
         up = T1.ToNumpy().reshape(g.out_shape())
         e = rel_err(up, st * t_up + ref_up)
         print(f"{shape} N={N} {matrix_path} st={st}: up {e:.2e}", end=" ")
         assert e < TOL and _guards_intact(F1, N)
-        T2, _ = _y(g, t_up)
+        T2 = _y(g, t_up)
         _loop_2d(g, X, W, DY, "up", T2, st)
         assert np.array_equal(up, T2.ToNumpy().reshape(g.out_shape())), "forward differs from the loop of 2-D entries"
-        T3, _ = _y(g, t_up)
+        T3 = _y(g, t_up)
         Matrix.Conv3DUp(X, W, T3, d, st)
         assert np.array_equal(up, T3.ToNumpy().reshape(g.out_shape())), "forward is not bit-identical from run to run"
         # dgrad: every input frame written (uncovered ones included), nothing outside the tensor
-        T1, F1 = _x(g, t_dn, guard=True)
+        T1, F1 = _x(g, t_dn, guard=GUARDED)
         Matrix.Conv3DDown(DY, W, T1, d, st)
         dn = T1.ToNumpy().reshape(g.in_shape())
         e = rel_err(dn, st * t_dn + ref_dn)
@@ -165,23 +125,23 @@ def test_conv3d_entries_against_ref_and_2d_loop(matrix_path, shape, N):
         covered = {m * g.st + k for m in range(g.Mt) for k in range(g.Kt)}
         for ti in set(range(g.T)) - covered:
             assert np.array_equal(dn[ti], np.float32(st) * t_dn[ti]), f"uncovered frame {ti}"
-        T2, _ = _x(g, t_dn)
+        T2 = _x(g, t_dn)
         _loop_2d(g, X, W, DY, "down", T2, st)
         assert rel_err(dn, T2.ToNumpy().reshape(g.in_shape())) < TOL
-        T3, _ = _x(g, t_dn)
+        T3 = _x(g, t_dn)
         Matrix.Conv3DDown(DY, W, T3, d, st)
         assert np.array_equal(dn, T3.ToNumpy().reshape(g.in_shape())), "dgrad is not bit-identical from run to run"
         # wgrad
-        T1, F1 = _w(g, t_w, guard=True)
+        T1, F1 = _w(g, t_w, guard=GUARDED)
         Matrix.Conv3DOutp(X, DY, T1, d, st, 0.5)
         dw = T1.ToNumpy().reshape(g.filt_shape())
         e = rel_err(dw, st * t_w + ref_w)
         print(f"outp {e:.2e}")
         assert e < TOL and _guards_intact(F1, g.F)
-        T2, _ = _w(g, t_w)
+        T2 = _w(g, t_w)
         _loop_2d(g, X, W, DY, "outp", T2, st, 0.5)
         assert rel_err(dw, T2.ToNumpy().reshape(g.filt_shape())) < TOL
-        T3, _ = _w(g, t_w)
+        T3 = _w(g, t_w)
         Matrix.Conv3DOutp(X, DY, T3, d, st, 0.5)
         assert np.array_equal(dw, T3.ToNumpy().reshape(g.filt_shape())), "wgrad is not bit-identical from run to run"
     assert _bytes(X, W, DY) == before, "a 3-D entry wrote to its caller's cudamat structs"
@@ -190,6 +150,7 @@ def test_conv3d_entries_against_ref_and_2d_loop(matrix_path, shape, N):
 @pytest.mark.parametrize("shape,N", [("c3_first_layer", 32), ("c16_3x3_rows10", 64), ("c16_5x5_s2_st2", 4), ("f12_st_gt_kt", 128)])
 def test_fused_conv3d_entries_equal_their_unfused_sequences(matrix_path, shape, N):
     from convnet_amd.matrix import Matrix
+    from hip_adapter import _desc, _mat, _w, _x, _y
     g = Geom3D(N=N, **SHAPES[shape])
     x, w, dy = _data(g, seed=7)
     rng = np.random.default_rng(2)
@@ -197,12 +158,12 @@ def test_fused_conv3d_entries_equal_their_unfused_sequences(matrix_path, shape, 
     state = rng.standard_normal(g.in_shape()).astype(np.float32)
     t_dn = rng.standard_normal(g.in_shape()).astype(np.float32)
     d = _desc(g)
-    (X, _), (W, _), (DY, _), (B, _), (S, _) = _x(g, x), _w(g, w), _y(g, dy), _mat(bias, 1, g.F), _x(g, state)
+    X, W, DY, B, S = _x(g, x), _w(g, w), _y(g, dy), _mat(bias, 1, g.F), _x(g, state)
     # convUp3DBiasAct == convUp3DGemm + the shared bias per output frame + ReLU (conv_edge.cc:155-164, layer.cc:549)
     for relu in (0, 1):
-        A, _ = _y(g, np.zeros(g.out_shape()))
+        A = _y(g, np.zeros(g.out_shape()))
         Matrix.Conv3DUpBiasAct(X, W, B, A, d, 0.0, relu)
-        U, _ = _y(g, np.zeros(g.out_shape()))
+        U = _y(g, np.zeros(g.out_shape()))
         Matrix.Conv3DUp(X, W, U, d, 0.0)
         U.Reshape(-1, g.F * g.Mt)
         for m in range(g.Mt):
@@ -213,35 +174,35 @@ def test_fused_conv3d_entries_equal_their_unfused_sequences(matrix_path, shape, 
         if relu:
             U.LowerBound(0.0)
         assert np.array_equal(A.ToNumpy(), U.ToNumpy()), f"convUp3DBiasAct relu={relu}"
-        A2, _ = _y(g, np.zeros(g.out_shape()))
+        A2 = _y(g, np.zeros(g.out_shape()))
         Matrix.Conv3DUpBiasAct(X, W, B, A2, d, 0.0, relu)
         assert np.array_equal(A.ToNumpy(), A2.ToNumpy()), "convUp3DBiasAct is not bit-identical from run to run"
         assert rel_err(A.ToNumpy().reshape(g.out_shape()),
                        (np.maximum if relu else lambda a, b: a)(R.conv_up(g, x, w) + bias.reshape(1, -1, 1, 1, 1), 0.0)) < TOL
     # convDown3DMask == convDown3DGemm + ReLU' of the source layer (layer.cc:556-558), accumulated target included
     for st in (0.0, 1.0):
-        A, FA = _x(g, t_dn, guard=True)
+        A, FA = _x(g, t_dn, guard=GUARDED)
         Matrix.Conv3DDownMask(DY, W, S, A, d, st, 1.0)
-        U, _ = _x(g, t_dn)
+        U = _x(g, t_dn)
         Matrix.Conv3DDown(DY, W, U, d, st)
         U.ApplyDerivativeOfReLU(S)
         assert np.array_equal(A.ToNumpy(), U.ToNumpy()), f"convDown3DMask st={st}"
-        A2, _ = _x(g, t_dn)
+        A2 = _x(g, t_dn)
         Matrix.Conv3DDownMask(DY, W, S, A2, d, st, 1.0)
         assert np.array_equal(A.ToNumpy(), A2.ToNumpy()), "convDown3DMask is not bit-identical from run to run"
         assert _guards_intact(FA, N)
-    A, _ = _x(g, t_dn)
+    A = _x(g, t_dn)
     Matrix.Conv3DDownMask(DY, W, S, A, d, 0.0, 0.5)
     assert rel_err(A.ToNumpy().reshape(g.in_shape()), 0.5 * R.conv_down(g, dy, w) * (state > 0)) < TOL
     # convOutp3DBias: dW as convOutp3DGemm, and the shared-bias gradient summed over images, pixels and frames
     for st in (0.0, 1.0):
         t_w, t_b = rng.standard_normal(g.filt_shape()).astype(np.float32), rng.standard_normal(g.F).astype(np.float32)
-        (A, _), (DB, FDB) = _w(g, t_w), _mat(t_b, 1, g.F, guard=True)
+        A, (DB, FDB) = _w(g, t_w), _mat(t_b, 1, g.F, guard=GUARDED)
         Matrix.Conv3DOutpBias(X, DY, A, DB, d, st, 0.25)
-        U, _ = _w(g, t_w)
+        U = _w(g, t_w)
         Matrix.Conv3DOutp(X, DY, U, d, st, 0.25)
         assert np.array_equal(A.ToNumpy(), U.ToNumpy()), f"convOutp3DBias dW st={st}"
-        (A2, _), (DB2, _) = _w(g, t_w), _mat(t_b, 1, g.F)
+        A2, DB2 = _w(g, t_w), _mat(t_b, 1, g.F)
         Matrix.Conv3DOutpBias(X, DY, A2, DB2, d, st, 0.25)
         assert np.array_equal(A.ToNumpy(), A2.ToNumpy()) and np.array_equal(DB.ToNumpy(), DB2.ToNumpy()), "convOutp3DBias is not bit-identical from run to run"
         assert rel_err(DB.ToNumpy().reshape(-1), st * t_b + 0.25 * dy.astype(np.float64).sum(axis=(0, 2, 3, 4))) < TOL and _guards_intact(FDB, 1)
@@ -254,25 +215,26 @@ def test_fused_bias_gradient_beside_the_batched_dw_slabs(matrix_path, C, F):
     run between the frame launches and the call's one dW reduction, and must not touch the frames' slabs.  dW bit for bit
     convOutp3DGemm's, db against float64."""
     from convnet_amd.matrix import Matrix
+    from hip_adapter import _desc, _mat, _w, _x, _y
     g = Geom3D(N=64, C=C, H=24, W=24, T=4, F=F, Ky=2, Kx=2, Kt=2)
     assert (g.C * g.Kt * g.Ky * g.Kx) % 256 == 0 and g.N * g.My * g.Mx >= 32768 and g.Mt == 3
     x, w, dy = _data(g, seed=C)
     rng = np.random.default_rng(4)
     d = _desc(g)
-    (X, _), (DY, _) = _x(g, x), _y(g, dy)
+    X, DY = _x(g, x), _y(g, dy)
     for st in (0.0, 1.0):
         t_w, t_b = rng.standard_normal(g.filt_shape()).astype(np.float32), rng.standard_normal(g.F).astype(np.float32)
-        (A, FA), (DB, FDB) = _w(g, t_w, guard=True), _mat(t_b, 1, g.F, guard=True)
+        (A, FA), (DB, FDB) = _w(g, t_w, guard=GUARDED), _mat(t_b, 1, g.F, guard=GUARDED)
         Matrix.Conv3DOutpBias(X, DY, A, DB, d, st, 0.25)
-        U, _ = _w(g, t_w)
+        U = _w(g, t_w)
         Matrix.Conv3DOutp(X, DY, U, d, st, 0.25)
         assert np.array_equal(A.ToNumpy(), U.ToNumpy()), f"convOutp3DBias dW differs from convOutp3DGemm's, st={st}"
         e = rel_err(DB.ToNumpy().reshape(-1), st * t_b + 0.25 * dy.astype(np.float64).sum(axis=(0, 2, 3, 4)))
         print(f"C={C} F={F} {matrix_path} st={st}: db {e:.2e}")
         assert e < TOL and _guards_intact(FA, g.F) and _guards_intact(FDB, 1)
         # and dW itself against the loop of 2-D entries (the unbatched form), so that both sides cannot be wrong together
-        L, _ = _w(g, t_w)
-        (W0, _) = _w(g, w)
+        L = _w(g, t_w)
+        W0 = _w(g, w)
         _loop_2d(g, X, W0, DY, "outp", L, st, 0.25)
         assert rel_err(A.ToNumpy(), L.ToNumpy()) < TOL
 
@@ -280,16 +242,17 @@ def test_fused_bias_gradient_beside_the_batched_dw_slabs(matrix_path, C, F):
 @pytest.mark.parametrize("C,size_f,N,T,blocked", [(16, 5, 32, 4, False), (64, 16, 4, 3, False), (96, 24, 64, 2, False), (20, 5, 128, 3, True)])
 def test_rnorm3d_is_the_2d_operation_on_every_frame(gpu, C, size_f, N, T, blocked):
     from convnet_amd.matrix import Matrix
+    from hip_adapter import _mat
     rng = np.random.default_rng(C)
     x, dy = (rng.standard_normal((T, C, 5, 6, N)).astype(np.float32) for _ in range(2))
-    (X, _), (DY, _), (Y, FY), (YR, _), (DX, FDX) = (_mat(a, N, a.size // N, None, gd) for a, gd in
-                                                     ((x, False), (dy, False), (np.zeros_like(x), True), (np.zeros_like(x), False), (np.zeros_like(x), True)))
+    X, DY, (Y, FY), YR, (DX, FDX) = (_mat(a, N, a.size // N, None, gd) for a, gd in
+                                         ((x, (0, 0)), (dy, (0, 0)), (np.zeros_like(x), GUARDED), (np.zeros_like(x), (0, 0)), (np.zeros_like(x), GUARDED)))
     before = _bytes(X, DY)
     Matrix.ConvResponseNormCrossMap3D(X, Y, C, size_f, 0.01, 0.75, blocked, T)
     Matrix.ConvResponseNormCrossMap3D(X, YR, C, size_f, 0.01, 0.75, blocked, T, relu=True)
     Matrix.ConvResponseNormCrossMapUndo3D(DY, X, Y, DX, C, size_f, 0.01, 0.75, blocked, T)
     y, dx = Y.ToNumpy().reshape(x.shape), DX.ToNumpy().reshape(x.shape)
-    (Y2, _), (YR2, _), (DX2, _) = (_mat(np.zeros_like(x), N, x.size // N) for _ in range(3))   # run-to-run bit-identity
+    Y2, YR2, DX2 = (_mat(np.zeros_like(x), N, x.size // N) for _ in range(3))   # run-to-run bit-identity
     Matrix.ConvResponseNormCrossMap3D(X, Y2, C, size_f, 0.01, 0.75, blocked, T)
     Matrix.ConvResponseNormCrossMap3D(X, YR2, C, size_f, 0.01, 0.75, blocked, T, relu=True)
     Matrix.ConvResponseNormCrossMapUndo3D(DY, X, Y2, DX2, C, size_f, 0.01, 0.75, blocked, T)
@@ -301,7 +264,7 @@ def test_rnorm3d_is_the_2d_operation_on_every_frame(gpu, C, size_f, N, T, blocke
     frame = x[0].size // N
     for t in range(T):   # bit for bit the 2-D entries on the frame's slice
         xs, ds = _frames(X, t, 1, frame, (N, 6, 5, C)), _frames(DY, t, 1, frame, (N, 6, 5, C))
-        (y2, _), (d2, _) = _mat(np.zeros_like(x[0]), N, frame), _mat(np.zeros_like(x[0]), N, frame)
+        y2, d2 = _mat(np.zeros_like(x[0]), N, frame), _mat(np.zeros_like(x[0]), N, frame)
         Matrix.ConvResponseNormCrossMap(xs, y2, C, size_f, 0.01, 0.75, blocked)
         Matrix.ConvResponseNormCrossMapUndo(ds, xs, y2, d2, C, size_f, 0.01, 0.75, blocked)
         assert np.array_equal(y2.ToNumpy().reshape(x[0].shape), y[t]) and np.array_equal(d2.ToNumpy().reshape(x[0].shape), dx[t])
@@ -319,32 +282,33 @@ POOLS = [
 @pytest.mark.parametrize("g", POOLS, ids=str)
 def test_pooling_over_time(gpu, g):
     from convnet_amd.matrix import Matrix
+    from hip_adapter import _desc, _mat, _x, _y
     rng = np.random.default_rng(g.N)
     d = _desc(g, pool=True)
     # small integers: many ties, and every sum of routed derivatives is exact in fp32 -> max pooling compares exactly
     x = rng.integers(-4, 5, g.in_shape()).astype(np.float32)
     dy = rng.integers(-4, 5, g.pooled_shape()).astype(np.float32)
     t_in = rng.integers(-4, 5, g.in_shape()).astype(np.float32)
-    (X, _), (DY, _), (Y, FY) = _x(g, x), _y(g, dy, pool=True), _y(g, np.zeros(g.pooled_shape()), guard=True, pool=True)
+    X, DY, (Y, FY) = _x(g, x), _y(g, dy, pool=True), _y(g, np.zeros(g.pooled_shape()), guard=GUARDED, pool=True)
     before = _bytes(X, DY)
     Matrix.ConvMaxPool(X, Y, d)
     y = Y.ToNumpy().reshape(g.pooled_shape())
     assert np.array_equal(y, R.max_pool(g, x)) and _guards_intact(FY, g.N)
     for st in (0.0, 1.0):
-        DX, FDX = _x(g, t_in, guard=True)
+        DX, FDX = _x(g, t_in, guard=GUARDED)
         Matrix.ConvMaxPoolUndo(X, DY, Y, DX, d, st)
         assert np.array_equal(DX.ToNumpy().reshape(g.in_shape()), R.max_pool_undo(g, x, dy, y, t_in, st)) and _guards_intact(FDX, g.N)
-    DX, _ = _x(g, t_in)
+    DX = _x(g, t_in)
     Matrix.ConvMaxPoolUndoRelu(X, DY, Y, DX, d, 0.0)
     assert np.array_equal(DX.ToNumpy().reshape(g.in_shape()), R.max_pool_undo(g, x, dy, y) * (x > 0))
     # averages on real-valued data, against float64
     xr, dyr = rng.standard_normal(g.in_shape()).astype(np.float32), rng.standard_normal(g.pooled_shape()).astype(np.float32)
-    (XR, _), (DYR, _), (YA, FYA) = _x(g, xr), _y(g, dyr, pool=True), _y(g, np.zeros(g.pooled_shape()), guard=True, pool=True)
+    XR, DYR, (YA, FYA) = _x(g, xr), _y(g, dyr, pool=True), _y(g, np.zeros(g.pooled_shape()), guard=GUARDED, pool=True)
     Matrix.ConvAvgPool(XR, YA, d)
     e1 = rel_err(YA.ToNumpy().reshape(g.pooled_shape()), R.avg_pool(g, xr))
     assert e1 < TOL and _guards_intact(FYA, g.N)
     for st in (0.0, 1.0):
-        DX, FDX = _x(g, t_in, guard=True)
+        DX, FDX = _x(g, t_in, guard=GUARDED)
         Matrix.ConvAvgPoolUndo(DYR, DX, d, st)
         e2 = rel_err(DX.ToNumpy().reshape(g.in_shape()), R.avg_pool_undo(g, dyr, t_in, st))
         print(f"{g}: avg fwd {e1:.2e} undo(st={st}) {e2:.2e}")
@@ -353,7 +317,7 @@ def test_pooling_over_time(gpu, g):
     # run-to-run bit-identity of the four kernels, on the real-valued data
     runs = []
     for _ in range(2):
-        (YM, _), (YV, _), (DM, _), (DV, _) = (_y(g, np.zeros(g.pooled_shape()), pool=True), _y(g, np.zeros(g.pooled_shape()), pool=True),
+        YM, YV, DM, DV = (_y(g, np.zeros(g.pooled_shape()), pool=True), _y(g, np.zeros(g.pooled_shape()), pool=True),
                                               _x(g, t_in), _x(g, t_in))
         Matrix.ConvMaxPool(XR, YM, d)
         Matrix.ConvAvgPool(XR, YV, d)
@@ -362,7 +326,7 @@ def test_pooling_over_time(gpu, g):
         runs.append([m.ToNumpy() for m in (YM, YV, DM, DV)])
     assert all(np.array_equal(a, b) for a, b in zip(*runs)), "pooling over time is not bit-identical from run to run"
     # the mask pair is 2-D only: refuses, touches nothing
-    (M, _), (Y2, _) = _mat(np.full(g.N * ((y.size // g.N + 1) // 2), 5.0), g.N, (y.size // g.N + 1) // 2), _y(g, np.full(g.pooled_shape(), 5.0), pool=True)
+    M, Y2 = _mat(np.full(g.N * ((y.size // g.N + 1) // 2), 5.0), g.N, (y.size // g.N + 1) // 2), _y(g, np.full(g.pooled_shape(), 5.0), pool=True)
     assert Matrix.ConvMaxPoolMask(X, Y2, M, d) is False
     assert np.all(Y2.ToNumpy() == 5.0) and np.all(M.ToNumpy() == 5.0)
 
@@ -371,6 +335,7 @@ def test_pooling_over_time(gpu, g):
 def test_frames_behind_a_2d_window_are_channels_bit_for_bit(gpu, N, K, S, pad):
     """T > 1 with kernel_size_t = 1, stride_t = 1, padding_t = 0: today's 2-D call on C*T channels, to the bit (mask pair included)."""
     from convnet_amd.matrix import Matrix
+    from hip_adapter import _desc, _mat, _x, _y
     C, T = 8, 3
     g = Geom3D(N=N, C=C, H=11, W=11, T=T, F=C, Ky=K, Kx=K, Kt=1, sy=S, sx=S, st=1, pady=pad, padx=pad)
     g2 = Geom3D(N=N, C=C * T, H=11, W=11, T=1, F=C * T, Ky=K, Kx=K, Kt=1, sy=S, sx=S, st=1, pady=pad, padx=pad)
@@ -379,19 +344,19 @@ def test_frames_behind_a_2d_window_are_channels_bit_for_bit(gpu, N, K, S, pad):
     out = {}
     for key, gg in (("frames", g), ("channels", g2)):
         d = _desc(gg, pool=True)
-        (X, _), (DY, _) = _x(g, x), _y(g, dy, pool=True)
+        X, DY = _x(g, x), _y(g, dy, pool=True)
         res = []
         for fwd, undo in ((Matrix.ConvMaxPool, "max"), (Matrix.ConvAvgPool, "avg")):
-            Y, _ = _y(g, np.zeros(g.pooled_shape()), pool=True)
+            Y = _y(g, np.zeros(g.pooled_shape()), pool=True)
             fwd(X, Y, d)
-            DX, _ = _x(g, np.zeros(g.in_shape()))
+            DX = _x(g, np.zeros(g.in_shape()))
             if undo == "max":
                 Matrix.ConvMaxPoolUndo(X, DY, Y, DX, d, 0.0)
             else:
                 Matrix.ConvAvgPoolUndo(DY, DX, d, 0.0)
             res += [Y.ToNumpy(), DX.ToNumpy()]
-        Y, _ = _y(g, np.zeros(g.pooled_shape()), pool=True)
-        M, _ = _mat(np.zeros(N * ((Y.GetCols() + 1) // 2)), N, (Y.GetCols() + 1) // 2)
+        Y = _y(g, np.zeros(g.pooled_shape()), pool=True)
+        M = _mat(np.zeros(N * ((Y.GetCols() + 1) // 2)), N, (Y.GetCols() + 1) // 2)
         ok = Matrix.ConvMaxPoolMask(X, Y, M, d)
         res += [np.asarray(ok), Y.ToNumpy() if ok else None, M.ToNumpy() if ok else None]
         out[key] = res

@@ -31,45 +31,10 @@ def matrix_path(request, gpu):
     _lib.lib.convnet_hip_set_matrix_path(1)
 
 
-def _mat(arr, rows, cols, shape4=None):
-    from convnet_amd.matrix import Matrix
-    m = Matrix()
-    m.AllocateGPUMemory(rows, cols)
-    m.FromNumpy(np.ascontiguousarray(arr, np.float32).reshape(-1))
-    if shape4:
-        m.SetShape4D(*shape4)
-    return m
-
-
-def _desc(g):
-    from convnet_amd.matrix import make_conv_desc
-    return make_conv_desc(g.C, g.F, g.Ky, g.Kx, g.sy, g.sx, g.pady, g.padx)
-
-
-def _x(g, a):
-    return _mat(a, g.N, g.H * g.W * g.C, (g.N, g.W, g.H, g.C))
-
-
-def _y(g, a):
-    return _mat(a, g.N, g.M * g.F, (g.N, g.Mx, g.My, g.F))
-
-
-def _w(g, a, extra=0):
-    """the bank, optionally followed by `extra` guard floats in the same allocation (the matrix handed to the kernel is a view)"""
-    from convnet_amd.matrix import Matrix
-    full = _mat(np.concatenate([np.asarray(a, np.float32).reshape(-1), np.full(extra * g.F, 7.0, np.float32)]), g.F, g.K * g.M + extra)
-    if not extra:
-        full.SetShape4D(g.F, g.Kx, g.Ky, g.C * g.M)
-        return full, full
-    v = Matrix()
-    full.GetSlice(v, 0, g.K * g.M)
-    v.SetShape4D(g.F, g.Kx, g.Ky, g.C * g.M)
-    return v, full
-
-
 def run_up(g, x, w, t=None, st=0.0, name="localUpGemm"):
     from convnet_amd._lib import lib
-    X, (W, _), T = _x(g, x), _w(g, w), _y(g, t if t is not None else np.zeros(g.out_shape()))
+    from hip_adapter import _desc, _w_local, _x, _y
+    X, W, T = _x(g, x), _w_local(g, w), _y(g, t if t is not None else np.zeros(g.out_shape()))
     getattr(lib, name)(X.GetMat(), W.GetMat(), T.GetMat(), ctypes.byref(X.shape_), ctypes.byref(W.shape_), ctypes.byref(T.shape_),
                        _desc(g), float(st))
     return T.ToNumpy().reshape(g.out_shape())
@@ -77,16 +42,20 @@ def run_up(g, x, w, t=None, st=0.0, name="localUpGemm"):
 
 def run_down(g, dy, w, t=None, st=0.0, name="localDownGemm"):
     from convnet_amd._lib import lib
-    D, (W, _), T = _y(g, dy), _w(g, w), _x(g, t if t is not None else np.zeros(g.in_shape()))
+    from hip_adapter import _desc, _w_local, _x, _y
+    D, W, T = _y(g, dy), _w_local(g, w), _x(g, t if t is not None else np.zeros(g.in_shape()))
     getattr(lib, name)(D.GetMat(), W.GetMat(), T.GetMat(), ctypes.byref(D.shape_), ctypes.byref(W.shape_), ctypes.byref(T.shape_),
                        _desc(g), float(st))
     return T.ToNumpy().reshape(g.in_shape())
 
 
 def run_outp(g, x, dy, t=None, st=0.0, so=1.0, name="localOutpGemm", guard=0):
+    """guard: that many columns of guard floats follow the bank gradient in its allocation (the matrix handed to the kernel is a view)"""
     from convnet_amd._lib import lib
+    from hip_adapter import _desc, _w_local, _x, _y
     X, D = _x(g, x), _y(g, dy)
-    T, full = _w(g, t if t is not None else np.zeros(g.bank_shape()), extra=guard)
+    bank = _w_local(g, t if t is not None else np.zeros(g.bank_shape()), (0, guard))
+    T, full = bank if guard else (bank, bank)
     getattr(lib, name)(X.GetMat(), D.GetMat(), T.GetMat(), ctypes.byref(X.shape_), ctypes.byref(D.shape_), ctypes.byref(T.shape_),
                        _desc(g), float(st), float(so))
     a = full.ToNumpy().reshape(-1)
@@ -170,10 +139,11 @@ def test_face_net_scale_layer_on_sampled_elements(matrix_path):
 @pytest.mark.parametrize("g", [GEOMS[1], GEOMS[4]], ids=str)
 def test_fused_bias_relu_is_bit_identical_to_the_unfused_sequence(matrix_path, g):
     from convnet_amd.matrix import Matrix
+    from hip_adapter import _desc, _mat, _w_local, _x, _y
     rng = np.random.default_rng(4)
     x, w, b, t = rnd(rng, g.in_shape()), rnd(rng, g.bank_shape()), rnd(rng, (1, g.F * g.M)), rnd(rng, g.out_shape())
     for st, relu in ((0.0, True), (1.0, True), (0.0, False)):
-        X, (W, _), B = _x(g, x), _w(g, w), _mat(b, 1, g.F * g.M)
+        X, W, B = _x(g, x), _w_local(g, w), _mat(b, 1, g.F * g.M)
         T1, T2 = _y(g, t), _y(g, t)
         Matrix.LocalUp(X, W, T1, _desc(g), st)
         T1.AddRowVec(B)
@@ -187,7 +157,7 @@ def test_fused_bias_relu_is_bit_identical_to_the_unfused_sequence(matrix_path, g
         assert np.array_equal(T3.ToNumpy(), a2)                      # repeated calls: bit-identical
     # the bias mapping of local_edge.cc: element j of the (1, F*M) row goes to output column j
     ref = L.up(g, x, w) + b.reshape(g.F, g.My, g.Mx)[..., None]
-    X, (W, _), B, T = _x(g, x), _w(g, w), _mat(b, 1, g.F * g.M), _y(g, np.zeros(g.out_shape()))
+    X, W, B, T = _x(g, x), _w_local(g, w), _mat(b, 1, g.F * g.M), _y(g, np.zeros(g.out_shape()))
     Matrix.LocalUpBiasAct(X, W, B, T, _desc(g), 0.0, False)
     assert rel_err(T.ToNumpy().reshape(g.out_shape()), ref) < 1e-4
 

@@ -26,19 +26,13 @@ def _n(size):
     return 1027 if size == "off4" else size
 
 
-def _mat(M, a, size=None):
+def _mat(a, size=None):
     """A (1, n) device matrix holding `a`; size "off4": a view one float into a flat buffer."""
+    from hip_adapter import _mat as device_mat
     a = np.asarray(a, np.float32).reshape(-1)
     if size != "off4":
-        m = M()
-        m.AllocateGPUMemory(1, a.size)
-        m.FromNumpy(a)
-        return m
-    flat, m = M(), M()
-    flat.AllocateGPUMemory(1, a.size + 1)
-    flat.FromNumpy(np.concatenate([[0], a]))
-    flat.GetSlice(m, 1, a.size + 1)
-    m._keep = flat
+        return device_mat(a, 1, a.size)
+    m, _ = device_mat(a, 1, a.size, guard=(1, 0))   # the view keeps the buffer alive: Matrix.GetSlice stores a torch slice of its storage
     assert m.mat_.data_device % 16 == 4
     return m
 
@@ -98,13 +92,13 @@ def np_rmsprop_step(g, w, h, a, factor, l2, clip, eps, mom):
 @pytest.mark.parametrize("size", SIZES)
 def test_reference_entries_equal_the_numpy_restatement(M, size):
     g, w, _, a = _data(size)
-    A, G = _mat(M, a, size), _mat(M, g, size)
+    A, G = _mat(a, size), _mat(g, size)
     M.AdagradUpdate(A, G, 0.1)
     assert np.array_equal(A.ToNumpy().reshape(-1), np_adagrad(a, g, 0.1))
-    A = _mat(M, a, size)
+    A = _mat(a, size)
     M.RMSPropUpdate(A, G, 0.9)
     assert np.array_equal(A.ToNumpy().reshape(-1), np_rms_prop(a, g, 0.9))
-    W = _mat(M, w, size)
+    W = _mat(w, size)
     W.Divide(A)
     assert np.array_equal(W.ToNumpy().reshape(-1), w / np_rms_prop(a, g, 0.9))
     assert np.array_equal(G.ToNumpy().reshape(-1), g)
@@ -112,8 +106,8 @@ def test_reference_entries_equal_the_numpy_restatement(M, size):
 
 def test_reference_entries_return_cudamat_error_codes(M):
     from convnet_amd._lib import lib
-    a, b, short = _mat(M, np.ones(12)), _mat(M, np.ones(12)), _mat(M, np.ones(11))
-    t = _mat(M, np.ones(12))
+    a, b, short = _mat(np.ones(12)), _mat(np.ones(12)), _mat(np.ones(11))
+    t = _mat(np.ones(12))
     t.mat_.is_trans = 1
     for fn, args in ((lib.adagrad, (0.5,)), (lib.rms_prop, (0.5,))):
         assert fn(a.GetMat(), short.GetMat(), *args) == -1          # ERROR_INCOMPATIBLE_DIMENSIONS
@@ -179,7 +173,7 @@ def test_fused_step_equals_the_numpy_restatement(M, kind, corner):
     l2, clip, mom = CORNERS[corner]
     for size in SIZES:
         arrays = _data(size, 1)
-        mats = [_mat(M, x, size) for x in arrays]
+        mats = [_mat(x, size) for x in arrays]
         _fused(M, kind, mats, HYPER[kind], l2, clip, 0.05, mom)
         want = _restated(kind, arrays, HYPER[kind], l2, clip, 0.05, mom)
         for what, m, v in zip(("gradient", "parameter", "history", "second history"), mats, want):
@@ -198,7 +192,7 @@ def test_fused_step_equals_the_unfused_sequence_of_library_entries(M, kind, corn
     unequal = []
     for size in SIZES:
         arrays = _data(size, 2)
-        a, b = [_mat(M, x, size) for x in arrays], [_mat(M, x, size) for x in arrays]
+        a, b = [_mat(x, size) for x in arrays], [_mat(x, size) for x in arrays]
         _fused(M, kind, a, HYPER[kind], l2, clip, 0.05, mom)
         _unfused(M, kind, b, HYPER[kind], l2, clip, 0.05, mom)
         for what, x, y in zip(("gradient", "parameter", "history", "second history"), a, b):
@@ -222,7 +216,7 @@ def test_multi_step_equals_single_steps_and_repeats_itself(M, kind):
         hypers.append((*first, l2 * (1 + i), clip * (1 + 0.1 * i), 0.01 * (1 + i), mom * rng.random()))
     runs = []
     for mode in ("single", "multi", "multi"):
-        items = [tuple(_mat(M, x, s) for x in _data(s, 3 + i)) + hypers[i] for i, s in enumerate(sizes)]
+        items = [tuple(_mat(x, s) for x in _data(s, 3 + i)) + hypers[i] for i, s in enumerate(sizes)]
         if mode == "single":
             for it in items:
                 _fused(M, kind, it[:4], it[4:-4], *it[-4:])

@@ -27,14 +27,14 @@ def hip():
 def _run(g, x, dy, t0, st, relu):
     """(y, dx) by the mask pair and by the classic pair on the same device tensors"""
     from convnet_amd.matrix import Matrix
-    from hip_adapter import _mat, _desc
+    from hip_adapter import _desc, _x, _y
     d = _desc(g, True)
-    xm = _mat(x, g.N, g.W * g.H * g.C, (g.N, g.W, g.H, g.C))
-    dym = _mat(dy, g.N, g.Mx * g.My * g.C, (g.N, g.Mx, g.My, g.C))
+    xm = _x(g, x)
+    dym = _y(g, dy, pool=True)
     out = []
     for masked in (True, False):
-        ym = _mat(np.zeros(g.pooled_shape(), np.float32), g.N, g.Mx * g.My * g.C, (g.N, g.Mx, g.My, g.C))
-        tm = _mat(t0.copy(), g.N, g.W * g.H * g.C, (g.N, g.W, g.H, g.C))
+        ym = _y(g, np.zeros(g.pooled_shape(), np.float32), pool=True)
+        tm = _x(g, t0.copy())
         if masked:
             mk = Matrix()
             mk.AllocateGPUMemory(g.N, (g.Mx * g.My * g.C + 1) // 2)
@@ -82,11 +82,11 @@ def test_mask_pair_equals_classic_pair_and_oracle(hip, g, ties):
 
 def test_geometries_without_a_mask_kernel_are_refused(hip):
     from convnet_amd.matrix import Matrix
-    from hip_adapter import _mat, _desc
+    from hip_adapter import _desc, _x, _y
     for g in (Geom(N=8, C=2, H=8, W=8, F=2, Ky=2, Kx=2, sy=2, sx=2),                   # 2 x 2 windows
               Geom(N=6, C=2, H=9, W=9, F=2, Ky=3, Kx=3, sy=2, sx=2, pady=1, padx=1)):  # N % 4 != 0
-        xm = _mat(np.zeros(g.in_shape(), np.float32), g.N, g.W * g.H * g.C, (g.N, g.W, g.H, g.C))
-        ym = _mat(np.full(g.pooled_shape(), 7.0, np.float32), g.N, g.Mx * g.My * g.C, (g.N, g.Mx, g.My, g.C))
+        xm = _x(g, np.zeros(g.in_shape(), np.float32))
+        ym = _y(g, np.full(g.pooled_shape(), 7.0, np.float32), pool=True)
         mk = Matrix()
         mk.AllocateGPUMemory(g.N, (g.Mx * g.My * g.C + 1) // 2)
         assert not Matrix.ConvMaxPoolMask(xm, ym, mk, _desc(g, True))
@@ -100,7 +100,7 @@ def test_maxpool_edge_uses_the_mask_only_for_its_own_forward_pass(hip):
     from convnet_amd.convnet import ConvNet
     from convnet_amd.edge import MaxPoolEdge
     from convnet_amd.matrix import Matrix
-    from hip_adapter import _mat
+    from hip_adapter import _x, _y
     net = ConvNet(pbtxt.parse(models.alexnet(image_size=64)), fused=True)
     e = next(x for x in net.edges_ if isinstance(x, MaxPoolEdge))
     assert e.fused
@@ -108,10 +108,10 @@ def test_maxpool_edge_uses_the_mask_only_for_its_own_forward_pass(hip):
     rng = np.random.default_rng(62)
     x = np.maximum(rng.standard_normal(g.in_shape()), 0).astype(np.float32)   # a ReLU layer's state
     dy = rng.standard_normal(g.pooled_shape()).astype(np.float32)
-    xm = _mat(x, g.N, g.W * g.H * g.C, (g.N, g.W, g.H, g.C))
-    ym = _mat(np.zeros(g.pooled_shape(), np.float32), g.N, g.Mx * g.My * g.C, (g.N, g.Mx, g.My, g.C))
-    dym = _mat(dy, g.N, g.Mx * g.My * g.C, (g.N, g.Mx, g.My, g.C))
-    dxm = _mat(np.zeros(g.in_shape(), np.float32), g.N, g.W * g.H * g.C, (g.N, g.W, g.H, g.C))
+    xm = _x(g, x)
+    ym = _y(g, np.zeros(g.pooled_shape(), np.float32), pool=True)
+    dym = _y(g, dy, pool=True)
+    dxm = _x(g, np.zeros(g.in_shape(), np.float32))
     y = oracle.port.max_pool(g, x)
     want = oracle.port.max_pool_undo(g, x, dy, y) * (x > 0)
     _lib.profile_enable(True)
@@ -122,7 +122,7 @@ def test_maxpool_edge_uses_the_mask_only_for_its_own_forward_pass(hip):
     assert "pool_fwd_mask_kernel<max>" in names and "pool_undo_mask_kernel<max>" in names, names
     assert np.array_equal(ym.ToNumpy().reshape(g.pooled_shape()), y) and rel_err(dxm.ToNumpy().reshape(g.in_shape()), want) < 1e-6
     masked = dxm.ToNumpy().copy()
-    x2 = _mat(x, g.N, g.W * g.H * g.C, (g.N, g.W, g.H, g.C))   # the same values in another matrix: not what the mask was written for
+    x2 = _x(g, x)   # the same values in another matrix: not what the mask was written for
     _lib.profile_enable(True)
     e.ComputeDown(dym, x2, ym, dxm, True, fuse_mask=1.0)
     names = [r["kernel"] for r in _lib.profile_report()]

@@ -633,10 +633,11 @@ def _local_case(case, kind, rng):
             if bias is None:
                 return TL.run_up(g, x, w, t0, case.st, "localUp")
             from convnet_amd._lib import lib
+            from hip_adapter import _desc, _mat, _w_local, _x, _y
             import ctypes
-            X, (Wm, _), T = TL._x(g, x), TL._w(g, w), TL._y(g, t0 if t0 is not None else np.zeros(g.out_shape()))
-            lib.localUpBiasAct(X.GetMat(), Wm.GetMat(), TL._mat(bias, 1, F * g.M).GetMat(), T.GetMat(), ctypes.byref(X.shape_),
-                               ctypes.byref(Wm.shape_), ctypes.byref(T.shape_), TL._desc(g), float(case.st), int(case.relu))
+            X, Wm, T = _x(g, x), _w_local(g, w), _y(g, t0 if t0 is not None else np.zeros(g.out_shape()))
+            lib.localUpBiasAct(X.GetMat(), Wm.GetMat(), _mat(bias, 1, F * g.M).GetMat(), T.GetMat(), ctypes.byref(X.shape_),
+                               ctypes.byref(Wm.shape_), ctypes.byref(T.shape_), _desc(g), float(case.st), int(case.relu))
             return T.ToNumpy().reshape(g.out_shape())
         exact, mag = L.torch_up(g, x, w), L.torch_up(g, np.abs(x), np.abs(w))
         extra = {"t0": t0, "bias": None if bias is None else bias[..., None]}

@@ -71,15 +71,16 @@ def leg(which, reps):
     from conv3d_ref import Geom3D
     from convnet_amd import _lib
     from convnet_amd.matrix import Matrix
-    from test_conv3d_gpu import _desc, _loop_2d, _w, _x, _y
+    from hip_adapter import _desc, _w, _x, _y
+    from test_conv3d_gpu import _loop_2d
     _setup()
     out = {}
     rng = np.random.default_rng(0)
     for name, kw in GEOMS.items():
         g = Geom3D(**kw)
-        (X, _), (W, _), (DY, _) = (_x(g, rng.standard_normal(g.in_shape(), np.float32)), _w(g, rng.standard_normal(g.filt_shape(), np.float32)),
+        X, W, DY = (_x(g, rng.standard_normal(g.in_shape(), np.float32)), _w(g, rng.standard_normal(g.filt_shape(), np.float32)),
                                    _y(g, rng.standard_normal(g.out_shape(), np.float32)))
-        (T, _), (DX, _), (DW, _) = _y(g, np.zeros(g.out_shape(), np.float32)), _x(g, np.zeros(g.in_shape(), np.float32)), _w(g, np.zeros(g.filt_shape(), np.float32))
+        T, DX, DW = _y(g, np.zeros(g.out_shape(), np.float32)), _x(g, np.zeros(g.in_shape(), np.float32)), _w(g, np.zeros(g.filt_shape(), np.float32))
         d = _desc(g)
         if which == "entry":
             calls = {"fprop": lambda: Matrix.Conv3DUp(X, W, T, d, 0.0), "dgrad": lambda: Matrix.Conv3DDown(DY, W, DX, d, 0.0),
@@ -102,14 +103,14 @@ def leg(which, reps):
 def pools(reps):
     from conv3d_ref import Geom3D
     from convnet_amd.matrix import Matrix
-    from test_conv3d_gpu import _desc, _x, _y
+    from hip_adapter import _desc, _x, _y
     rng = np.random.default_rng(1)
     out = {}
     for name, kw in POOLS.items():
         g = Geom3D(**kw)
         d = _desc(g, pool=True)
-        (X, _), (DY, _) = _x(g, rng.standard_normal(g.in_shape(), np.float32)), _y(g, rng.standard_normal(g.pooled_shape(), np.float32), pool=True)
-        (Y, _), (DX, _) = _y(g, np.zeros(g.pooled_shape(), np.float32), pool=True), _x(g, np.zeros(g.in_shape(), np.float32))
+        X, DY = _x(g, rng.standard_normal(g.in_shape(), np.float32)), _y(g, rng.standard_normal(g.pooled_shape(), np.float32), pool=True)
+        Y, DX = _y(g, np.zeros(g.pooled_shape(), np.float32), pool=True), _x(g, np.zeros(g.in_shape(), np.float32))
         Matrix.ConvMaxPool(X, Y, d)
         a, p = 4.0 * X.GetNumEls(), 4.0 * Y.GetNumEls()
         calls = {"max_fwd": (lambda: Matrix.ConvMaxPool(X, Y, d), a + p), "avg_fwd": (lambda: Matrix.ConvAvgPool(X, Y, d), a + p),

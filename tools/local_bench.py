@@ -55,14 +55,14 @@ def bench_geometry(g, reps):
     import torch
     import torch.nn.functional as Fn
     from convnet_amd import _lib
-    from test_local_gpu import _desc, _w, _x, _y
+    from hip_adapter import _desc, _w_local, _x, _y
     lib = _lib.lib
     rng = np.random.default_rng(0)
     x = rng.standard_normal(g.in_shape()).astype(np.float32)
     w = rng.standard_normal(g.bank_shape()).astype(np.float32)
     dy = rng.standard_normal(g.out_shape()).astype(np.float32)
-    X, (W, _), D = _x(g, x), _w(g, w), _y(g, dy)
-    T, DX, (DW, _) = _y(g, np.zeros(g.out_shape())), _x(g, np.zeros(g.in_shape())), _w(g, np.zeros(g.bank_shape()))
+    X, W, D = _x(g, x), _w_local(g, w), _y(g, dy)
+    T, DX, DW = _y(g, np.zeros(g.out_shape())), _x(g, np.zeros(g.in_shape())), _w_local(g, np.zeros(g.bank_shape()))
     d = _desc(g)
     b = ctypes.byref
     calls = {
