@@ -493,6 +493,19 @@ __device__ __forceinline__ void win_bwd(int j, int C, int sizeF, bool blocked, i
   start = max(0, start);
 }
 
+// x * x rounded on its own.  Contracted into the add (an fma), a slide would add x*x unrounded and later subtract it unrounded from a
+// sum that was rounded in between: the window sum keeps that rounding error of every square that has passed through it, which the
+// oracle's separately rounded product does not (it subtracts exactly what it added).  At sizeF == 1, where the oracle's sum - x*x is
+// exactly 0, a channel of magnitude 2^-6 behind one of 2^6 came out 440 units of 2^-24 off (tests/test_pool_norm_gpu.py).
+__device__ __forceinline__ float sq_rn(float v) {
+#pragma clang fp contract(off)
+  return v * v;
+}
+__device__ __forceinline__ f32x4 sq_rn(f32x4 v) {
+#pragma clang fp contract(off)
+  return v * v;
+}
+
 __global__ void rnorm_fwd_kernel(const float* __restrict__ in, float* __restrict__ out, size_t locs, int C, int sizeF, float addScale,
                                  float powScale, bool blocked, bool vec, int cseg, int nseg, bool relu) {
   const size_t nq = (locs + 3) >> 2;
@@ -513,11 +526,11 @@ __global__ void rnorm_fwd_kernel(const float* __restrict__ in, float* __restrict
       win_fwd(j, C, sizeF, blocked, s, e);
       for (int i = ps; i < s; ++i) {
         const f32x4 v = ldv(in + (size_t)i * locs + l, 0, rem, vec);
-        sum = sum - v * v;
+        sum = sum - sq_rn(v);
       }
       for (int i = pe; i < e; ++i) {
         const f32x4 v = ldv(in + (size_t)i * locs + l, 0, rem, vec);
-        sum = sum + v * v;
+        sum = sum + sq_rn(v);
       }
       const f32x4 x = ldv(in + (size_t)j * locs + l, 0, rem, vec);
       f32x4 y;
@@ -555,11 +568,11 @@ __global__ void rnorm_undo1_kernel(const float* __restrict__ dout, const float* 
       win_fwd(j, C, sizeF, blocked, s, e);
       for (int i = ps; i < s; ++i) {
         const f32x4 v = ldv(in + (size_t)i * locs + l, 0, rem, vec);
-        sum = sum - v * v;
+        sum = sum - sq_rn(v);
       }
       for (int i = pe; i < e; ++i) {
         const f32x4 v = ldv(in + (size_t)i * locs + l, 0, rem, vec);
-        sum = sum + v * v;
+        sum = sum + sq_rn(v);
       }
       const f32x4 x = ldv(in + (size_t)j * locs + l, 0, rem, vec);
       const f32x4 d = ldv(dout + (size_t)j * locs + l, 0, rem, vec);
@@ -641,8 +654,10 @@ __device__ __forceinline__ long rn_tile(unsigned tiles, bool xcd) {
   return L < tiles ? (long)L : -1;
 }
 
+// (`in` / `out`, and `dout` / `out` of the undo, carry no __restrict__: include/convnet_hip.h allows targets == images and
+// targets == outGrads.  A block stages every channel of its tile before the barrier and writes only behind it; tiles are block-private.)
 template <int LT>
-__global__ void rnorm_fwd_lds_kernel(const float* __restrict__ in, float* __restrict__ out, size_t locs, int C, int sizeF, float addScale,
+__global__ void rnorm_fwd_lds_kernel(const float* in, float* out, size_t locs, int C, int sizeF, float addScale,
                                      float powScale, bool blocked, bool vec, bool relu, unsigned tiles, bool xcd) {
   extern __shared__ __attribute__((aligned(16))) float rn_smem[];
   float* xs = rn_smem;   // [C][LT]
@@ -664,8 +679,8 @@ __global__ void rnorm_fwd_lds_kernel(const float* __restrict__ in, float* __rest
   for (int j = j0; j < j1; ++j) {
     int s, e;
     win_fwd(j, C, sizeF, blocked, s, e);
-    for (int i = ps; i < s; ++i) { const float v = xs[i * LT + l]; sum -= v * v; }
-    for (int i = pe; i < e; ++i) { const float v = xs[i * LT + l]; sum += v * v; }
+    for (int i = ps; i < s; ++i) { const float v = xs[i * LT + l]; sum -= sq_rn(v); }
+    for (int i = pe; i < e; ++i) { const float v = xs[i * LT + l]; sum += sq_rn(v); }
     // u^(-b) = exp2(-b * log2(u)), u >= 1: two quarter-rate transcendentals instead of ~100 VALU of powf
     // (the reference's own GPU path uses __powf, cudamat_conv_gemm.cu:458); relative error ~1e-6.
     const float y = xs[j * LT + l] * exp2f(-powScale * __log2f(1.f + addScale * sum));
@@ -676,7 +691,7 @@ __global__ void rnorm_fwd_lds_kernel(const float* __restrict__ in, float* __rest
 }
 
 template <int LT>
-__global__ void __launch_bounds__(512) rnorm_undo_lds_kernel(const float* __restrict__ dout, const float* __restrict__ in, float* __restrict__ out, size_t locs, int C,
+__global__ void __launch_bounds__(512) rnorm_undo_lds_kernel(const float* dout, const float* __restrict__ in, float* out, size_t locs, int C,
                                       int sizeF, float addScale, float powScale, bool blocked, bool vec, unsigned tiles, bool xcd) {
   extern __shared__ __attribute__((aligned(16))) float rn_smem[];
   float* xs = rn_smem;            // [C][LT] inputs
@@ -702,8 +717,8 @@ __global__ void __launch_bounds__(512) rnorm_undo_lds_kernel(const float* __rest
     for (int j = j0; j < j1; ++j) {
       int s, e;
       win_fwd(j, C, sizeF, blocked, s, e);
-      for (int i = ps; i < s; ++i) { const float v = xs[i * LT + l]; sum -= v * v; }
-      for (int i = pe; i < e; ++i) { const float v = xs[i * LT + l]; sum += v * v; }
+      for (int i = ps; i < s; ++i) { const float v = xs[i * LT + l]; sum -= sq_rn(v); }
+      for (int i = pe; i < e; ++i) { const float v = xs[i * LT + l]; sum += sq_rn(v); }
       const float lg = __log2f(1.f + addScale * sum);
       const float den = exp2f((-powScale - 1.f) * lg);          // (1 + a*S)^(-b-1)
       const float d = ds[j * LT + l];
@@ -820,6 +835,12 @@ struct RnSeg {
   static_assert(SZ % 2 == 0 && CG % SS == 0 && H % SS == 0, "the first window is a whole number of sub-segments on either side");
 };
 
+// In place (targets == images forward, targets == outGrads undo; include/convnet_hip.h) is relied on although the pointers are
+// __restrict__: a tile belongs to one block; every load of it through `in` / `dout` (rn_fetch) is consumed into LDS (rn_put) in front of
+// a __syncthreads(), and its only stores through `out` (rn_copy_out) come behind later barriers; the prefetch in between reads ANOTHER
+// tile.  No access through one pointer can therefore be moved across one through the other to the same address.  The qualifiers
+// stay because these are the benchmark's kernels and their schedule was tuned with them (tests/test_pool_norm_gpu.py holds the in-place
+// results bit-identical to out of place).
 template <int LT, int CG, int SZ>
 __global__ void __launch_bounds__(512) rnorm_fwd_fast_kernel(const float* __restrict__ in, float* __restrict__ out, size_t locs, int C, float addScale,
                                                              float powScale, bool relu, unsigned tiles) {
@@ -1479,6 +1500,8 @@ static void rnorm_fwd_impl(cudamat* images, cudamat* targets, int numFilters, in
       return;
     }
   }
+  // the walker below subtracts channels it has already written and reads other segments' channels while they are written
+  CHIP_REQUIRE(images->data_device != targets->data_device);   // in place: numFilters <= 768 only (include/convnet_hip.h)
   int cseg, nseg;
   rnorm_segments((locs + 3) / 4, numFilters, sizeF, cseg, nseg);
   hipLaunchKernelGGL(rnorm_fwd_kernel, dim3(grid_for((locs + 3) / 4 * nseg)), dim3(256), 0, stream(), images->data_device, targets->data_device, locs,

@@ -358,7 +358,12 @@ void MaxPoolUndo(cudamat* images, cudamat* maxGrads, cudamat* maxActs,
 void AvgPoolUndo(cudamat* avgGrads, cudamat* targets, Shape4D* avgGrads_shape,
                  Shape4D* targets_shape, ConvDesc conv_desc, float scaleTargets);
 
-/* ---- cross-map response normalisation: cudamat_conv_gemm.cuh:100-106, cudamat_conv.cuh:35-42 --------- */
+/* ---- cross-map response normalisation: cudamat_conv_gemm.cuh:100-106, cudamat_conv.cuh:35-42 ---------
+ * In place: targets == images (forward, also ...Relu) is allowed for numFilters <= 768 only — above that the kernel walks the
+ * channels in global memory and subtracts from its window sum channels it has already overwritten: the call prints
+ * "check failed: ..." and aborts, as for convUpGemm;
+ * targets == outGrads (undo) is allowed for every channel count (outGrads has been consumed before the first element is written).
+ * targets == inputs is never allowed in the undo. */
 void ResponseNormCrossMapGemm(cudamat* images, cudamat* targets, int numFilters, int sizeF,
                               float addScale, float powScale, bool blocked);
 void ResponseNormCrossMapUndoGemm(cudamat* outGrads, cudamat* inputs, cudamat* targets,

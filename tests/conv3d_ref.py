@@ -97,7 +97,7 @@ def conv_outp(g, x, dy, targets=None, scale_targets=0.0, scale_output=1.0):
     return dw if targets is None else scale_targets * _f64(targets) + dw
 
 
-def _boxes(g):
+def boxes(g):
     """(mt, my, mx) and the CLIPPED input box of every pooling window."""
     for mt in range(g.Mt):
         t0, t1 = max(0, mt * g.st - g.padt), min(g.T, mt * g.st - g.padt + g.Kt)
@@ -115,7 +115,7 @@ def _bc(v):
 def max_pool(g, x):
     x = _f64(x)
     out = np.zeros(g.pooled_shape())
-    for (mt, my, mx), b in _boxes(g):
+    for (mt, my, mx), b in boxes(g):
         out[mt, :, my, mx, :] = x[b].max(axis=(0, 2, 3))
     return out
 
@@ -123,7 +123,7 @@ def max_pool(g, x):
 def avg_pool(g, x):
     x = _f64(x)
     out = np.zeros(g.pooled_shape())
-    for (mt, my, mx), b in _boxes(g):
+    for (mt, my, mx), b in boxes(g):
         out[mt, :, my, mx, :] = x[b].mean(axis=(0, 2, 3))     # divides by the clipped box
     return out
 
@@ -132,7 +132,7 @@ def max_pool_undo(g, x, dy, y, targets=None, scale_targets=0.0):
     """Every input of a box that equals the box's recorded maximum receives the box's derivative (all ties); boxes add."""
     x, dy, y = _f64(x), _f64(dy), _f64(y)
     dx = np.zeros(g.in_shape())
-    for (mt, my, mx), b in _boxes(g):
+    for (mt, my, mx), b in boxes(g):
         dx[b] += (x[b] == _bc(y[mt, :, my, mx, :])) * _bc(dy[mt, :, my, mx, :])
     return dx if targets is None else scale_targets * _f64(targets) + dx
 
@@ -140,13 +140,13 @@ def max_pool_undo(g, x, dy, y, targets=None, scale_targets=0.0):
 def avg_pool_undo(g, dy, targets=None, scale_targets=0.0):
     dy = _f64(dy)
     dx = np.zeros(g.in_shape())
-    for (mt, my, mx), b in _boxes(g):
+    for (mt, my, mx), b in boxes(g):
         size = (b[0].stop - b[0].start) * (b[2].stop - b[2].start) * (b[3].stop - b[3].start)
         dx[b] += _bc(dy[mt, :, my, mx, :] / size)
     return dx if targets is None else scale_targets * _f64(targets) + dx
 
 
-def _rnorm_windows(C, size_f, blocked):
+def rnorm_windows(C, size_f, blocked):
     """M[j, i] = 1 when channel i lies in the window of channel j."""
     M = np.zeros((C, C))
     for j in range(C):
@@ -158,13 +158,13 @@ def _rnorm_windows(C, size_f, blocked):
 def rnorm(x, size_f, add_scale, pow_scale, blocked=False):
     """Cross-map response norm on every frame: x (T, C, ...) -> x * (1 + a * sum over the channel window of x^2)^-b."""
     x = _f64(x)
-    M = _rnorm_windows(x.shape[1], size_f, blocked)
+    M = rnorm_windows(x.shape[1], size_f, blocked)
     return x * (1 + add_scale * np.einsum("ji,ti...->tj...", M, x * x)) ** (-pow_scale)
 
 
 def rnorm_undo(dy, x, size_f, add_scale, pow_scale, blocked=False):
     dy, x = _f64(dy), _f64(x)
-    M = _rnorm_windows(x.shape[1], size_f, blocked)
+    M = rnorm_windows(x.shape[1], size_f, blocked)
     D = 1 + add_scale * np.einsum("ji,ti...->tj...", M, x * x)
     return dy * D ** (-pow_scale) - 2 * add_scale * pow_scale * x * np.einsum("ij,ti...->tj...", M, dy * x * D ** (-pow_scale - 1))
 
