@@ -11,8 +11,8 @@ What changed relative to the reference, and why (MI355X-first):
     (data_parallel.GradientExchange).
   * GetLoss no longer forces a device->host sync every step (src/convnet.cc:482 -> matrix.cc:253-268):
     with ``fused=True`` the correct-count accumulates on device and is read every ``print_after``.
-  * ``fused=True`` routes conv+bias+ReLU, FC+bias+ReLU, ReLU+dropout, softmax+CE-deriv+count and
-    the SGD step through the library's fused entry points.  ``fused=False`` issues exactly the
+  * ``fused=True`` routes conv+bias+ReLU, FC+bias+ReLU, ReLU+dropout, logistic+dropout, softmax+CE-deriv+count (and its logistic
+    and softmax-distribution counterparts) and the SGD step through the library's fused entry points.  ``fused=False`` issues exactly the
     reference's Matrix-call sequence (used by the parity tests and grad_check).
 """
 import sys
@@ -22,7 +22,7 @@ import torch
 
 from . import pbtxt
 from .edge import AvgPoolEdge, ConvEdge, Edge, EdgeWithWeight, FCEdge, LocalEdge, MaxPoolEdge, ResponseNormEdge
-from .layer import Layer, LinearLayer, ReLULayer, SoftmaxLayer
+from .layer import Layer, LinearLayer, LogisticLayer, ReLULayer, SoftmaxDistLayer, SoftmaxLayer
 from .matrix import Matrix
 from .optimizer import RunFusedSteps
 from .trainer import TrainLoopMixin
@@ -97,7 +97,7 @@ class ConvNet(TrainLoopMixin):
         self.edge_slices_ = {}   # edge -> (offset, length) in the flat buffers
         self.train_dataset_ = None
         self.correct_accum_ = None
-        self._logits_pending = set()   # output layers whose state still holds logits (fused softmax)
+        self._logits_pending = set()   # output layers whose state still holds logits (fused softmax / logistic / softmax-distribution)
         self._bn_steps = []            # fused host: the gamma / beta SGD steps planned during Bprop, run with the edges' batch
         self.BuildNet()
         if exchange is not None and any(l.UseBatchNormalization() for l in self.layers_):
@@ -292,9 +292,32 @@ class ConvNet(TrainLoopMixin):
             return l.is_relu       # the ReLU of an rnorm-fed layer rides in the rnorm kernel; other activations do not
         return isinstance(e, FCEdge)
 
+    def _fused_output(self, l):
+        """Which fused output entry (activation + loss derivative + metric accumulated on the device) serves output layer l:
+        "softmax" (softmax_ce_grad_correct), "logistic" (logistic_ce_grad_correct), "softmax_dist" (softmax_dist_ce_grad) or None.
+        The last two hold for a single output without dropout whose loss and metric are the ones the entry computes; anything
+        else runs the reference's calls."""
+        if not self.fused or not l.IsOutput() or l.IsInput():
+            return None
+        if type(l) is SoftmaxLayer:
+            return "softmax"
+        if len(self.output_layers_) != 1 or l.dropprob_ > 0:
+            return None
+        if isinstance(l, LogisticLayer) and (l.loss_function_, l.performance_metric_) == ("CROSS_ENTROPY_BINARY", "CLASSIFICATION_BINARY"):
+            return "logistic"
+        if isinstance(l, SoftmaxDistLayer) and l.loss_function_ == l.performance_metric_ == "CROSS_ENTROPY_MULTINOMIAL_DISTRIBUTED":
+            return "softmax_dist"
+        return None
+
+    @staticmethod
+    def _dropout_scale(l):
+        return 1.0 / (1 - l.dropprob_) if (l.dropprob_ > 0 and l.dropout_scale_up_at_train_time_) else 1.0
+
     def Fprop(self, train):
         for l in self.layers_:
             fused_act = self._can_fuse_up(l)
+            logistic = isinstance(l, LogisticLayer)   # its edge's epilogue takes the bias only: the sigmoid is a pass of its own
+            dropped = False
             bn = l.UseBatchNormalization()
             for e in l.incoming_edge_:
                 src = e.GetSource()
@@ -306,12 +329,16 @@ class ConvNet(TrainLoopMixin):
                 l.ApplyBatchNormalization(train, relu=self.fused and l.is_relu)
                 if not self.fused:
                     l.ApplyActivation()
-            elif not l.IsInput() and not fused_act:
-                if self.fused and isinstance(l, SoftmaxLayer) and l.IsOutput() and train:
-                    self._logits_pending.add(l)   # softmax + CE derivative + correct count are fused in ComputeDeriv
+            elif not l.IsInput() and (not fused_act or logistic):
+                if train and self._fused_output(l) is not None:
+                    self._logits_pending.add(l)   # activation + CE derivative + metric are fused in ComputeDeriv
+                elif self.fused and logistic and train and l.dropprob_ > 0:
+                    l.GetState().LogisticDropout(l.dropprob_, self._dropout_scale(l))   # (a logistic layer never stores its noise)
+                    dropped = True
                 else:
                     l.ApplyActivation()
-            l.ApplyDropout(train)
+            if not dropped:
+                l.ApplyDropout(train)
 
     def _bprop_edge(self, output, input, edge, fuse_mask=None):
         # ConvNet::Bprop(output, input, edge), src/convnet.cc:362-375
@@ -417,7 +444,9 @@ class ConvNet(TrainLoopMixin):
             scale = self._fused_down_scale(l)
             for e in l.outgoing_edge_:
                 self._bprop_edge(e.GetDest(), l, e, fuse_mask=scale)
-            if scale is None:   # else dropout' and ReLU' were applied by the edge's epilogue
+            if self.fused and isinstance(l, LogisticLayer) and not l.IsInput() and not l.IsOutput():
+                l.GetDeriv().LogisticDerivScaled(l.GetState(), self._dropout_scale(l))   # dropout' and logistic' in one pass
+            elif scale is None:   # else dropout' and ReLU' were applied by the edge's epilogue
                 l.ApplyDerivativeofDropout()
                 if not l.IsInput() and not l.IsOutput():
                     l.ApplyDerivativeOfActivation()
@@ -435,17 +464,19 @@ class ConvNet(TrainLoopMixin):
         for l in self.output_layers_:
             if l in self._logits_pending:
                 self._logits_pending.discard(l)
-                Matrix.SoftmaxCEGradCorrect(l.GetState(), l.GetData(), l.GetState(), l.GetDeriv(), self.correct_accum_,
-                                            l.loss_function_weight_)
+                entry = {"softmax": Matrix.SoftmaxCEGradCorrect, "logistic": Matrix.LogisticCEGradCorrect,
+                         "softmax_dist": Matrix.SoftmaxDistCEGrad}[self._fused_output(l)]
+                entry(l.GetState(), l.GetData(), l.GetState(), l.GetDeriv(), self.correct_accum_, l.loss_function_weight_)
             else:
                 l.ComputeDeriv()
 
     def GetLoss(self):
-        """Per-output-layer performance metric (src/convnet.cc:456-461).  In fused mode a softmax output's correct count
-        accumulates on device (no per-step sync; ReadCorrectCount) and GetLoss returns None — unless some output layer did not
-        take the fused softmax path (e.g. a SQUARED_ERROR linear output) or there are several outputs: the on-device counter
-        is one number, so those nets report per layer through the reference's own call, like the unfused path."""
-        if self.fused and len(self.output_layers_) == 1 and isinstance(self.output_layers_[0], SoftmaxLayer):
+        """Per-output-layer performance metric (src/convnet.cc:456-461).  In fused mode a softmax output's correct count (a
+        logistic output's normalised correct count, a softmax-distribution output's cross entropy) accumulates on device (no
+        per-step sync; ReadCorrectCount) and GetLoss returns None — unless some output layer did not take a fused output path
+        (e.g. a SQUARED_ERROR linear output) or there are several outputs: the on-device counter is one number, so those nets
+        report per layer through the reference's own call, like the unfused path."""
+        if len(self.output_layers_) == 1 and self._fused_output(self.output_layers_[0]) is not None:
             return None
         return [l.GetPerformanceMetric() for l in self.output_layers_]
 
@@ -468,7 +499,7 @@ class ConvNet(TrainLoopMixin):
         return ts
 
     def ReadCorrectCount(self, reset=True):
-        """Fused mode: number of correct predictions since the last read (one D2H sync)."""
+        """Fused mode: the output layer's metric summed since the last read (one D2H sync)."""
         v = float(self.correct_accum_.ToNumpy().reshape(-1)[0])
         if reset:
             self.correct_accum_.Set(0.0)

@@ -531,8 +531,10 @@ struct Philox {
 
 __device__ __forceinline__ float u01(unsigned x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }  // [0,1)
 
+__device__ __forceinline__ float sigmoid1(float x) { return 1.0f / (1.0f + expf(-x)); }   // eigenmat.cc:1389; exp overflow gives 1 / inf = 0
+
 // MODE 0: uniform fill; 1: normal fill (Box-Muller); 2: dropout(p,val,scale) in place; 3: bernoulli(target = u < mat);
-// 4: relu then dropout(p, 0, scale)
+// 4: relu then dropout(p, 0, scale); 5: sigmoid then dropout(p, 0, scale)
 template <int MODE>
 __global__ void rng_kernel(float* __restrict__ out, const float* __restrict__ in, size_t n, Philox ph, float p, float val, float scale) {
   const size_t n4 = (n + 3) >> 2;
@@ -552,7 +554,8 @@ __global__ void rng_kernel(float* __restrict__ out, const float* __restrict__ in
       if (MODE <= 1) out[i] = u[e];
       else if (MODE == 2) out[i] = (p > u[e]) ? val : in[i] * scale;
       else if (MODE == 3) out[i] = (u[e] < in[i]) ? 1.f : 0.f;
-      else { const float x = in[i] > 0.f ? in[i] : 0.f; out[i] = (p > u[e]) ? 0.f : x * scale; }
+      else if (MODE == 4) { const float x = in[i] > 0.f ? in[i] : 0.f; out[i] = (p > u[e]) ? 0.f : x * scale; }
+      else { const float x = sigmoid1(in[i]); out[i] = (p > u[e]) ? 0.f : x * scale; }
     }
   }
 }
@@ -568,9 +571,198 @@ int rng_launch(rnd_struct* st, float* out, const float* in, size_t n, float p, f
   ph.k1 = (unsigned)h->seed ^ (unsigned)(h->counter >> 32) ^ 0x85EBCA6Bu;
   h->counter++;
   if (n == 0) return 0;
-  KernelTimer timer(MODE == 2 ? "rng_kernel<dropout>" : MODE == 4 ? "rng_kernel<relu_dropout>" : "rng_kernel", "rng", 0.0, 4.0 * n * (in ? 2 : 1));
+  KernelTimer timer(MODE == 2 ? "rng_kernel<dropout>" : MODE == 4 ? "rng_kernel<relu_dropout>" : MODE == 5 ? "rng_kernel<logistic_dropout>" : "rng_kernel", "rng", 0.0, 4.0 * n * (in ? 2 : 1));
   hipLaunchKernelGGL(rng_kernel<MODE>, dim3(blocks_for(n / 4 + 1)), dim3(kThreads), 0, stream(), out, in, n, ph, p, val, scale);
   return launch_status();
+}
+
+// ---- logistic and softmax-distribution layers (src/layer.cc:579-602, src/loss_functions.cc:55-140; arithmetic of eigenmat.cc) ----------
+// The stream skeleton of the element-wise entries: NI inputs, NO outputs of n floats, outputs may alias inputs (an element is read and
+// written by the same lane).  When every pointer has the same offset within 16 bytes (a get_slice view of a matrix with an odd row
+// count starts 4-byte aligned only) the `head` floats up to the first 16-byte boundary and the tail run scalar and the body as one
+// 16-byte access per array; pointers that disagree run all scalar (head == n).
+// (map2 above stays as it is — it serves every older entry and goes all scalar on such a view; it takes two inputs and one output, and
+// these entries need the head, and a skeleton that extends to more arrays, without touching the kernels those entries were measured with.)
+template <int NI, int NO, typename F>
+struct StreamArgs {
+  const float* in[NI];
+  float* out[NO];
+  size_t n, head;
+  F f;   // void f(const float (&x)[NI], float (&y)[NO])
+};
+template <int NI, int NO, typename F>
+__global__ void stream_kernel(const StreamArgs<NI, NO, F> a) {
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  const size_t n4 = (a.n - a.head) >> 2;
+  for (size_t i = tid; i < n4; i += stride) {
+    f32x4 x[NI], y[NO];
+#pragma unroll
+    for (int k = 0; k < NI; ++k) x[k] = reinterpret_cast<const f32x4*>(a.in[k] + a.head)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float xv[NI], yv[NO];
+#pragma unroll
+      for (int k = 0; k < NI; ++k) xv[k] = x[k][e];
+      a.f(xv, yv);
+#pragma unroll
+      for (int k = 0; k < NO; ++k) y[k][e] = yv[k];
+    }
+#pragma unroll
+    for (int k = 0; k < NO; ++k) reinterpret_cast<f32x4*>(a.out[k] + a.head)[i] = y[k];
+  }
+  const size_t rest = a.n - (n4 << 2);   // head + tail
+  for (size_t r = tid; r < rest; r += stride) {
+    const size_t i = r < a.head ? r : (n4 << 2) + r;
+    float xv[NI], yv[NO];
+#pragma unroll
+    for (int k = 0; k < NI; ++k) xv[k] = a.in[k][i];
+    a.f(xv, yv);
+#pragma unroll
+    for (int k = 0; k < NO; ++k) a.out[k][i] = yv[k];
+  }
+}
+template <int NI, int NO, typename F>
+int stream_launch(const char* name, const float* const (&in)[NI], float* const (&out)[NO], size_t n, F f) {
+  if (n == 0) return 0;
+  StreamArgs<NI, NO, F> a{{}, {}, n, 0, f};
+  const uintptr_t off = reinterpret_cast<uintptr_t>(out[0]) & 15;
+  bool same = (off & 3) == 0;
+  for (int k = 0; k < NI; ++k) { a.in[k] = in[k]; same = same && (reinterpret_cast<uintptr_t>(in[k]) & 15) == off; }
+  for (int k = 0; k < NO; ++k) { a.out[k] = out[k]; same = same && (reinterpret_cast<uintptr_t>(out[k]) & 15) == off; }
+  a.head = same ? ((16 - off) & 15) >> 2 : n;
+  if (a.head > n) a.head = n;
+  KernelTimer timer(name, "logistic", 0.0, 4.0 * n * (NI + NO));
+  hipLaunchKernelGGL((stream_kernel<NI, NO, F>), dim3(blocks_for(n / 4 + 1)), dim3(kThreads), 0, stream(), a);
+  return launch_status();
+}
+
+// One case per matrix ROW, as in the softmax kernels above: a block owns 32 consecutive rows and G column groups; lane (r, g) walks
+// columns g, g + G, ... of row r (coalesced over the 32 rows), the groups of a row are combined in LDS in group order.
+//  * get_logistic_correct_normalized (eigenmat.cc:1344-1373): share[row] = #{t >= 0 and (p >= 0.5) == (t >= 0.5)} / #{t >= 0}, 0 when
+//    nothing counts.  Both counts are integers below 2^24, so any summation order gives the reference's fp32 loop exactly.
+//  * FUSED: mat holds logits; p = sigmoid into probs (may alias mat), deriv = (t < 0 ? 0 : p - t) * deriv_scale, and the block's sum of
+//    its rows' shares (row order) goes to part[blockIdx.x] for accum_finish_kernel.
+template <int G, bool FUSED>
+__global__ void __launch_bounds__(G * 32) logistic_rows_kernel(const float* mat, const float* __restrict__ targets, float* probs, float* __restrict__ deriv,
+                                                                float* __restrict__ out, int rows, int cols, float deriv_scale) {
+  __shared__ float rc[G][33], rt[G][33];
+  const int r = threadIdx.x & 31, g = threadIdx.x >> 5;
+  const int row = blockIdx.x * 32 + r;
+  float correct = 0.f, total = 0.f;
+  if (row < rows)
+    for (int j = g; j < cols; j += G) {
+      const size_t x = (size_t)j * rows + row;
+      const float t = targets[x];
+      float p = mat[x];
+      if (FUSED) {
+        p = sigmoid1(p);
+        probs[x] = p;
+        const float d = t < 0.f ? 0.f : p - t;
+        deriv[x] = d * deriv_scale;
+      }
+      if (!(t < 0.f)) {
+        total += 1.f;
+        correct += ((t >= 0.5f && p >= 0.5f) || (t < 0.5f && p < 0.5f)) ? 1.f : 0.f;
+      }
+    }
+  rc[g][r] = correct;
+  rt[g][r] = total;
+  __syncthreads();
+  float share = 0.f;
+  if (g == 0) {
+#pragma unroll
+    for (int k = 1; k < G; ++k) {
+      correct += rc[k][r];
+      total += rt[k][r];
+    }
+    share = total > 0.f ? correct / total : 0.f;
+  }
+  if (!FUSED) {
+    if (g == 0 && row < rows) out[row] = share;
+    return;
+  }
+  if (g == 0) rc[0][r] = row < rows ? share : 0.f;   // (lane (r, 0) alone has read column r of rc)
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = 0.f;
+    for (int k = 0; k < 32; ++k) s += rc[0][k];
+    out[blockIdx.x] = s;
+  }
+}
+
+// softmax_rows_kernel's three passes (same maxima, same exponentials, same order of the row sums: bit-identical probabilities) with a
+// target DISTRIBUTION per row: deriv = (p - t) * deriv_scale, and the block's sum of -t * log(p + tiny) to part[blockIdx.x]
+// (per lane in column order, lanes of a row in group order, rows in row order).
+template <int G>
+__global__ void __launch_bounds__(G * 32) softmax_dist_rows_kernel(const float* logits, const float* __restrict__ targets, float* probs, float* __restrict__ deriv,
+                                                                    float* __restrict__ part, int rows, int cols, float deriv_scale, float tiny) {
+  __shared__ float red[G][33];
+  const int r = threadIdx.x & 31, g = threadIdx.x >> 5;
+  const int row = blockIdx.x * 32 + r;
+  const bool ok = row < rows;
+  float mx = -FLT_MAX;
+  if (ok)
+    for (int j = g; j < cols; j += G) {
+      const float v = logits[(size_t)j * rows + row];
+      if (v > mx) mx = v;
+    }
+  red[g][r] = mx;
+  __syncthreads();
+  mx = red[0][r];
+#pragma unroll
+  for (int k = 1; k < G; ++k) {
+    const float v = red[k][r];
+    if (v > mx) mx = v;
+  }
+  __syncthreads();
+  float s = 0.f;
+  if (ok)
+    for (int j = g; j < cols; j += G) {
+      const size_t x = (size_t)j * rows + row;
+      const float e = expf(logits[x] - mx);
+      probs[x] = e;
+      s += e;
+    }
+  red[g][r] = s;
+  __syncthreads();
+  s = 0.f;
+#pragma unroll
+  for (int k = 0; k < G; ++k) s += red[k][r];
+  __syncthreads();
+  float ce = 0.f;
+  if (ok)
+    for (int j = g; j < cols; j += G) {
+      const size_t x = (size_t)j * rows + row;
+      const float pr = probs[x] / s;
+      const float t = targets[x];
+      probs[x] = pr;
+      const float d = pr - t;
+      deriv[x] = d * deriv_scale;
+      ce += -t * logf(pr + tiny);
+    }
+  red[g][r] = ce;
+  __syncthreads();
+  if (g == 0) {
+    ce = 0.f;
+#pragma unroll
+    for (int k = 0; k < G; ++k) ce += red[k][r];
+    red[0][r] = ce;   // (lane (r, 0) alone has read column r of red)
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int k = 0; k < 32; ++k) t += red[0][k];
+    part[blockIdx.x] = t;
+  }
+}
+
+// accum[0] += sum of part[0 .. n) in a fixed order: one block, no atomics — the same bits from call to call
+__global__ void accum_finish_kernel(const float* __restrict__ part, int n, float* __restrict__ accum) {
+  __shared__ float sh[8];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) s += part[i];
+  s = block_sum(s, sh);
+  if (threadIdx.x == 0) accum[0] += s;
 }
 
 // One fused pass of SGDOptimizer::Optimize.  Explicit __fmul_rn/__fadd_rn keep each reference
@@ -1054,6 +1246,112 @@ int rmsprop_momentum_step_multi(int count, cudamat** grads, cudamat** params, cu
     m[0] = grads[i]; m[1] = params[i]; m[2] = histories[i]; m[3] = rms_histories[i];
     op = RmsPropOp{factor[i], l2_decay[i], gradient_clip[i], epsilon[i], momentum[i]};
   });
+}
+
+// ---- logistic and softmax-distribution layers: cudamat.cuh:204,216,233,252,289 and the fused entries (include/convnet_hip.h) -----------
+namespace {
+// cudamat's checks (cudamat.cu:2385-2452): on device, then transposedness, then the exact sizes
+int same_shape_check(const cudamat* a, const cudamat* b, const cudamat* c) {
+  if (!a->on_device || !b->on_device || (c && !c->on_device)) return ERROR_NOT_ON_DEVICE;
+  if (a->is_trans != b->is_trans) return ERROR_TRANSPOSEDNESS;
+  if (a->size[0] != b->size[0] || a->size[1] != b->size[1] || (c && (a->size[0] != c->size[0] || a->size[1] != c->size[1])))
+    return ERROR_INCOMPATIBLE_DIMENSIONS;
+  return 0;
+}
+inline bool is_1x1(const cudamat* m) { return m->size[0] == 1 && m->size[1] == 1; }
+}  // namespace
+
+int apply_sigmoid(cudamat* mat, cudamat* target) {
+  if (int rc = same_shape_check(mat, target, nullptr)) return rc;
+  const float* const in[] = {mat->data_device};
+  float* const out[] = {target->data_device};
+  return stream_launch("stream_kernel<sigmoid>", in, out, numel(mat), [] __device__(const float (&x)[1], float (&y)[1]) { y[0] = sigmoid1(x[0]); });
+}
+int apply_logistic_deriv(cudamat* mat1, cudamat* mat2, cudamat* target) {
+  if (int rc = same_shape_check(mat1, mat2, target)) return rc;
+  const float* const in[] = {mat1->data_device, mat2->data_device};
+  float* const out[] = {target->data_device};
+  return stream_launch("stream_kernel<logistic_deriv>", in, out, numel(mat1), [] __device__(const float (&x)[2], float (&y)[1]) {
+#pragma clang fp contract(off)
+    const float dy = x[0] * x[1];
+    const float om = 1.0f - x[1];
+    y[0] = dy * om;
+  });
+}
+int apply_logistic_grad(cudamat* mat1, cudamat* mat2, cudamat* out_grad) {
+  if (int rc = same_shape_check(mat1, mat2, out_grad)) return rc;
+  const float* const in[] = {mat1->data_device, mat2->data_device};
+  float* const out[] = {out_grad->data_device};
+  return stream_launch("stream_kernel<logistic_grad>", in, out, numel(mat1),
+                       [] __device__(const float (&x)[2], float (&y)[1]) { y[0] = x[1] < 0.f ? 0.f : x[0] - x[1]; });
+}
+int get_logistic_correct_normalized(cudamat* mat1, cudamat* mat2, cudamat* out) {
+  if (!mat1->on_device || !mat2->on_device || !out->on_device) return ERROR_NOT_ON_DEVICE;
+  if (mat1->is_trans != mat2->is_trans) return ERROR_TRANSPOSEDNESS;
+  if (mat1->size[0] != mat2->size[0] || mat1->size[1] != mat2->size[1] || mat1->size[0] != out->size[0] || out->size[1] != 1)
+    return ERROR_INCOMPATIBLE_DIMENSIONS;
+  const int rows = mat1->size[0], cols = mat1->size[1];
+  if (rows == 0) return 0;
+  KernelTimer timer("logistic_rows_kernel", "logistic", 0.0, 4.0 * ((double)rows * cols * 2 + rows));
+  hipLaunchKernelGGL((logistic_rows_kernel<32, false>), dim3(divup(rows, 32)), dim3(1024), 0, stream(), mat1->data_device, mat2->data_device, nullptr,
+                     nullptr, out->data_device, rows, cols, 1.0f);
+  return launch_status();
+}
+int compute_cross_entropy(cudamat* mat, cudamat* pow, cudamat* target, float tiny) {
+  if (int rc = same_shape_check(mat, pow, target)) return rc;
+  const float* const in[] = {mat->data_device, pow->data_device};
+  float* const out[] = {target->data_device};
+  return stream_launch("stream_kernel<cross_entropy>", in, out, numel(mat),
+                       [tiny] __device__(const float (&x)[2], float (&y)[1]) { y[0] = -x[0] * logf(x[1] + tiny); });
+}
+
+int logistic_dropout(rnd_struct* st, cudamat* mat, float dropprob, float scale) {
+  if (!mat->on_device) return ERROR_NOT_ON_DEVICE;
+  return rng_launch<5>(st, mat->data_device, mat->data_device, numel(mat), dropprob, 0.f, scale);
+}
+int logistic_deriv_scaled(cudamat* deriv, cudamat* state, float scale) {
+  if (int rc = same_shape_check(deriv, state, nullptr)) return rc;
+  const float* const in[] = {deriv->data_device, state->data_device};
+  float* const out[] = {deriv->data_device};
+  return stream_launch("stream_kernel<logistic_deriv_scaled>", in, out, numel(deriv), [scale] __device__(const float (&x)[2], float (&y)[1]) {
+#pragma clang fp contract(off)
+    const float d = scale == 1.0f ? x[0] : x[0] * scale;
+    const float dy = d * x[1];
+    const float om = 1.0f - x[1];
+    y[0] = dy * om;
+  });
+}
+int logistic_ce_grad_correct(cudamat* logits, cudamat* targets, cudamat* probs, cudamat* deriv, cudamat* correct_accum, float deriv_scale) {
+  if (!correct_accum->on_device) return ERROR_NOT_ON_DEVICE;
+  if (int rc = same_shape_check(logits, targets, probs)) return rc;
+  if (int rc = same_shape_check(logits, targets, deriv)) return rc;
+  if (!is_1x1(correct_accum)) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  const int rows = logits->size[0], cols = logits->size[1];
+  if (rows == 0) return 0;
+  const int nb = divup(rows, 32);
+  float* part = static_cast<float*>(workspace(sizeof(float) * nb));
+  // reads logits and targets, writes probs and deriv
+  KernelTimer timer("logistic_rows_kernel<fused>", "logistic_ce", 0.0, 4.0 * (double)rows * cols * 4);
+  hipLaunchKernelGGL((logistic_rows_kernel<32, true>), dim3(nb), dim3(1024), 0, stream(), logits->data_device, targets->data_device, probs->data_device,
+                     deriv->data_device, part, rows, cols, deriv_scale);
+  hipLaunchKernelGGL(accum_finish_kernel, dim3(1), dim3(256), 0, stream(), part, nb, correct_accum->data_device);
+  return launch_status();
+}
+int softmax_dist_ce_grad(cudamat* logits, cudamat* targets, cudamat* probs, cudamat* deriv, cudamat* ce_accum, float deriv_scale, float tiny) {
+  if (!ce_accum->on_device) return ERROR_NOT_ON_DEVICE;
+  if (int rc = same_shape_check(logits, targets, probs)) return rc;
+  if (int rc = same_shape_check(logits, targets, deriv)) return rc;
+  if (!is_1x1(ce_accum)) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  const int rows = logits->size[0], cols = logits->size[1];
+  if (rows == 0) return 0;
+  const int nb = divup(rows, 32);
+  float* part = static_cast<float*>(workspace(sizeof(float) * nb));
+  // reads logits twice, probs once and targets; writes probs twice and deriv
+  KernelTimer timer("softmax_dist_rows_kernel", "softmax_dist_ce", 0.0, 4.0 * (double)rows * cols * 7);
+  hipLaunchKernelGGL(softmax_dist_rows_kernel<32>, dim3(nb), dim3(1024), 0, stream(), logits->data_device, targets->data_device, probs->data_device,
+                     deriv->data_device, part, rows, cols, deriv_scale, tiny);
+  hipLaunchKernelGGL(accum_finish_kernel, dim3(1), dim3(256), 0, stream(), part, nb, ce_accum->data_device);
+  return launch_status();
 }
 
 int init_random(rnd_struct* rnd_state, int seed) {

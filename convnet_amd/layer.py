@@ -1,6 +1,6 @@
-"""Layers — mirror of src/layer.{h,cc} for the hot path: Linear / ReLU / Softmax layers with binary
-dropout, batch normalisation, CE loss and the classification metric.  Logistic, slices and the
-model-parallel state copies are out of scope."""
+"""Layers — mirror of src/layer.{h,cc} for the hot path: Linear / ReLU / Logistic / Softmax / Softmax-distribution layers with
+binary dropout, batch normalisation, their losses and metrics.  Slices, Gaussian dropout and the model-parallel state copies are
+out of scope."""
 import numpy as np
 
 from .loss_functions import LossFunction
@@ -15,10 +15,14 @@ class Layer:
         a = config.activation
         if a == "LINEAR":
             return LinearLayer(config)
+        if a == "LOGISTIC":
+            return LogisticLayer(config)
         if a == "RECTIFIED_LINEAR":
             return ReLULayer(config)
         if a == "SOFTMAX":
             return SoftmaxLayer(config)
+        if a == "SOFTMAX_DIST":
+            return SoftmaxDistLayer(config)
         raise SystemExit(f"Undefined layer type {a} (out of hot-path scope).")
 
     def __init__(self, config):
@@ -313,3 +317,36 @@ class SoftmaxLayer(Layer):
 
     def ApplyDerivativeOfActivation(self):
         raise SystemExit("Back prop through softmax is not implemented.")
+
+
+class SoftmaxDistLayer(SoftmaxLayer):
+    """Softmax against a target DISTRIBUTION per case (src/layer.cc:579-584)."""
+
+    def AllocateMemory(self, batch_size):
+        Layer.AllocateMemory(self, batch_size)
+        numdims = self.state_.GetCols()
+        Matrix.RegisterTempMemory(batch_size * numdims)   # for computing CE
+        if self.is_output_:
+            self.data_.AllocateGPUMemory(batch_size, numdims, self.name_ + " data")
+
+
+class LogisticLayer(Layer):
+    """src/layer.cc:586-602.  The dropout mask is not stored: ApplyDerivativeofDropout scales the derivative by 1 / (1 - p) and the
+    logistic derivative y (1 - y) is then taken at the dropout-SCALED state, exactly 0 for a dropped unit — the reference's quirk, kept."""
+    is_relu = False
+
+    def __init__(self, config):
+        super().__init__(config)
+        self.store_dropout_noise_ = False
+
+    def AllocateMemory(self, batch_size):
+        super().AllocateMemory(batch_size)
+        Matrix.RegisterTempMemory(batch_size)
+        if self.is_output_:
+            self.data_.AllocateGPUMemory(batch_size, self.num_channels_, self.name_ + " data")
+
+    def ApplyActivation(self):
+        self.state_.ApplyLogistic()
+
+    def ApplyDerivativeOfActivation(self):
+        self.deriv_.ApplyDerivativeOfLogistic(self.state_)

@@ -351,6 +351,20 @@ class Matrix:
     def ApplySoftmax(self):
         _chk(lib.softmax_row_major(self.GetMat(), self.GetMat()), "softmax")
 
+    def ApplyLogistic(self):
+        _chk(lib.apply_sigmoid(self.GetMat(), self.GetMat()), "logistic")
+
+    def ApplyDerivativeOfLogistic(self, state):
+        _chk(lib.apply_logistic_deriv(self.GetMat(), state.GetMat(), self.GetMat()), "logistic deriv")
+
+    def LogisticDropout(self, dropprob, scale_factor):
+        """Fused ApplyLogistic + Dropout(p, 0, scale) (one pass; same mask, same bits)."""
+        _chk(lib.logistic_dropout(ctypes.byref(Matrix._rnd), self.GetMat(), float(dropprob), float(scale_factor)), "logistic_dropout")
+
+    def LogisticDerivScaled(self, state, scale):
+        """Fused Mult(scale) + ApplyDerivativeOfLogistic(state) (one pass; same bits)."""
+        _chk(lib.logistic_deriv_scaled(self.GetMat(), state.GetMat(), float(scale)), "logistic_deriv_scaled")
+
     def Dropout(self, dropprob, fill_value, scale_factor):
         _chk(lib.dropout(ctypes.byref(Matrix._rnd), self.GetMat(), float(dropprob), float(fill_value), float(scale_factor)), "dropout")
 
@@ -558,6 +572,28 @@ class Matrix:
     @staticmethod
     def SoftmaxCE(state, gt, output):
         _chk(lib.get_softmax_cross_entropy_row_major(state.GetMat(), gt.GetMat(), output.GetMat(), 1e-10), "softmax ce")
+
+    @staticmethod
+    def LogisticCEDeriv(state, gt, deriv):
+        _chk(lib.apply_logistic_grad(state.GetMat(), gt.GetMat(), deriv.GetMat()), "logistic grad")
+
+    @staticmethod
+    def LogisticCorrect(state, gt, output):
+        _chk(lib.get_logistic_correct_normalized(state.GetMat(), gt.GetMat(), output.GetMat()), "logistic correct")
+
+    @staticmethod
+    def SoftmaxDistCE(state, gt, output):
+        _chk(lib.compute_cross_entropy(gt.GetMat(), state.GetMat(), output.GetMat(), 1e-10), "SoftmaxDistCE")
+
+    @staticmethod
+    def LogisticCEGradCorrect(logits, gt, probs, deriv, correct_accum, deriv_scale=1.0):
+        _chk(lib.logistic_ce_grad_correct(logits.GetMat(), gt.GetMat(), probs.GetMat(), deriv.GetMat(), correct_accum.GetMat(),
+                                          float(deriv_scale)), "logistic fused")
+
+    @staticmethod
+    def SoftmaxDistCEGrad(logits, gt, probs, deriv, ce_accum, deriv_scale=1.0):
+        _chk(lib.softmax_dist_ce_grad(logits.GetMat(), gt.GetMat(), probs.GetMat(), deriv.GetMat(), ce_accum.GetMat(), float(deriv_scale),
+                                      1e-10), "softmax dist fused")
 
     @staticmethod
     def SoftmaxCEGradCorrect(logits, gt, probs, deriv, correct_accum, deriv_scale=1.0):

@@ -14,6 +14,9 @@ text so they can also be written to disk and fed to the reference's own binaries
                      softmax.
 * ``video_small()`` — a small spatio-temporal (3-D) net: 3-D convs, max pooling without and with a time extent, response norm,
                      average pooling over all remaining frames.
+* ``multilabel_small()`` — a small multi-label net: conv -> LOGISTIC -> average pool -> FC LOGISTIC -> FC LOGISTIC output of independent
+                     yes/no units (CROSS_ENTROPY_BINARY / CLASSIFICATION_BINARY; a negative target means "don't care").
+* ``softdist_small()`` — the same trunk with ReLU and a SOFTMAX_DIST output trained on a target distribution per case.
 tests/test_models.py checks the first two against the reference's files when they are mounted.
 """
 
@@ -280,6 +283,34 @@ def video_small(image_size=32, frames=16, num_classes=10, grad_check=False, init
     s += _time(_pool("conv3", "pool3", 0, 1, kind="AVERAGE_POOL"), kt=0)   # kernel sizes <= 0: the whole map, all frames (maxpool_edge.cc:13-25)
     s += _fc("pool3", "output", init_wt=init_wt, grad_check=gc)
     return s
+
+
+def _small_head_trunk(name, act, dropprob, image_size, output, init_wt, gc):
+    s = _header(name)
+    s += _layer("input", 3, size=image_size)
+    s += _layer("conv1", 16, act, dropprob) + _layer("pool1", 16) + _layer("fc2", 32, act, dropprob) + output
+    s += _conv("input", "conv1", 3, 1, 1, init_wt=init_wt, grad_check=gc) + _pool("conv1", "pool1", 3, 2, kind="AVERAGE_POOL")
+    s += _fc("pool1", "fc2", init_wt=init_wt, grad_check=gc) + _fc("fc2", "output", init_wt=init_wt, grad_check=gc)
+    return s
+
+
+def multilabel_small(image_size=12, num_labels=2, dropprob=0.0, grad_check=False):
+    """A small multi-label net: conv3p1/16 LOGISTIC -> avg3s2 -> fc32 LOGISTIC -> fc LOGISTIC output with ``num_labels`` independent
+    yes/no units, trained with CROSS_ENTROPY_BINARY and scored with CLASSIFICATION_BINARY (the share of a case's counted labels that
+    are right; a negative target is not counted).  ``dropprob``: dropout on the two logistic hidden layers.
+    Sigmoid units with average pooling (the LeNet pairing) make the whole net smooth, and init_wt = 3 keeps the two y (1 - y) <= 1/4
+    factors of the backward pass from shrinking conv1's gradients to the fp32 difference-quotient quantum ulp(loss) / (2 eps batch)
+    ~ 1e-6: a grad_check of this net measures the gradients, not the rounding of the loss."""
+    out = _layer("output", num_labels, "LOGISTIC", extra="  loss_function: CROSS_ENTROPY_BINARY\n  performance_metric: CLASSIFICATION_BINARY\n")
+    return _small_head_trunk("multilabel_small", "LOGISTIC", dropprob, image_size, out, 3.0, _gc(grad_check, 6))
+
+
+def softdist_small(image_size=12, num_classes=10, dropprob=0.0, grad_check=False):
+    """multilabel_small's trunk with ReLU layers and a SOFTMAX_DIST output: the target is a distribution over ``num_classes`` per case
+    (soft labels, distillation); CROSS_ENTROPY_MULTINOMIAL_DISTRIBUTED is both the loss and the reported metric."""
+    out = _layer("output", num_classes, "SOFTMAX_DIST", extra="  loss_function: CROSS_ENTROPY_MULTINOMIAL_DISTRIBUTED\n"
+                 "  performance_metric: CROSS_ENTROPY_MULTINOMIAL_DISTRIBUTED\n")
+    return _small_head_trunk("softdist_small", "RECTIFIED_LINEAR", dropprob, image_size, out, 1.0, _gc(grad_check, 6))
 
 
 # forward MACs per image of a built net (for roofline accounting): see bench.py

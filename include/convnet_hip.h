@@ -430,6 +430,27 @@ int apply_softmax_grad_row_major(cudamat* mat, cudamat* labels, cudamat* target)
 int get_softmax_correct_row_major(cudamat* mat, cudamat* labels, cudamat* target);
 int get_softmax_cross_entropy_row_major(cudamat* mat, cudamat* labels, cudamat* target, float tiny);
 
+/* ---- logistic and softmax-distribution layers: cudamat.cuh:204,216,233,252,289 (src/layer.cc:579-602, src/loss_functions.cc:55-140) ----
+ * Arithmetic of the reference's CPU build (eigenmat.cc:1133-1151,1344-1392,1543-1557,1771-1786), the whole-net parity target.  Checks:
+ * ERROR_NOT_ON_DEVICE, then ERROR_TRANSPOSEDNESS when the first two operands differ in is_trans, then ERROR_INCOMPATIBLE_DIMENSIONS
+ * unless every operand has the same (rows, cols).  Views are fine (a get_slice that starts 4-byte aligned only runs its first floats
+ * scalar, then 16-byte accesses), and so is target == an operand.
+ *  apply_sigmoid       : target = 1 / (1 + exp(-mat)): exactly 1 for large x, 0 or a denormal for very negative x (exp overflows to
+ *                        inf, 1 / inf = 0: no NaN from overflow), NaN for NaN.
+ *  apply_logistic_deriv: target = (mat1 * mat2) * (1 - mat2), mat1 the derivative, mat2 the logistic state; three separately rounded
+ *                        fp32 operations.
+ *  apply_logistic_grad : out_grad = mat2 < 0 ? 0 : mat1 - mat2, mat1 the probabilities, mat2 the targets; a negative target means
+ *                        "don't care".
+ *  get_logistic_correct_normalized: out is (rows, 1); out[row] = the share of the row's entries with target >= 0 whose (p >= 0.5)
+ *                        agrees with (target >= 0.5); 0 when the row has no entry with target >= 0.  Exact (integer counts).
+ *  compute_cross_entropy: target = -mat * log(pow + tiny), mat the target distribution, pow the probabilities.  (eigenmat's second
+ *                        size check compares pow with itself; here pow must have mat's size.) */
+int apply_sigmoid(cudamat* mat, cudamat* target);
+int apply_logistic_deriv(cudamat* mat1, cudamat* mat2, cudamat* target);
+int apply_logistic_grad(cudamat* mat1, cudamat* mat2, cudamat* out_grad);
+int get_logistic_correct_normalized(cudamat* mat1, cudamat* mat2, cudamat* out);
+int compute_cross_entropy(cudamat* mat, cudamat* pow, cudamat* target, float tiny);
+
 /* ---- RNG (cudamat.cuh:117-119,154-164).  The reference's GPU (multiply-with-carry) and CPU
  * (std::default_random_engine) streams already differ from each other; this
  * library uses a counter-based Philox-4x32-10 keyed by (seed, call counter, element index). --------- */
@@ -492,6 +513,32 @@ int rmsprop_momentum_step_multi(int count, cudamat** grads, cudamat** params, cu
 int softmax_ce_grad_correct(cudamat* logits, cudamat* labels, cudamat* probs, cudamat* deriv,
                             cudamat* correct_accum, float deriv_scale);
 int relu_dropout(rnd_struct* rnd_state, cudamat* mat, float dropprob, float scale);
+/* The logistic and softmax-distribution layers in fewer passes.  Error codes as for the entries they replace; the accumulators must be
+ * 1x1 device matrices (ERROR_INCOMPATIBLE_DIMENSIONS otherwise).
+ *  logistic_dropout     : apply_sigmoid(mat, mat) then dropout(p, 0, scale) (src/layer.cc:391,597) in one pass over mat.  Draws the
+ *                         Philox value dropout would draw for each element and advances the call counter once, as dropout does: the
+ *                         same mask and the same bits as the two calls.
+ *  logistic_deriv_scaled: mult_by_scalar(deriv, scale) then apply_logistic_deriv(deriv, state, deriv) (Layer::ApplyDerivativeofDropout
+ *                         + LogisticLayer::ApplyDerivativeOfActivation, src/layer.cc:399-413,600-602) in place:
+ *                         deriv = ((deriv * scale) * state) * (1 - state), every product separately rounded, bit-identical to the two
+ *                         calls; scale == 1 skips the first product (no dropout: the reference issues no Mult either).
+ *  logistic_ce_grad_correct: apply_sigmoid(logits, probs) + apply_logistic_grad(probs, targets, deriv) + mult_by_scalar(deriv,
+ *                         deriv_scale) + get_logistic_correct_normalized + the sum of its (rows, 1) result (src/layer.cc:597,
+ *                         src/loss_functions.cc:93-95,130-135).  probs may alias logits.  probs and deriv are bit-identical to the
+ *                         sequence; the sum over rows of the normalised correct share is ADDED to correct_accum: per-block partials in
+ *                         row order, then one block adds them in a fixed order — no atomics, the same bits from call to call, and no
+ *                         device-to-host copy, so the host reads it every print_after steps.
+ *  softmax_dist_ce_grad : softmax_row_major(logits, probs) + subtract_elementwise(probs, targets, deriv) + mult_by_scalar(deriv,
+ *                         deriv_scale) + compute_cross_entropy(targets, probs, .., tiny) + the sum of its result (src/layer.cc:570,
+ *                         src/loss_functions.cc:100-110); targets holds one distribution per row.  probs may alias logits.  probs and
+ *                         deriv are bit-identical to the sequence; the sum of -t * log(p + tiny) is ADDED to ce_accum the same
+ *                         atomics-free way (fp32 partial sums: tolerance-equal to a float64 sum). */
+int logistic_dropout(rnd_struct* rnd_state, cudamat* mat, float dropprob, float scale);
+int logistic_deriv_scaled(cudamat* deriv, cudamat* state, float scale);
+int logistic_ce_grad_correct(cudamat* logits, cudamat* targets, cudamat* probs, cudamat* deriv, cudamat* correct_accum,
+                             float deriv_scale);
+int softmax_dist_ce_grad(cudamat* logits, cudamat* targets, cudamat* probs, cudamat* deriv, cudamat* ce_accum, float deriv_scale,
+                         float tiny);
 /* Batch normalisation of a layer's state in place, `state` read as (numel / C, C) with C = numel(gamma) (layer.cc:454: Reshape(-1, C));
  * gamma, beta, mu, sigma, batch_mu, batch_sigma are C-float device vectors.
  *  bn_fprop_act  : Layer::ApplyBatchNormalization(train) (src/layer.cc:452-480) [+ ReLULayer::ApplyActivation, layer.cc:549-551 when
