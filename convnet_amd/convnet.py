@@ -13,10 +13,13 @@ What changed relative to the reference, and why (MI355X-first):
     with ``fused=True`` the correct-count accumulates on device and is read every ``print_after``.
   * ``fused=True`` routes conv+bias+ReLU, FC+bias+ReLU, ReLU+dropout, logistic+dropout, softmax+CE-deriv+count (and its logistic
     and softmax-distribution counterparts) and the SGD step through the library's fused entry points.  ``fused=False`` issues exactly the
-    reference's Matrix-call sequence (used by the parity tests and grad_check).
+    reference's Matrix-call sequence (used by the parity tests and grad_check).  Which entry serves which layer is decided once, when the
+    graph is built (LayerPlan); Fprop / Bprop / ComputeDeriv / GetLoss read the plan.
 """
+import os
 import sys
 from collections import deque
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -26,6 +29,19 @@ from .layer import Layer, LinearLayer, LogisticLayer, ReLULayer, SoftmaxDistLaye
 from .matrix import Matrix
 from .optimizer import RunFusedSteps
 from .trainer import TrainLoopMixin
+
+
+class LayerPlan(NamedTuple):
+    """Which library entries serve one layer: every per-layer choice of Fprop / Bprop / ComputeDeriv, made once by ConvNet._plan_layer
+    when BuildNet has wired the graph.  An unfused net plans the reference's own sequence."""
+    fuse_relu: Optional[bool]          # incoming edges' ComputeUp: None = the reference sequence, False = bias in the epilogue, True = bias and ReLU
+    bn_relu: Optional[bool]            # a batch-normalised layer (else None): whether bn_fprop_act applies the ReLU in the same pass
+    activate: bool                     # ApplyActivation follows: no epilogue has applied the activation
+    output_entry: Optional[Callable]   # train: the state keeps the logits for this entry (activation + loss derivative + metric, ComputeDeriv)
+    logistic_dropout: bool             # train: LogisticDropout instead of ApplyActivation + ApplyDropout (a logistic layer never stores its noise)
+    dropout_scale: float               # Layer.TrainDropoutScale()
+    down_scale: Optional[float]        # ComputeDown's post-scale: ReLU' and dropout' ride in the only outgoing edge's epilogue (None: they do not)
+    logistic_deriv: bool               # LogisticDerivScaled instead of ApplyDerivativeofDropout + ApplyDerivativeOfActivation
 
 
 class ConvNet(TrainLoopMixin):
@@ -50,7 +66,6 @@ class ConvNet(TrainLoopMixin):
         # layer's response-norm / pool undo).  Same arithmetic; which pairing is faster is a property of the kernels of the day: round 3
         # measured "after" 0.08 ms ahead; with round 4's kernels (faster gather-GEMMs, the 2 x 2-block pool undo) "before" is 0.25 ms ahead
         # (10.98-11.00 vs 11.23-11.28 ms, same call, profiles/r04_kernel_experiments.md §4).  CONVNET_WGRAD_ORDER overrides (A/B runs).
-        import os
         self.wgrad_order_ = os.environ.get("CONVNET_WGRAD_ORDER", "before")
         self.side_stream_ = None
         self._pending_updates = []     # [(edge, event on the main stream after its dgrad, held back?)]
@@ -113,12 +128,6 @@ class ConvNet(TrainLoopMixin):
         m = self.model_
         self.layers_ = [Layer.ChooseLayerClass(l) for l in m.layer]
         self.edges_ = [Edge.ChooseEdgeClass(e) for e in m.edge]
-        for e in self.edges_:
-            e.fused = self.fused
-            if isinstance(e, EdgeWithWeight):
-                e.weight_optimizer_.fused = self.fused
-                if e.bias_optimizer_ is not None:
-                    e.bias_optimizer_.fused = self.fused
         by_name = {e.GetName(): e for e in self.edges_}
         for e in self.edges_:
             if e.IsTied():
@@ -134,18 +143,16 @@ class ConvNet(TrainLoopMixin):
                     e.SetDest(l)
                     e.SetOutputChannels(l.GetNumChannels())
         self.Sort()
+        # the edges, the layers and their optimizers all switch on ``fused`` (fused host: the plain steps, a batch-normalised layer's
+        # gamma / beta steps included, are planned into the step's one multi launch, PlanFusedStep)
+        for x in (*self.edges_, *self.layers_):
+            x.fused = self.fused
+            for opt in (getattr(x, n, None) for n in ("weight_optimizer_", "bias_optimizer_", "gamma_optimizer_", "beta_optimizer_")):
+                if opt is not None:
+                    opt.fused = self.fused
         for l in self.layers_:
-            l.fused = self.fused
             if l.UseBatchNormalization():
                 self._check_batch_norm(l)
-                # fused host: the gamma / beta steps are planned into the step's one sgd_momentum_step_multi launch (PlanFusedStep)
-                l.gamma_optimizer_.fused = l.beta_optimizer_.fused = self.fused
-        for e in self.edges_:
-            if isinstance(e, MaxPoolEdge):
-                # the mask pair equals the reference's MaxPoolUndo only if backprop sees the raw maxima (edge.MaxPoolEdge)
-                d = e.GetDest()
-                e.mask_legal_ = d.dropprob_ == 0 and type(d) in (LinearLayer, ReLULayer)
-        for l in self.layers_:
             if not l.incoming_edge_:
                 self.input_layers_.append(l)
                 self.data_layers_.append(l)
@@ -171,6 +178,52 @@ class ConvNet(TrainLoopMixin):
             self.log(f"Layer {l.GetName()}: {y}x{x}")
             for e in l.outgoing_edge_:
                 e.SetImageSize(y, x, t)
+        self.PlanLayers()
+
+    def PlanLayers(self):
+        """Every layer's LayerPlan.  BuildNet ends with it; whoever changes a built graph by hand (a test) calls it again."""
+        self.plan_ = {l: self._plan_layer(l) for l in self.layers_}
+        # the metric accumulates on the device (GetLoss returns None) only for one output on a fused output entry: the counter is one number
+        self.metric_on_device_ = len(self.output_layers_) == 1 and self.plan_[self.output_layers_[0]].output_entry is not None
+
+    def _fused_down_scale(self, l):
+        return self.plan_[l].down_scale   # the ComputeDown post-scale planned for layer l, or None (the tests ask by layer)
+
+    def _plan_layer(self, l):
+        """The LayerPlan of layer l, from what BuildNet has fixed: the layer's class and dropout, its edge lists, the edges' classes,
+        bias kinds and block_backprop, the number of output layers.  Also sets the verdict on the max-pool mask pair on l's incoming
+        max-pool edges (the edges' own ``fused`` stays a live switch: MaxPoolEdge.MaskEligible)."""
+        fused, hidden = self.fused, not l.IsInput() and not l.IsOutput()
+        bn, logistic, scale = l.UseBatchNormalization(), isinstance(l, LogisticLayer), l.TrainDropoutScale()
+        for e in l.incoming_edge_:
+            if isinstance(e, MaxPoolEdge):
+                # the mask pair equals the reference's MaxPoolUndo only if backprop sees the raw maxima (edge.MaxPoolEdge)
+                e.mask_legal_ = l.dropprob_ == 0 and type(l) in (LinearLayer, ReLULayer)
+        # forward.  The only incoming edge's epilogue takes the bias, and the ReLU unless batch normalisation sits in between; a sigmoid
+        # is a pass of its own, a softmax layer takes the reference's calls
+        fuse_up = fused and len(l.incoming_edge_) == 1 and not isinstance(l, SoftmaxLayer) and l.incoming_edge_[0].CanFuseUp(l)
+        activate = not fused if bn else not l.IsInput() and (not fuse_up or logistic)
+        # output: softmax always; logistic and softmax-distribution for a single output without dropout whose loss and metric are the
+        # ones the entry computes.  Anything else runs the reference's calls
+        entry = None
+        if fused and l.IsOutput() and not l.IsInput():
+            single = len(self.output_layers_) == 1 and l.dropprob_ <= 0
+            if type(l) is SoftmaxLayer:
+                entry = Matrix.SoftmaxCEGradCorrect
+            elif single and logistic and (l.loss_function_, l.performance_metric_) == ("CROSS_ENTROPY_BINARY", "CLASSIFICATION_BINARY"):
+                entry = Matrix.LogisticCEGradCorrect
+            elif single and isinstance(l, SoftmaxDistLayer) and l.loss_function_ == l.performance_metric_ == "CROSS_ENTROPY_MULTINOMIAL_DISTRIBUTED":
+                entry = Matrix.SoftmaxDistCEGrad
+        # backward.  The reference applies dropout' and ReLU' after ALL outgoing edges have accumulated (src/convnet.cc:390-404), so they
+        # ride in a ComputeDown epilogue only with exactly one edge; a max-pool undo masks but does not scale
+        down_scale = None
+        if fused and hidden and l.is_relu and len(l.outgoing_edge_) == 1:
+            e = l.outgoing_edge_[0]
+            if e.can_fuse_mask and not e.IsBackPropBlocked() and not l.store_dropout_noise_ and not (isinstance(e, MaxPoolEdge) and scale != 1.0):
+                down_scale = scale
+        return LayerPlan(fuse_relu=(l.is_relu and not bn) if fuse_up else None, bn_relu=(fused and l.is_relu) if bn else None,
+                         activate=activate, output_entry=entry, logistic_dropout=fused and logistic and not l.IsInput() and l.dropprob_ > 0,
+                         dropout_scale=scale, down_scale=down_scale, logistic_deriv=fused and logistic and hidden)
 
     @staticmethod
     def _check_batch_norm(l):
@@ -280,65 +333,22 @@ class ConvNet(TrainLoopMixin):
         return sum(n for _, n in self.edge_slices_.values())
 
     # ---- fprop / bprop: src/convnet.cc:355-405 ---------------------------------------------------------
-    def _can_fuse_up(self, l):
-        if not self.fused or len(l.incoming_edge_) != 1 or isinstance(l, SoftmaxLayer):
-            return False
-        e = l.incoming_edge_[0]
-        if isinstance(e, ConvEdge):
-            return e.has_no_bias_ or e.shared_bias_
-        if isinstance(e, LocalEdge):
-            return True            # localUpBiasAct: the (per-column) bias and the ReLU in the kernel's epilogue
-        if isinstance(e, ResponseNormEdge):
-            return l.is_relu       # the ReLU of an rnorm-fed layer rides in the rnorm kernel; other activations do not
-        return isinstance(e, FCEdge)
-
-    def _fused_output(self, l):
-        """Which fused output entry (activation + loss derivative + metric accumulated on the device) serves output layer l:
-        "softmax" (softmax_ce_grad_correct), "logistic" (logistic_ce_grad_correct), "softmax_dist" (softmax_dist_ce_grad) or None.
-        The last two hold for a single output without dropout whose loss and metric are the ones the entry computes; anything
-        else runs the reference's calls."""
-        if not self.fused or not l.IsOutput() or l.IsInput():
-            return None
-        if type(l) is SoftmaxLayer:
-            return "softmax"
-        if len(self.output_layers_) != 1 or l.dropprob_ > 0:
-            return None
-        if isinstance(l, LogisticLayer) and (l.loss_function_, l.performance_metric_) == ("CROSS_ENTROPY_BINARY", "CLASSIFICATION_BINARY"):
-            return "logistic"
-        if isinstance(l, SoftmaxDistLayer) and l.loss_function_ == l.performance_metric_ == "CROSS_ENTROPY_MULTINOMIAL_DISTRIBUTED":
-            return "softmax_dist"
-        return None
-
-    @staticmethod
-    def _dropout_scale(l):
-        return 1.0 / (1 - l.dropprob_) if (l.dropprob_ > 0 and l.dropout_scale_up_at_train_time_) else 1.0
-
     def Fprop(self, train):
         for l in self.layers_:
-            fused_act = self._can_fuse_up(l)
-            logistic = isinstance(l, LogisticLayer)   # its edge's epilogue takes the bias only: the sigmoid is a pass of its own
-            dropped = False
-            bn = l.UseBatchNormalization()
+            p = self.plan_[l]
             for e in l.incoming_edge_:
-                src = e.GetSource()
                 overwrite = l.AddOrOverwriteState(e.GetDestSliceName())
-                # batch normalisation sits between the edge and the activation: the bias may ride in the edge's epilogue, the ReLU not
-                e.ComputeUp(src.GetState(), l.GetState(), overwrite, train, fuse_relu=((l.is_relu and not bn) if fused_act else None))
-            if bn:
-                # src/convnet.cc:382-384; the fused entry applies the ReLU in the same pass
-                l.ApplyBatchNormalization(train, relu=self.fused and l.is_relu)
-                if not self.fused:
-                    l.ApplyActivation()
-            elif not l.IsInput() and (not fused_act or logistic):
-                if train and self._fused_output(l) is not None:
-                    self._logits_pending.add(l)   # activation + CE derivative + metric are fused in ComputeDeriv
-                elif self.fused and logistic and train and l.dropprob_ > 0:
-                    l.GetState().LogisticDropout(l.dropprob_, self._dropout_scale(l))   # (a logistic layer never stores its noise)
-                    dropped = True
-                else:
-                    l.ApplyActivation()
-            if not dropped:
-                l.ApplyDropout(train)
+                e.ComputeUp(e.GetSource().GetState(), l.GetState(), overwrite, train, fuse_relu=p.fuse_relu)
+            if p.bn_relu is not None:
+                l.ApplyBatchNormalization(train, relu=p.bn_relu)   # src/convnet.cc:382-384
+            if train and p.output_entry is not None:
+                self._logits_pending.add(l)
+            elif train and p.logistic_dropout:
+                l.GetState().LogisticDropout(l.dropprob_, p.dropout_scale)
+                continue
+            elif p.activate:
+                l.ApplyActivation()
+            l.ApplyDropout(train)
 
     def _bprop_edge(self, output, input, edge, fuse_mask=None):
         # ConvNet::Bprop(output, input, edge), src/convnet.cc:362-375
@@ -357,13 +367,9 @@ class ConvNet(TrainLoopMixin):
         owner = edge.tied_edge_ if edge.IsTied() else edge
 
         def dgrad():
-            if input.IsInput():
-                return
-            overwrite = input.AddOrOverwriteDeriv(edge.GetSourceSliceName())
-            if fuse_mask is not None:
+            if not input.IsInput():
+                overwrite = input.AddOrOverwriteDeriv(edge.GetSourceSliceName())
                 edge.ComputeDown(output.GetDeriv(), input.GetState(), output.GetState(), input.GetDeriv(), overwrite, fuse_mask=fuse_mask)
-            else:
-                edge.ComputeDown(output.GetDeriv(), input.GetState(), output.GetState(), input.GetDeriv(), overwrite)
 
         if side and self.overlap_wgrad_ and isinstance(edge, EdgeWithWeight):
             # weight gradient on the second stream, behind everything enqueued so far (the derivative it reads); the all-reduce of
@@ -425,28 +431,14 @@ class ConvNet(TrainLoopMixin):
                 edge.UpdateWeights()
         self._pending_updates = keep
 
-    def _fused_down_scale(self, l):
-        """If layer l's dropout' + ReLU' can ride in its only outgoing edge's ComputeDown epilogue, return the
-        scale to apply (else None).  The reference applies them after ALL outgoing edges have accumulated
-        (src/convnet.cc:390-404), so this is only legal with exactly one edge."""
-        if not self.fused or l.IsInput() or l.IsOutput() or not l.is_relu or len(l.outgoing_edge_) != 1:
-            return None
-        e = l.outgoing_edge_[0]
-        if not e.can_fuse_mask or e.IsBackPropBlocked() or l.store_dropout_noise_:
-            return None
-        scale = 1.0 / (1 - l.dropprob_) if (l.dropprob_ > 0 and l.dropout_scale_up_at_train_time_) else 1.0
-        if isinstance(e, MaxPoolEdge) and scale != 1.0:
-            return None
-        return scale
-
     def Bprop(self):
         for l in reversed(self.layers_):
-            scale = self._fused_down_scale(l)
+            p = self.plan_[l]
             for e in l.outgoing_edge_:
-                self._bprop_edge(e.GetDest(), l, e, fuse_mask=scale)
-            if self.fused and isinstance(l, LogisticLayer) and not l.IsInput() and not l.IsOutput():
-                l.GetDeriv().LogisticDerivScaled(l.GetState(), self._dropout_scale(l))   # dropout' and logistic' in one pass
-            elif scale is None:   # else dropout' and ReLU' were applied by the edge's epilogue
+                self._bprop_edge(e.GetDest(), l, e, fuse_mask=p.down_scale)
+            if p.logistic_deriv:
+                l.GetDeriv().LogisticDerivScaled(l.GetState(), p.dropout_scale)   # dropout' and logistic' in one pass
+            elif p.down_scale is None:   # else dropout' and ReLU' were applied by the edge's epilogue
                 l.ApplyDerivativeofDropout()
                 if not l.IsInput() and not l.IsOutput():
                     l.ApplyDerivativeOfActivation()
@@ -464,9 +456,7 @@ class ConvNet(TrainLoopMixin):
         for l in self.output_layers_:
             if l in self._logits_pending:
                 self._logits_pending.discard(l)
-                entry = {"softmax": Matrix.SoftmaxCEGradCorrect, "logistic": Matrix.LogisticCEGradCorrect,
-                         "softmax_dist": Matrix.SoftmaxDistCEGrad}[self._fused_output(l)]
-                entry(l.GetState(), l.GetData(), l.GetState(), l.GetDeriv(), self.correct_accum_, l.loss_function_weight_)
+                self.plan_[l].output_entry(l.GetState(), l.GetData(), l.GetState(), l.GetDeriv(), self.correct_accum_, l.loss_function_weight_)
             else:
                 l.ComputeDeriv()
 
@@ -476,16 +466,12 @@ class ConvNet(TrainLoopMixin):
         per-step sync; ReadCorrectCount) and GetLoss returns None — unless some output layer did not take a fused output path
         (e.g. a SQUARED_ERROR linear output) or there are several outputs: the on-device counter is one number, so those nets
         report per layer through the reference's own call, like the unfused path."""
-        if len(self.output_layers_) == 1 and self._fused_output(self.output_layers_[0]) is not None:
-            return None
-        return [l.GetPerformanceMetric() for l in self.output_layers_]
+        return None if self.metric_on_device_ else [l.GetPerformanceMetric() for l in self.output_layers_]
 
     def TimestampModel(self):
         """ConvNet::TimestampModel (src/convnet.cc:830-838): stamp the run — checkpoints go to <dir>/<name>_<timestamp>.h5 — append
         the stamp to the model, write the stamped model as <dir>/<name>_<timestamp>.pbtxt and name the two log files."""
-        import os
         import time
-        from . import pbtxt
         ts = time.strftime("%Y%m%d%H%M%S")
         while ts in self.model_.timestamp:   # a resume within the same second must not reuse the name
             ts += "_"
@@ -575,7 +561,6 @@ class ConvNet(TrainLoopMixin):
 
     def GetCheckpointFilename(self):
         # src/convnet.cc:651-657: <checkpoint_dir>/<name>_<timestamp>.h5
-        import os
         m = self.model_
         ts = m.timestamp[-1] if m.timestamp else ""
         return os.path.join(m.checkpoint_dir, f"{m.name}_{ts}.h5")
@@ -583,7 +568,6 @@ class ConvNet(TrainLoopMixin):
     def Save(self, output_file=None):
         """HDF5 file in the reference's layout: every edge's weight / bias / gradient_history datasets and step attributes,
         plus ``__lr_reduce_counter__`` and ``__current_iter__``; written to ``<name>temp`` and renamed (convnet.cc:666-684)."""
-        import os
         from . import hdf5io
         if output_file is None:
             # ConvNet::Save() (src/convnet.cc:659-667): the checkpoint, then — with Polyak averaging on — the AVERAGED weights

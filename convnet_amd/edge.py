@@ -4,7 +4,8 @@ ComputeUp / ComputeDown / ComputeOuter / UpdateWeights contract, same parameter 
 
 Up-down-sample / RGB->YUV edges are out of hot-path scope.
 ``fused`` selects the library's fused entry points (conv+bias+ReLU epilogue, one-pass bias
-gradient); the unfused path issues exactly the reference's Matrix-call sequence.
+gradient); the unfused path issues exactly the reference's Matrix-call sequence.  What an edge class can
+fuse it says itself (``CanFuseUp``, ``can_fuse_mask``); which of it a net uses is ConvNet's per-layer plan.
 """
 import math
 import os
@@ -21,7 +22,11 @@ def _divup(x, y):
 
 
 class Edge:
-    can_fuse_mask = False   # ComputeDown(fuse_mask=...) supported
+    can_fuse_mask = False   # ComputeDown(fuse_mask=post_scale) supported; the other classes are never handed one
+
+    def CanFuseUp(self, dest):
+        """Whether ComputeUp(fuse_relu=...) can apply layer ``dest``'s bias and activation in its epilogue."""
+        return False
 
     @staticmethod
     def ChooseEdgeClass(edge_config):
@@ -417,14 +422,6 @@ class EdgeWithWeight(Edge):
         if not shared:
             deriv_output.SumRows(db, scale_targets, scale_outputs)
             return
-        if self.fused and frames is None:
-            # one pass: (N*My*Mx, F) column sums == the reference's two-step SumRows.  (Nothing reaches this today: the only caller
-            # with a shared bias, ConvEdge.ComputeOuter, takes ConvOutpBias first whenever it is fused.)
-            cols = deriv_output.GetCols()
-            deriv_output.Reshape(-1, shared)
-            deriv_output.SumRows(db, scale_targets, scale_outputs)
-            deriv_output.Reshape(-1, cols)
-            return
         db_temp = Matrix()
         Matrix.GetTemp(1, deriv_output.GetCols(), db_temp)
         deriv_output.SumRows(db_temp, 0, 1)
@@ -506,6 +503,9 @@ class ConvEdge(EdgeWithWeight):
         if not self.is_tied_ and self.shared_bias_ and not self.has_no_bias_:
             Matrix.RegisterTempMemory(self.conv_desc_.num_output_channels * self._num_modules(), "shared bias")
         super().SetGradMemory(p, hist, hist2)
+
+    def CanFuseUp(self, dest):
+        return self.has_no_bias_ or self.shared_bias_   # (the epilogue's bias is one value per filter)
 
     def _bias_view(self):
         """(shared, frames) of _add_bias / _bias_grad for this edge."""
@@ -597,6 +597,9 @@ class LocalEdge(EdgeWithWeight):
         return (d.num_output_channels, self._num_modules(),
                 (d.num_output_channels, d.kernel_size_x, d.kernel_size_y, d.num_input_channels * self.num_modules_y_ * self.num_modules_x_))
 
+    def CanFuseUp(self, dest):
+        return True   # localUpBiasAct: the (per-column) bias and the ReLU in the kernel's epilogue
+
     def ComputeUp(self, input, output, overwrite, train=True, fuse_relu=None):
         scale_targets = 0 if overwrite else 1
         if fuse_relu is not None:
@@ -605,7 +608,8 @@ class LocalEdge(EdgeWithWeight):
         Matrix.LocalUp(input, self._w(), output, self.conv_desc_, scale_targets)
         self._add_bias(output)
 
-    def ComputeDown(self, deriv_output, input, output, deriv_input, overwrite):
+    def ComputeDown(self, deriv_output, input, output, deriv_input, overwrite, fuse_mask=None):
+        assert fuse_mask is None
         Matrix.LocalDown(deriv_output, self._w(), deriv_input, self.conv_desc_, 0 if overwrite else 1)
 
     def ComputeOuter(self, input, deriv_output):
@@ -628,6 +632,9 @@ class FCEdge(EdgeWithWeight):
 
     def GetDescription(self):
         return f"{self.name_} Fully Connected :{self.image_size_y_}-{self.image_size_x_}-{self.num_input_channels_}:{self.num_output_channels_}"
+
+    def CanFuseUp(self, dest):
+        return True
 
     def ComputeUp(self, input, output, overwrite, train=True, fuse_relu=None):
         # src/fc_edge.cc:51-61
@@ -753,7 +760,7 @@ class MaxPoolEdge(_PoolEdge):
 
     def __init__(self, c):
         super().__init__(c)
-        self.mask_legal_ = False   # set by ConvNet.BuildNet from the destination layer (see the class docstring)
+        self.mask_legal_ = False   # set by ConvNet's per-layer plan from the destination layer (see the class docstring)
         self.mask_ = None
         self.mask_for_ = None   # (input data pointer, output data pointer, batch) of the ComputeUp that wrote mask_
         self.mask_refused_ = set()   # (batch, input size, output size) the mask kernel refused: no mask, no call from then on
@@ -798,7 +805,8 @@ class AvgPoolEdge(_PoolEdge):
             raise SystemExit(" In AvgPoolEdge::ComputeUp() : some other layer is writing to this layer's output as well. Not implemented.")
         Matrix.ConvAvgPool(input, output, self.conv_desc_)
 
-    def ComputeDown(self, deriv_output, input, output, deriv_input, overwrite):
+    def ComputeDown(self, deriv_output, input, output, deriv_input, overwrite, fuse_mask=None):
+        assert fuse_mask is None
         Matrix.ConvAvgPoolUndo(deriv_output, deriv_input, self.conv_desc_, 0 if overwrite else 1)
 
 
@@ -819,6 +827,9 @@ class ResponseNormEdge(Edge):
         # (int) truncation of a *float* product, as in C++ (src/response_norm_edge.cc:37-38)
         self.num_filters_response_norm_ = int(np.float32(self.frac_of_filters_response_norm_) * np.float32(self.num_input_channels_))
 
+    def CanFuseUp(self, dest):
+        return dest.is_relu   # the ReLU of an rnorm-fed layer rides in the rnorm kernel; other activations do not
+
     def ComputeUp(self, input, output, overwrite, train=True, fuse_relu=None):
         # fuse_relu=True: the destination layer's ReLU (layer.cc:549) is applied by the same kernel
         if self.image_size_t_ > 1:   # src/response_norm_edge.cc:46-50: frame by frame
@@ -828,7 +839,8 @@ class ResponseNormEdge(Edge):
         Matrix.ConvResponseNormCrossMap(input, output, self.num_input_channels_, self.num_filters_response_norm_,
                                         self.add_scale_, self.pow_scale_, self.blocked_, relu=bool(fuse_relu))
 
-    def ComputeDown(self, deriv_output, input, output, deriv_input, overwrite):
+    def ComputeDown(self, deriv_output, input, output, deriv_input, overwrite, fuse_mask=None):
+        assert fuse_mask is None
         if self.image_size_t_ > 1:
             Matrix.ConvResponseNormCrossMapUndo3D(deriv_output, input, output, deriv_input, self.num_input_channels_,
                                                   self.num_filters_response_norm_, self.add_scale_, self.pow_scale_, self.blocked_,

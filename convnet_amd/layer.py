@@ -237,10 +237,14 @@ class Layer:
         else:
             self.ApplyDropoutAtTestTime()
 
+    def TrainDropoutScale(self):
+        """What the units kept at train time are scaled by: 1 / (1 - p) with dropout and scale-up at train time, else 1."""
+        return 1.0 / (1 - self.dropprob_) if (self.dropprob_ > 0 and self.dropout_scale_up_at_train_time_) else 1.0
+
     def ApplyDropoutAtTrainTime(self):
         # src/layer.cc:367-397
         if self.dropprob_ > 0:
-            scale = 1.0 / (1 - self.dropprob_) if self.dropout_scale_up_at_train_time_ else 1.0
+            scale = self.TrainDropoutScale()
             if self.store_dropout_noise_:
                 self.dropout_noise_.SampleBernoulli(1 - self.dropprob_)
                 self.dropout_noise_.Mult(scale)
@@ -254,7 +258,7 @@ class Layer:
             if self.store_dropout_noise_:
                 self.deriv_.Mult(self.dropout_noise_)
             elif self.dropout_scale_up_at_train_time_:
-                self.deriv_.Mult(1.0 / (1 - self.dropprob_))
+                self.deriv_.Mult(self.TrainDropoutScale())
 
     def ApplyDropoutAtTestTime(self):
         if self.dropprob_ > 0 and not self.dropout_scale_up_at_train_time_:

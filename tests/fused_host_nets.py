@@ -1,4 +1,4 @@
-"""Small nets that reach each per-layer choice of ConvNet(fused=True)'s host (``_can_fuse_up``, ``_fused_down_scale``, the max-pool
+"""Small nets that reach each per-layer choice of ConvNet(fused=True)'s host (the rows of ``convnet.LayerPlan``, the max-pool
 mask path of MaxPoolEdge): dropout on pool, conv, 1x1 and rnorm-fed layers, linear layers, refused pool geometries, layers with two
 outgoing or two incoming edges.  Inputs <= 35 x 35, channels <= 48.  Used by tests/test_fused_host_configs_{cpu,gpu}.py."""
 from convnet_amd import models

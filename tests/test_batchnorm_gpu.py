@@ -244,12 +244,14 @@ def test_test_mode_forward_uses_the_running_statistics(M):
         l = net.GetLayerByName(name)
         cls = l.__class__
         l.__class__, l.batch_normalize_ = LinearLayer, False    # the same pass without BN and ReLU: the pre-BN activations
+        net.PlanLayers()
         for k in net.layers_:
             k.ResetAddOrOverwrite()
         net.Fprop(False)
         C = l.GetNumChannels()
         x = l.GetState().ToNumpy().reshape(C, -1)
         l.__class__, l.batch_normalize_ = cls, True
+        net.PlanLayers()
         for k in net.layers_:
             k.ResetAddOrOverwrite()
         net.Fprop(False)

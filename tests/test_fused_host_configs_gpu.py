@@ -1,4 +1,4 @@
-"""GPU: the host's choice of entry point per layer configuration (ConvNet(fused=True): ``_can_fuse_up``, ``_fused_down_scale``, the
+"""GPU: the host's choice of entry point per layer configuration (ConvNet(fused=True): its per-layer ``LayerPlan``, the
 max-pool mask path) on the small nets of tests/fused_host_nets.py — dropout on pool, conv, 1x1 and rnorm-fed layers, linear layers,
 refused pool geometries, two outgoing / two incoming edges, and the reference's NIN model with its real dropout layers.
 
