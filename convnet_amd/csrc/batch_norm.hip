@@ -252,8 +252,6 @@ Seg plan(int H, int C) {
   return Seg{H, (int)((H + L - 1) / L), (int)L};
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 int apply_blocks(size_t items) { return (int)std::min<size_t>((items + kThreads - 1) / kThreads, 8192); }
 
 bool is_vec(const cudamat* m, int C) { return m && m->on_device && (int)numel(m) == C; }

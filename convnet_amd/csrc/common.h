@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 
@@ -119,5 +120,6 @@ void wg_batch_end();
 
 inline int divup(int a, int b) { return (a + b - 1) / b; }
 inline size_t numel(const cudamat* m) { return (size_t)m->size[0] * (size_t)m->size[1]; }
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }   // (a null pointer counts as aligned)
 
 }  // namespace chip

@@ -22,8 +22,6 @@ inline int blocks_for(size_t work_items) {
   return (int)b;
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // out[i] = f(i, a[i], b[i]); a/b may alias out.  Vector body + scalar tail.
 template <typename F>
 __global__ void map2_kernel(float* __restrict__ out, const float* a, const float* b, size_t n, bool vec, F f) {
@@ -50,7 +48,7 @@ int map2(cudamat* out, const cudamat* a, const cudamat* b, F f) {
   if (!a->on_device || !out->on_device || (b && !b->on_device)) return ERROR_NOT_ON_DEVICE;
   if (numel(out) != n || (b && numel(b) != n)) return ERROR_INCOMPATIBLE_DIMENSIONS;
   if (n == 0) return 0;
-  const bool vec = al16(out->data_device) && al16(a->data_device) && (!b || al16(b->data_device));
+  const bool vec = aligned16(out->data_device) && aligned16(a->data_device) && (!b || aligned16(b->data_device));
   KernelTimer timer("map2_kernel", "elementwise", 0.0, 4.0 * n * (b ? 3 : 2));
   hipLaunchKernelGGL(map2_kernel<F>, dim3(blocks_for(n / 4 + 1)), dim3(kThreads), 0, stream(), out->data_device,
                      a->data_device, b ? b->data_device : nullptr, n, vec, f);
@@ -259,7 +257,7 @@ int add_row(cudamat* mat, cudamat* vec, cudamat* target, float mult) {
   if (mat->size[1] != vec->size[1] || vec->size[0] != 1 || mat->size[0] != target->size[0] || mat->size[1] != target->size[1])
     return ERROR_INCOMPATIBLE_DIMENSIONS;
   const size_t n = numel(mat);
-  const bool v4 = (mat->size[0] & 3) == 0 && al16(mat->data_device) && al16(target->data_device);
+  const bool v4 = (mat->size[0] & 3) == 0 && aligned16(mat->data_device) && aligned16(target->data_device);
   hipLaunchKernelGGL(add_row_kernel, dim3(blocks_for(n / 4 + 1)), dim3(kThreads), 0, stream(), target->data_device, mat->data_device,
                      vec->data_device, mat->size[0], n, mult, v4);
   return launch_status();
@@ -368,7 +366,7 @@ inline int rows_normlimit(float* g, float* w_in, float* w_out, float* h, int row
   float* partial = static_cast<float*>(workspace(sizeof(float) * ((size_t)nchunks * rows + rows)));
   float* factor = partial + (size_t)nchunks * rows;
   dim3 grid(divup(rows, 256), nchunks);
-  const bool v4 = (rows & 3) == 0 && al16(w_in) && (!do_sgd || (al16(g) && al16(h)));
+  const bool v4 = (rows & 3) == 0 && aligned16(w_in) && (!do_sgd || (aligned16(g) && aligned16(h)));
   // (one timer over the three launches: the fused SGD + row-norm pass reads g, w, h, writes h, w, then re-reads and re-writes w)
   KernelTimer timer(do_sgd ? "rows_sq_kernel<sgd> + row_scale_kernel" : "rows_sq_kernel + row_scale_kernel", do_sgd ? "sgd_normlimit" : "normlimit", 0.0,
                     4.0 * (double)rows * cols * (do_sgd ? 7 : 3));
@@ -920,7 +918,7 @@ StepItem<Op> step_item(cudamat* const (&mats)[Op::N], const Op& op) {
   t.vec = 1;
   for (int k = 0; k < Op::N; ++k) {
     t.p[k] = mats[k]->data_device;
-    t.vec &= al16(t.p[k]) ? 1 : 0;
+    t.vec &= aligned16(t.p[k]) ? 1 : 0;
   }
   t.n = numel(mats[1]);
   t.op = op;

@@ -1,6 +1,7 @@
 // Shared device helpers of the gather-GEMM translation units (gather_gemm.hip, patch_gemm.hip): launch parameter blocks, the
 // exact bf16 three-way split (Split8), the tile selection and the block-tile write-out.  gfx950 only.
 #pragma once
+#include <cmath>
 #include <cstring>
 #include <type_traits>
 
@@ -594,5 +595,63 @@ bool wgw_try(WGParams& p, bool vec, bool split_products, const char* op, double 
 
 // split-K second stage (gather_gemm.hip): dst = scaleTargets*dst + sum of the slabs, with the fused bias / ReLU / mask options of p
 void gg_reduce_launch(const GGParams& p, size_t dst_elems, int splits, const char* op);
+
+// ---- the launch plans' two estimates, shared by gg_launch_cfg (gather_gemm.hip) and patch_run / wide_plan (patch_gemm.hip); host only ----
+// Estimated time of a launch cut into sp K-ranges.  Every block of a launch takes the same time, so a grid of b blocks on `slots`
+// resident-block slots runs ceil(b / slots) rounds and wastes the empty part of the last one (338 tiles on 512 slots = 66 % busy;
+// 3 K-splits = 1014 blocks = 99 %): rounds * (work per block) + the slab reduce's traffic.  tile_flops: one whole-K tile.
+inline double gg_split_time(int tiles, int sp, double slots, double tile_flops, double block_rate, size_t dst_elems) {
+  const double rounds = std::ceil(tiles * (double)sp / slots);
+  double t = rounds * (tile_flops / sp) / block_rate;
+  if (sp > 1) t += sizeof(float) * (double)dst_elems * (2.0 * sp + 1) / 4.0e12 + 4e-6;
+  return t;
+}
+// Split-K factor by that estimate (a new best must win by 3 %); needs a launch that owns the whole destination (dst_elems > 0).  A
+// K-range keeps at least 8 of the `kchunks` BK-deep chunks and one of the `units` it is cut in (gg_kernel / ggp_kernel: the chunks
+// themselves; the patch kernels: superchunks).  *best_time: the estimate of the returned factor.
+inline int gg_split_k(int tiles, double slots, double tile_flops, double block_rate, size_t dst_elems, int kchunks, int units,
+                      double* best_time = nullptr) {
+  int splits = 1;
+  double best_t = 1e30;
+  if (dst_elems > 0 && kchunks >= 16)
+    for (int sp = 1; sp <= 16 && kchunks / sp >= 8 && units / sp >= 1; ++sp) {
+      const double t = gg_split_time(tiles, sp, slots, tile_flops, block_rate, dst_elems);
+      if (t < best_t * 0.97) {
+        best_t = t;
+        splits = sp;
+      }
+    }
+  if (best_time) *best_time = best_t;
+  return splits;
+}
+// Tail split: more tiles than slots and a partial last round (conv2 fprop: 1352 tiles = 2.64 rounds of 512).  Cut only the last
+// round's tiles into s K-ranges so that round is full as well: 2 + ceil(328*3/512)/3 = 2.67 rounds instead of 3.
+inline bool gg_partial_last_round(int tiles, int slots, int kchunks) { return tiles > slots && tiles % slots != 0 && kchunks >= 32; }
+// ... the s with the cheapest last round, in units of one whole-K round (today's cost: 1; a 5 % gain is required), or 1: leave it
+inline int gg_tail_split(int tiles, int slots, double tile_flops, double block_rate, int tile_elems, int kchunks) {
+  const int rem = tiles - (tiles / slots) * slots;
+  const double tile_bytes = sizeof(float) * (double)tile_elems;
+  const double t_round = tile_flops / block_rate;   // one whole-K block
+  double best = 0.95;
+  int best_s = 1;
+  for (int s = 2; s <= 8 && kchunks / s >= 8; ++s) {
+    const double cost = std::ceil(rem * (double)s / slots) / s + (rem * (s + 1.0) * tile_bytes / 4.0e12 + 6e-6) / t_round;
+    if (cost < best) {
+      best = cost;
+      best_s = s;
+    }
+  }
+  return best_s;
+}
+// ... and the launch's tail_* fields for s K-ranges of a reduction of `units` (chunks / superchunks); the pieces' sums come from workspace()
+inline void gg_set_tail(GGParams& p, int tiles, int slots, int units, int s, int tile_elems) {
+  const int full = (tiles / slots) * slots, rem = tiles - full;
+  p.tail_first = full;
+  p.tail_cps = divup(units, s);
+  p.tail_splits = divup(units, p.tail_cps);
+  p.tail_tf8 = full / 8;
+  p.tail_tt8 = divup(rem * p.tail_splits, 8);
+  p.tail_partial = static_cast<float*>(workspace(sizeof(float) * (size_t)rem * p.tail_splits * tile_elems));
+}
 
 }  // namespace chip

@@ -1391,10 +1391,12 @@ namespace {
 
 constexpr int kTargetBlocks = 512;  // ~2 resident blocks per CU
 
-// tag + algorithmic flops of the call being dispatched (consumed by KernelTimer in the launchers)
-const char* t_op = "";
-double t_flops = 0.0;
-double t_exec = 0.0;   // MFMA work the launch issues when it differs from the algorithmic t_flops (0 = same)
+// Timer arguments of the call being dispatched, for the KernelTimer of its GEMM launch: the op tag, the call's algorithmic flops, and the
+// MFMA work the launch issues when that differs (0 = same).
+struct GGTimer {
+  const char* op;
+  double flops, exec;
+};
 
 // Issue-priority scheme of gg_kernel's main loop (CONVNET_GG_PRIO overrides, for A/B runs).  Measured per layer (AlexNet, N=256):
 // raising the STAGING phase (2) beats raising the MFMA phase (1, round 1's choice) and no priority (0) by ~1 % — the co-resident
@@ -1418,7 +1420,7 @@ inline bool wg_split_mode() {
   return v < 0 ? gg_split_mode() : v != 0;
 }
 
-// ggp_kernel exists for the tile shapes whose B stage has 64 sixteen-byte pieces per k-row (gg_run picks those for R > 32).
+// ggp_kernel exists for the tile shapes whose B stage has 64 sixteen-byte pieces per k-row (gg_tile picks those for R > 32).
 inline bool ggp_shape_ok(int R, int KC) { return gg_producer_mode() && R > 32 && KC > 0 && KC % BK == 0 && !CHIP_DIAG_KNOB("CONVNET_GG_ROWS64", 0); }
 
 template <typename Kern>
@@ -1434,25 +1436,121 @@ inline int wg_prio_mode() {
   return CHIP_DIAG_KNOB("CONVNET_WG_PRIO", 2);
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 template <typename Kern>
 void allow_big_lds(Kern kern, size_t lds) {
   // >64 KiB of dynamic LDS needs an explicit opt-in once per kernel.
   if (lds > 64 * 1024) CHIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 }
 
-// Launch one gather-GEMM.  `dst_elems` > 0 means the launch covers the whole destination matrix,
-// which makes a split-K (slab per split + deterministic reduce) legal.
+// The block tile of gg_kernel / ggp_kernel: WR x WC waves of MT 32-row MFMA tiles by CW columns, ROWS = WR * MT * 32.  Five are built.
+template <int WR_, int WC_, int MT_, int CW_>
+struct GGTileOf {
+  static constexpr int WR = WR_, WC = WC_, MT = MT_, CW = CW_;
+};
+struct GGTile {
+  int WR, WC, MT, CW;
+  int rows() const { return WR * MT * 32; }
+};
+// Row tile by problem height: 128 rows (2x2 waves of 64x128), 96 rows (4 waves of 96x64: conv1 fprop, conv2 dgrad — vector path only:
+// the 96-row 6-wave config measured 68 TFLOP/s vs 106 for the 128-row one, and the scalar path runs them 25 % padded on 128 rows), 64
+// and 32 rows for small layers.  An FC layer at a small per-GPU batch (strong scaling of a global batch: 128 / 64 / 32 images per GPU)
+// is a GEMM with <= 128 columns, bound by streaming the weight matrix once: four waves stacked along the rows, one 64-column
+// wave-column, so a 32-image batch pads 2x instead of 8x and every weight row still reaches LDS with 16-byte pieces (`skinny`).
+inline GGTile gg_tile(int R, bool vec, bool skinny) {
+  if (skinny && vec && !CHIP_DIAG_KNOB("CONVNET_GG_NO_SKINNY", 0)) return {4, 1, 1, 64};
+  if (CHIP_DIAG_KNOB("CONVNET_GG_ROWS64", 0)) return {2, 2, 1, 128};   // experiment knob: 64-row tiles everywhere
+  if (R > 96 || (R > 64 && !vec)) return {2, 2, 2, 128};
+  if (R > 64) return {1, 4, 3, 64};
+  if (R > 32) return {2, 2, 1, 128};
+  return {1, 4, 1, 128};
+}
+// fn(GGTileOf<...>{}) for the built tile that `t` names
+template <typename Fn>
+void gg_with_tile(const GGTile& t, Fn fn) {
+  if (t.WR == 4) fn(GGTileOf<4, 1, 1, 64>{});
+  else if (t.MT == 2) fn(GGTileOf<2, 2, 2, 128>{});
+  else if (t.MT == 3) fn(GGTileOf<1, 4, 3, 64>{});
+  else if (t.WR == 2) fn(GGTileOf<2, 2, 1, 128>{});
+  else fn(GGTileOf<1, 4, 1, 128>{});
+}
+// Row-tile height of an R-row problem on the producer-wave kernels, which are vector-path only (the pre-split filter planes are laid
+// out per row tile of this height, filter_planes_rt_kernel; conv_down_impl sizes its arena by it on the scalar path as well).
+inline int gg_tile_rows(int R) { return gg_tile(R, true, false).rows(); }
+
+// Dynamic LDS of the builds: `stages` A + B stages (gg_kernel 2, ggp_kernel 3); ggp_kernel's pre-split build keeps A as bf16 planes.
+template <int WR, int WC, int MT, int CW, bool AK>
+constexpr size_t gg_lds(int stages) {
+  constexpr int ROWS = WR * MT * 32;
+  return sizeof(float) * stages * ((AK ? ROWS * (BK + 4) : BK * ROWS) + WC * BK * CW);
+}
+template <int WR, int WC, int MT, int CW>
+constexpr size_t ggp_pre_lds() {
+  return sizeof(float) * 3 * (6 * (WR * MT * 32) * 4 + WC * BK * CW);
+}
+// ggp_kernel exists for r-contiguous A and 64 sixteen-byte pieces per k-row of the B stage
+template <int WC, int CW, bool AK>
+constexpr bool kHasProducer = !AK && WC * (CW / 4) == 64;
+
+// resident-block slots of the three ggp_kernel builds of a tile
+template <int WR, int WC, int MT, int CW>
+int ggp_slots(bool split, bool pre) {
+  constexpr int threads = WR * WC * 64 + 64;
+  static const int pslots_s = resident_slots(ggp_kernel<WR, WC, MT, CW, true>, threads, gg_lds<WR, WC, MT, CW, false>(3));
+  static const int pslots_p = resident_slots(ggp_kernel<WR, WC, MT, CW, true, true>, threads, ggp_pre_lds<WR, WC, MT, CW>());
+  static const int pslots_f = resident_slots(ggp_kernel<WR, WC, MT, CW>, threads, gg_lds<WR, WC, MT, CW, false>(3));
+  return split ? (pre ? pslots_p : pslots_s) : pslots_f;
+}
+
+template <typename Kern>
+void gg_launch_kernel(Kern kern, dim3 grid, int threads, size_t lds, const GGParams& p, const GGClassTable& ct) {
+  allow_big_lds(kern, lds);
+  hipLaunchKernelGGL(kern, grid, dim3(threads), lds, stream(), p, ct);
+}
+
 static const GGClassTable kNoClasses = {};
+
+// The launch of one gather-GEMM grid, single problem (ct = kNoClasses) or stride classes: picks among the seven builds — ggp_kernel
+// split + pre-split A, split, fp32 (p.KC > 0); gg_kernel split, vector, scalar and three blocks per CU (o3) —, with that build's timer
+// name, LDS size (+ lds_pad) and block size.
+template <int WR, int WC, int MT, int CW, bool AK>
+void gg_launch_variant(const GGParams& p, const GGClassTable& ct, bool vec, bool o3, dim3 grid, size_t lds_pad, const GGTimer& tm) {
+  static const std::string tile = std::to_string(WR) + "," + std::to_string(WC) + "," + std::to_string(MT) + "," + std::to_string(CW);
+  static const std::string kname_g = "gg_kernel<" + tile + "," + (AK ? "kc" : "rc") + ">", kname_gs = "gg_kernel<" + tile + "," + (AK ? "kc" : "rc") + ",split>";
+  static const std::string kname_p = "ggp_kernel<" + tile + ">", kname_s0 = "ggp_kernel<" + tile + ",split>";
+  static const std::string kname_s1 = "ggp_kernel<" + tile + ",split,pre>";   // A read as pre-split bf16 planes
+  const bool split = gg_split_mode();
+  const std::string& kname = p.KC > 0 ? (split ? (p.apre ? kname_s1 : kname_s0) : kname_p) : ((vec && split) ? kname_gs : kname_g);
+  // ggp_kernel leaves out the border taps no pixel of the tile has when the block owns its whole reduction: executed <= algorithmic then
+  const bool skips = p.KC > 0 && p.splits == 1;
+  KernelTimer timer(kname.c_str(), tm.op, tm.flops, 0.0, skips ? 0.0 : tm.exec);
+  constexpr int threads = WR * WC * 64;
+  const size_t lds = gg_lds<WR, WC, MT, CW, AK>(2) + lds_pad;
+  if (p.KC > 0) {
+    CHIP_REQUIRE((kHasProducer<WC, CW, AK>) && vec);
+    if constexpr (kHasProducer<WC, CW, AK>) {
+      const size_t lds3 = gg_lds<WR, WC, MT, CW, AK>(3) + lds_pad;
+      if (split && p.apre) gg_launch_kernel(ggp_kernel<WR, WC, MT, CW, true, true>, grid, threads + 64, ggp_pre_lds<WR, WC, MT, CW>() + lds_pad, p, ct);
+      else if (split) gg_launch_kernel(ggp_kernel<WR, WC, MT, CW, true>, grid, threads + 64, lds3, p, ct);
+      else gg_launch_kernel(ggp_kernel<WR, WC, MT, CW>, grid, threads + 64, lds3, p, ct);
+    }
+    return;
+  }
+  if constexpr (!AK && WR == 2 && WC == 2 && MT == 2 && CW == 128) {
+    if (o3) {
+      gg_launch_kernel(gg_kernel<WR, WC, MT, CW, AK, true, true>, grid, threads, lds, p, ct);
+      return;
+    }
+  }
+  if (vec && split) gg_launch_kernel(gg_kernel<WR, WC, MT, CW, AK, true, false, true>, grid, threads, lds, p, ct);
+  else if (vec) gg_launch_kernel(gg_kernel<WR, WC, MT, CW, AK, true>, grid, threads, lds, p, ct);
+  else gg_launch_kernel(gg_kernel<WR, WC, MT, CW, AK, false>, grid, threads, lds, p, ct);
+}
 
 // One launch over every stride class of a strided dgrad.  `cls` carries A, K, GX, G, TX, TYX, y0, x0, dy0, dx0
 // per class; ncols / col_tiles / tile_end are filled here for the chosen tile shape.
 template <int WR, int WC, int MT, int CW>
-void gg_launch_classes(GGParams& p, GGClassTable& ct, bool vec) {
+void gg_launch_classes(GGParams& p, GGClassTable& ct, bool vec, const GGTimer& tm) {
   constexpr int ROWS = WR * MT * 32;
-  constexpr int A_STAGE = BK * ROWS, B_STAGE = WC * BK * CW;
-  const size_t lds = sizeof(float) * 2 * (A_STAGE + B_STAGE);
   p.NP = vec ? p.N : divup(p.N, CW) * CW;
   p.row_tiles = divup(p.R, ROWS);
   p.zero = zero_page();
@@ -1469,53 +1567,18 @@ void gg_launch_classes(GGParams& p, GGClassTable& ct, bool vec) {
     end += p.row_tiles * ct.c[i].col_tiles;
     ct.c[i].tile_end = end;
   }
-  static const std::string kname_g = "gg_kernel<" + std::to_string(WR) + "," + std::to_string(WC) + "," + std::to_string(MT) + "," + std::to_string(CW) + ",rc>";
-  static const std::string kname_p = "ggp_kernel<" + std::to_string(WR) + "," + std::to_string(WC) + "," + std::to_string(MT) + "," + std::to_string(CW) + ">";
-  static const std::string kname_s0 = kname_p.substr(0, kname_p.size() - 1) + ",split>";
-  static const std::string kname_s1 = kname_p.substr(0, kname_p.size() - 1) + ",split,pre>";   // A read as pre-split bf16 planes
-  const std::string& kname_s = p.apre ? kname_s1 : kname_s0;
-  static const std::string kname_gs = kname_g.substr(0, kname_g.size() - 1) + ",split>";
-  const std::string& kname = p.KC > 0 ? (gg_split_mode() ? kname_s : kname_p) : ((vec && gg_split_mode()) ? kname_gs : kname_g);
-  KernelTimer timer(kname.c_str(), t_op, t_flops, 0.0, p.KC > 0 ? 0.0 : t_exec);
-  dim3 grid(end), block(WR * WC * 64);
-  if (p.KC > 0) {
-    CHIP_REQUIRE(vec && WC * (CW / 4) == 64);
-    if constexpr (WC * (CW / 4) == 64) {
-      const size_t lds3 = lds / 2 * 3;
-      if (gg_split_mode() && p.apre) {
-        const size_t lds3p = sizeof(float) * 3 * (6 * ROWS * 4 + B_STAGE);
-        allow_big_lds(ggp_kernel<WR, WC, MT, CW, true, true>, lds3p);
-        hipLaunchKernelGGL((ggp_kernel<WR, WC, MT, CW, true, true>), grid, dim3(WR * WC * 64 + 64), lds3p, stream(), p, ct);
-      } else if (gg_split_mode()) {
-        allow_big_lds(ggp_kernel<WR, WC, MT, CW, true>, lds3);
-        hipLaunchKernelGGL((ggp_kernel<WR, WC, MT, CW, true>), grid, dim3(WR * WC * 64 + 64), lds3, stream(), p, ct);
-      } else {
-        allow_big_lds(ggp_kernel<WR, WC, MT, CW>, lds3);
-        hipLaunchKernelGGL((ggp_kernel<WR, WC, MT, CW>), grid, dim3(WR * WC * 64 + 64), lds3, stream(), p, ct);
-      }
-    }
-  } else if (vec && gg_split_mode()) {
-    allow_big_lds(gg_kernel<WR, WC, MT, CW, false, true, false, true>, lds);
-    hipLaunchKernelGGL((gg_kernel<WR, WC, MT, CW, false, true, false, true>), grid, block, lds, stream(), p, ct);
-  } else if (vec) {
-    allow_big_lds(gg_kernel<WR, WC, MT, CW, false, true>, lds);
-    hipLaunchKernelGGL((gg_kernel<WR, WC, MT, CW, false, true>), grid, block, lds, stream(), p, ct);
-  } else {
-    allow_big_lds(gg_kernel<WR, WC, MT, CW, false, false>, lds);
-    hipLaunchKernelGGL((gg_kernel<WR, WC, MT, CW, false, false>), grid, block, lds, stream(), p, ct);
-  }
+  gg_launch_variant<WR, WC, MT, CW, false>(p, ct, vec, false, dim3(end), 0, tm);
 }
 
+// Launch one gather-GEMM.  `dst_elems` > 0 means the launch covers the whole destination matrix,
+// which makes a split-K (slab per split + deterministic reduce) legal.
 template <int WR, int WC, int MT, int CW, bool AK>
-void gg_launch_cfg(GGParams& p, bool vec, size_t dst_elems) {
-  constexpr int ROWS = WR * MT * 32;
-  constexpr int A_STAGE = AK ? ROWS * (BK + 4) : BK * ROWS;
-  constexpr int B_STAGE = WC * BK * CW;
+void gg_launch_cfg(GGParams& p, bool vec, size_t dst_elems, const GGTimer& tm) {
+  constexpr int ROWS = WR * MT * 32, TILE = ROWS * WC * CW;
   p.NP = vec ? p.N : divup(p.N, CW) * CW;
   p.ncols = divup(p.G * p.NP, CW);
   // CONVNET_GG_LDS_PAD (diagnostic): extra dynamic LDS per block, e.g. 65536 to force ONE resident block per CU
   const size_t lds_pad = (size_t)CHIP_DIAG_KNOB("CONVNET_GG_LDS_PAD", 0);
-  const size_t lds = sizeof(float) * 2 * (A_STAGE + B_STAGE) + lds_pad;
   p.row_tiles = divup(p.R, ROWS);
   p.col_tiles = divup(p.ncols, WC);
   p.zero = zero_page();
@@ -1526,51 +1589,31 @@ void gg_launch_cfg(GGParams& p, bool vec, size_t dst_elems) {
   // vector build has the variant (it is the one whose register count sits between the 2- and 3-block limits).
   const bool no_o3 = CHIP_DIAG_KNOB("CONVNET_GG_NO_O3", 0) != 0;
   const bool o3 = !no_o3 && !gg_split_mode() && vec && !AK && WR == 2 && WC == 2 && MT == 2 && CW == 128 && tiles >= 2 * 768 && p.KC == 0;
-  int slots_launch = o3 ? 768 : kTargetBlocks;
-  if constexpr (!AK && WC * (CW / 4) == 64) {
-    if (p.KC > 0) {
-      static const int pslots_s = resident_slots(ggp_kernel<WR, WC, MT, CW, true>, WR * WC * 64 + 64, sizeof(float) * 3 * (A_STAGE + B_STAGE));
-      static const int pslots_p = resident_slots(ggp_kernel<WR, WC, MT, CW, true, true>, WR * WC * 64 + 64, sizeof(float) * 3 * (6 * ROWS * 4 + B_STAGE));
-      static const int pslots_f = resident_slots(ggp_kernel<WR, WC, MT, CW>, WR * WC * 64 + 64, sizeof(float) * 3 * (A_STAGE + B_STAGE));
-      slots_launch = gg_split_mode() ? (p.apre ? pslots_p : pslots_s) : pslots_f;
-    }
+  int slots = o3 ? 768 : kTargetBlocks;
+  if constexpr (kHasProducer<WC, CW, AK>) {
+    if (p.KC > 0) slots = ggp_slots<WR, WC, MT, CW>(gg_split_mode(), p.apre != 0);
   }
   // FLOP/s of one resident block, for the two estimates below: fp32 MFMA = half a CU (64 FLOP/clk/SIMD, 2 blocks per CU) at 80 %;
   // bf16-split = the measured ~190 TFLOP/s-equivalent of a full chip over its resident blocks.
-  const double block_rate = gg_split_mode() ? 190e12 / slots_launch : 64.0 * 4 * 2.2e9 * 0.8 / 2;
-  // Split-K factor by wave quantisation: every block of a launch takes the same time, so a grid of b
-  // blocks on `slots` resident-block slots runs ceil(b/slots) rounds and wastes the empty part of the
-  // last one (338 tiles on 512 slots = 66 % busy; 3 K-splits = 1014 blocks = 99 %).  Pick the split with
-  // the best estimated time = rounds * (work per block) + slab-reduce traffic; needs a launch that owns
-  // the whole destination (dst_elems > 0).
-  int splits = 1;
+  const double block_rate = gg_split_mode() ? 190e12 / slots : 64.0 * 4 * 2.2e9 * 0.8 / 2;
+  const double flops = 2.0 * ROWS * (WC * (double)CW) * (double)p.K;           // per tile, all K
+  const bool may_tail = dst_elems > 0 && gg_partial_last_round(tiles, slots, kchunks) && !CHIP_DIAG_KNOB("CONVNET_GG_NO_TAIL_SPLIT", 0);
+  // split-K by wave quantisation (gg_split_k) ...
+  double best_t = 1e30;
+  int splits = gg_split_k(tiles, slots, flops, block_rate, dst_elems, kchunks, kchunks, &best_t);
   int tail_s_instead = 0;   // > 0: split-K was cancelled in favour of a tail split with this many K-ranges (the choice below must honour it)
-  if (dst_elems > 0 && kchunks >= 16) {
-    const double slots = slots_launch;
-    const double flops = 2.0 * ROWS * (WC * (double)CW) * (double)p.K;           // per tile, all K
-    double best_t = 1e30;
-    for (int sp = 1; sp <= 16 && kchunks / sp >= 8; ++sp) {
-      const double rounds = std::ceil(tiles * (double)sp / slots);
-      double t = rounds * (flops / sp) / block_rate;
-      if (sp > 1) t += sizeof(float) * (double)dst_elems * (2.0 * sp + 1) / 4.0e12 + 4e-6;
-      if (t < best_t * 0.97) {
-        best_t = t;
-        splits = sp;
-      }
-    }
-    // ... against the tail split below (whole-K blocks for the full rounds, only the last round's tiles cut): the same round count
-    // with a fix-up over a few tiles instead of a reduce over the whole destination (conv3 dgrad: 338 tiles on 256 slots, 3 slabs of
-    // 44 MB reduced in 35 us vs 82 tail tiles fixed in ~10)
-    if (splits > 1 && tiles > slots_launch && tiles % slots_launch != 0 && kchunks >= 32 && !CHIP_DIAG_KNOB("CONVNET_GG_NO_TAIL_SPLIT", 0)) {
-      const int full = (tiles / slots_launch) * slots_launch, rem = tiles - full;
-      const double t_round = flops / block_rate, tile_bytes = sizeof(float) * (double)ROWS * WC * CW;
-      for (int s = 2; s <= 8 && kchunks / s >= 8; ++s) {
-        const double t = (full / slots + std::ceil(rem * (double)s / slots) / s) * t_round + rem * (s + 1.0) * tile_bytes / 4.0e12 + 6e-6;
-        if (t < best_t) {
-          splits = 1;
-          tail_s_instead = s;
-          break;
-        }
+  // ... against the tail split below (whole-K blocks for the full rounds, only the last round's tiles cut): the same round count
+  // with a fix-up over a few tiles instead of a reduce over the whole destination (conv3 dgrad: 338 tiles on 256 slots, 3 slabs of
+  // 44 MB reduced in 35 us vs 82 tail tiles fixed in ~10)
+  if (splits > 1 && may_tail) {
+    const int full = (tiles / slots) * slots, rem = tiles - full;
+    const double t_round = flops / block_rate, tile_bytes = sizeof(float) * (double)ROWS * WC * CW;
+    for (int s = 2; s <= 8 && kchunks / s >= 8; ++s) {
+      const double t = (full / (double)slots + std::ceil(rem * (double)s / (double)slots) / s) * t_round + rem * (s + 1.0) * tile_bytes / 4.0e12 + 6e-6;
+      if (t < best_t) {
+        splits = 1;
+        tail_s_instead = s;
+        break;
       }
     }
   }
@@ -1579,103 +1622,27 @@ void gg_launch_cfg(GGParams& p, bool vec, size_t dst_elems) {
   p.splits = splits;
   p.slab = dst_elems;
   p.partial = splits > 1 ? static_cast<float*>(workspace(sizeof(float) * dst_elems * splits)) : nullptr;
-  // Tail split: more tiles than slots and a partial last round (conv2 fprop: 1352 tiles = 2.64 rounds of 512).  Cut only
-  // the last round's tiles into s K-ranges so that round is full as well: 2 + ceil(328*3/512)/3 = 2.67 rounds instead of 3.
   p.tail_splits = 1;
   p.tail_partial = nullptr;
-  const int slots = slots_launch;
-  const bool no_tail = CHIP_DIAG_KNOB("CONVNET_GG_NO_TAIL_SPLIT", 0) != 0;
-  if (!no_tail && splits == 1 && dst_elems > 0 && tiles > slots && tiles % slots != 0 && kchunks >= 32) {
-    const int full = (tiles / slots) * slots, rem = tiles - full;
-    const double tile_bytes = sizeof(float) * (double)ROWS * WC * CW;
-    const double t_round = 2.0 * ROWS * (WC * (double)CW) * (double)p.K / block_rate;   // one whole-K block
-    double best = 0.95;   // cost of the last round today = 1 round; require a 5 % gain on it
-    int best_s = 1;
-    for (int s = 2; s <= 8 && kchunks / s >= 8; ++s) {
-      const double cost = std::ceil(rem * (double)s / slots) / s + (rem * (s + 1.0) * tile_bytes / 4.0e12 + 6e-6) / t_round;
-      if (cost < best) {
-        best = cost;
-        best_s = s;
-      }
-    }
+  if (splits == 1 && may_tail) {
+    int best_s = gg_tail_split(tiles, slots, flops, block_rate, TILE, kchunks);
     if (best_s == 1 && tail_s_instead > 1) best_s = tail_s_instead;   // (the two estimates differ in form: never fall between them)
-    if (best_s > 1) {
-      p.tail_first = full;
-      p.tail_cps = divup(kchunks, best_s);
-      p.tail_splits = divup(kchunks, p.tail_cps);
-      p.tail_tf8 = full / 8;
-      p.tail_tt8 = divup(rem * p.tail_splits, 8);
-      p.tail_partial = static_cast<float*>(workspace(sizeof(float) * (size_t)rem * p.tail_splits * ROWS * WC * CW));
-    }
+    if (best_s > 1) gg_set_tail(p, tiles, slots, kchunks, best_s, TILE);
   }
   dim3 grid(p.tail_splits > 1 ? 8 * (p.tail_tf8 + p.tail_tt8) : ((tiles + 7) / 8) * 8, splits);
-  dim3 block(WR * WC * 64);
-  static const std::string kname_g = "gg_kernel<" + std::to_string(WR) + "," + std::to_string(WC) + "," + std::to_string(MT) + "," + std::to_string(CW) + "," + (AK ? "kc" : "rc") + ">";
-  static const std::string kname_p = "ggp_kernel<" + std::to_string(WR) + "," + std::to_string(WC) + "," + std::to_string(MT) + "," + std::to_string(CW) + ">";
-  static const std::string kname_s0 = kname_p.substr(0, kname_p.size() - 1) + ",split>";
-  static const std::string kname_s1 = kname_p.substr(0, kname_p.size() - 1) + ",split,pre>";   // A read as pre-split bf16 planes
-  const std::string& kname_s = p.apre ? kname_s1 : kname_s0;
-  static const std::string kname_gs = kname_g.substr(0, kname_g.size() - 1) + ",split>";
-  const std::string& kname = p.KC > 0 ? (gg_split_mode() ? kname_s : kname_p) : ((vec && gg_split_mode()) ? kname_gs : kname_g);
-  {
-    // ggp_kernel leaves out the border taps no pixel of the tile has when the block owns its whole reduction: executed <= algorithmic then
-    const bool skips = p.KC > 0 && splits == 1;
-    KernelTimer timer(kname.c_str(), t_op, t_flops, 0.0, skips ? 0.0 : t_exec);
-    if constexpr (!AK && WR == 2 && WC == 2 && MT == 2 && CW == 128) {
-      if (o3) {
-        allow_big_lds(gg_kernel<WR, WC, MT, CW, AK, true, true>, lds);
-        hipLaunchKernelGGL((gg_kernel<WR, WC, MT, CW, AK, true, true>), grid, block, lds, stream(), p, kNoClasses);
-      }
-    }
-    bool donep = false;
-    if (p.KC > 0) CHIP_REQUIRE(!AK && vec && WC * (CW / 4) == 64);
-    if constexpr (!AK && WC * (CW / 4) == 64) {
-      if (p.KC > 0) {
-        const size_t lds3 = sizeof(float) * 3 * (A_STAGE + B_STAGE) + lds_pad;
-        if (gg_split_mode() && p.apre) {
-          const size_t lds3p = sizeof(float) * 3 * (6 * ROWS * 4 + B_STAGE) + lds_pad;
-          allow_big_lds(ggp_kernel<WR, WC, MT, CW, true, true>, lds3p);
-          hipLaunchKernelGGL((ggp_kernel<WR, WC, MT, CW, true, true>), grid, dim3(WR * WC * 64 + 64), lds3p, stream(), p, kNoClasses);
-        } else if (gg_split_mode()) {
-          allow_big_lds(ggp_kernel<WR, WC, MT, CW, true>, lds3);
-          hipLaunchKernelGGL((ggp_kernel<WR, WC, MT, CW, true>), grid, dim3(WR * WC * 64 + 64), lds3, stream(), p, kNoClasses);
-        } else {
-          allow_big_lds(ggp_kernel<WR, WC, MT, CW>, lds3);
-          hipLaunchKernelGGL((ggp_kernel<WR, WC, MT, CW>), grid, dim3(WR * WC * 64 + 64), lds3, stream(), p, kNoClasses);
-        }
-        donep = true;
-      }
-    }
-    if (o3 || donep) {
-    } else if (vec && gg_split_mode()) {
-      allow_big_lds(gg_kernel<WR, WC, MT, CW, AK, true, false, true>, lds);
-      hipLaunchKernelGGL((gg_kernel<WR, WC, MT, CW, AK, true, false, true>), grid, block, lds, stream(), p, kNoClasses);
-    } else if (vec) {
-      allow_big_lds(gg_kernel<WR, WC, MT, CW, AK, true>, lds);
-      hipLaunchKernelGGL((gg_kernel<WR, WC, MT, CW, AK, true>), grid, block, lds, stream(), p, kNoClasses);
-    } else {
-      allow_big_lds(gg_kernel<WR, WC, MT, CW, AK, false>, lds);
-      hipLaunchKernelGGL((gg_kernel<WR, WC, MT, CW, AK, false>), grid, block, lds, stream(), p, kNoClasses);
-    }
-  }
+  gg_launch_variant<WR, WC, MT, CW, AK>(p, kNoClasses, vec, o3, grid, lds_pad, tm);
   if (p.tail_splits > 1) {
     const int rem = tiles - p.tail_first;
-    KernelTimer timer("gg_tail_fix_kernel", t_op, 0.0, sizeof(float) * (double)rem * (p.tail_splits + 1) * ROWS * WC * CW);
-    if (vec) hipLaunchKernelGGL((gg_tail_fix_kernel<WR, WC, MT, CW, true>), dim3(rem * kTailFixParts), block, 0, stream(), p);
-    else hipLaunchKernelGGL((gg_tail_fix_kernel<WR, WC, MT, CW, false>), dim3(rem * kTailFixParts), block, 0, stream(), p);
+    KernelTimer timer("gg_tail_fix_kernel", tm.op, 0.0, sizeof(float) * (double)rem * (p.tail_splits + 1) * ROWS * WC * CW);
+    if (vec) hipLaunchKernelGGL((gg_tail_fix_kernel<WR, WC, MT, CW, true>), dim3(rem * kTailFixParts), dim3(WR * WC * 64), 0, stream(), p);
+    else hipLaunchKernelGGL((gg_tail_fix_kernel<WR, WC, MT, CW, false>), dim3(rem * kTailFixParts), dim3(WR * WC * 64), 0, stream(), p);
   }
-  if (splits > 1) {
-    KernelTimer timer("gg_reduce_kernel", t_op, 0.0, sizeof(float) * (double)dst_elems * (splits + 1));
-    size_t nb = (dst_elems + 255) / 256;
-    if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(gg_reduce_kernel, dim3((unsigned)nb), dim3(256), 0, stream(), p.dst, p.partial, p.bias, dst_elems, p.slab,
-                       splits, (size_t)p.DP * p.N, p.scaleTargets, p.relu, p.mask, p.post_scale);
-  }
+  if (splits > 1) gg_reduce_launch(p, dst_elems, splits, tm.op);
 }
 
 }  // namespace
 
-void wg_reduce_launch(const WGParams& p, size_t total, int splits, int groups, const char* op) {   // (wgw_kernel's; wg_launch_cfg carries its own copy)
+void wg_reduce_launch(const WGParams& p, size_t total, int splits, int groups, const char* op) {
   KernelTimer timer("wg_reduce_kernel", op, 0.0, sizeof(float) * (double)total * (splits + 1));
   size_t nb = (total + 255) / 256;
   if (nb > 4096) nb = 4096;
@@ -1759,42 +1726,22 @@ void gg_reduce_launch(const GGParams& p, size_t dst_elems, int splits, const cha
 namespace {
 
 template <bool AK>
-void gg_run(GGParams& p, bool vec, size_t dst_elems) {
-  // pick the row tile (128/64/32) that pads the fewest rows; ties go to the larger tile.  (The 96-row
-  // 6-wave config measured 68 TFLOP/s vs 106 for the 128-row one, so 96-row problems — conv1 fprop,
-  // conv2 dgrad — run 25 % padded on the 128-row kernel: 80 effective TFLOP/s.)
-  // row tile by problem height: 128 rows (2x2 waves of 64x128), 96 rows (4 waves of 96x64: conv1 fprop,
-  // conv2 dgrad), 64 and 32 rows for small layers.
-  const int force64 = CHIP_DIAG_KNOB("CONVNET_GG_ROWS64", 0);   // experiment knob: 64-row tiles everywhere
-  const bool no_skinny = CHIP_DIAG_KNOB("CONVNET_GG_NO_SKINNY", 0) != 0;
-  // An FC layer at a small per-GPU batch (strong scaling of a global batch: 128 / 64 / 32 images per GPU) is a GEMM with <= 128
-  // columns, bound by streaming the weight matrix once: four waves stacked along the rows, one 64-column wave-column, so a
-  // 32-image batch pads 2x instead of 8x and every weight row still reaches LDS with 16-byte pieces.
-  if (p.skinny && vec && !no_skinny) gg_launch_cfg<4, 1, 1, 64, AK>(p, vec, dst_elems);
-  else if (force64) gg_launch_cfg<2, 2, 1, 128, AK>(p, vec, dst_elems);
-  else if (p.R > 96 || (p.R > 64 && p.R <= 96 && (!vec)))
-    gg_launch_cfg<2, 2, 2, 128, AK>(p, vec, dst_elems);
-  else if (p.R > 64)
-    gg_launch_cfg<1, 4, 3, 64, AK>(p, vec, dst_elems);
-  else if (p.R > 32)
-    gg_launch_cfg<2, 2, 1, 128, AK>(p, vec, dst_elems);
-  else
-    gg_launch_cfg<1, 4, 1, 128, AK>(p, vec, dst_elems);
+void gg_run(GGParams& p, bool vec, size_t dst_elems, const GGTimer& tm) {
+  gg_with_tile(gg_tile(p.R, vec, p.skinny != 0), [&](auto t) {
+    using T = decltype(t);
+    gg_launch_cfg<T::WR, T::WC, T::MT, T::CW, AK>(p, vec, dst_elems, tm);
+  });
 }
 
-void gg_run_classes(GGParams& p, GGClassTable& ct, bool vec) {   // same tile choice as gg_run
-  if (p.R > 96 || (p.R > 64 && p.R <= 96 && (!vec)))
-    gg_launch_classes<2, 2, 2, 128>(p, ct, vec);
-  else if (p.R > 64)
-    gg_launch_classes<1, 4, 3, 64>(p, ct, vec);
-  else if (p.R > 32)
-    gg_launch_classes<2, 2, 1, 128>(p, ct, vec);
-  else
-    gg_launch_classes<1, 4, 1, 128>(p, ct, vec);
+void gg_run_classes(GGParams& p, GGClassTable& ct, bool vec, const GGTimer& tm) {
+  gg_with_tile(gg_tile(p.R, vec, false), [&](auto t) {
+    using T = decltype(t);
+    gg_launch_classes<T::WR, T::WC, T::MT, T::CW>(p, ct, vec, tm);
+  });
 }
 
 template <int WM, int WN, int MT, int NTL, int TS = 32>
-void wg_launch_cfg(WGParams& p, bool vec) {
+void wg_launch_cfg(WGParams& p, bool vec, const GGTimer& tm) {
   constexpr int KT = WM * MT * TS, FT = WN * NTL * TS;
   const size_t lds = sizeof(float) * 2 * (KT + FT) * (vec ? WG_NB : WG_PITCH);
   p.k_tiles = divup(p.K, KT);
@@ -1832,7 +1779,7 @@ void wg_launch_cfg(WGParams& p, bool vec) {
   const bool split_products = vec && wg_split_mode();
   const std::string& kname = split_products ? kname_s : kname_f;
   {
-    KernelTimer timer(kname.c_str(), t_op, t_flops, 0.0, t_exec);
+    KernelTimer timer(kname.c_str(), tm.op, tm.flops, 0.0, tm.exec);
     if (split_products) {
       allow_big_lds(wg_kernel<WM, WN, MT, NTL, true, TS, true>, lds);
       hipLaunchKernelGGL((wg_kernel<WM, WN, MT, NTL, true, TS, true>), grid, block, lds, stream(), p);
@@ -1844,26 +1791,11 @@ void wg_launch_cfg(WGParams& p, bool vec) {
       hipLaunchKernelGGL((wg_kernel<WM, WN, MT, NTL, false, TS>), grid, block, lds, stream(), p);
     }
   }
-  if (splits > 1 && !frame_slabs) {
-    KernelTimer timer("wg_reduce_kernel", t_op, 0.0, sizeof(float) * (double)total * (splits + 1));
-    size_t nb = (total + 255) / 256;
-    if (nb > 4096) nb = 4096;
-    const float* slabs = p.partial;
-    int nslabs = splits;
-    if (groups > 1) {
-      float* stage = p.partial + (size_t)splits * total;
-      const int per = divup(splits, groups);
-      hipLaunchKernelGGL(wg_reduce_group_kernel, dim3((unsigned)nb, divup(splits, per)), dim3(256), 0, stream(), stage, p.partial, total, splits, per);
-      slabs = stage;
-      nslabs = divup(splits, per);
-    }
-    hipLaunchKernelGGL(wg_reduce_kernel, dim3((unsigned)nb), dim3(256), 0, stream(), p.dst, p.bias_dst, slabs, total,
-                       (size_t)p.K * p.F, nslabs, p.scaleTargets, p.scaleOutput);
-  }
+  if (splits > 1 && !frame_slabs) wg_reduce_launch(p, total, splits, groups, tm.op);
 }
 
-void wg_launch(WGParams& p, bool vec) {
-  if (wgw_try(p, vec, vec && wg_split_mode(), t_op, t_flops, t_exec)) return;   // the wide tile (wgrad_wide.hip), when selected
+void wg_launch(WGParams& p, bool vec, const GGTimer& tm) {
+  if (wgw_try(p, vec, vec && wg_split_mode(), tm.op, tm.flops, tm.exec)) return;   // the wide tile (wgrad_wide.hip), when selected
   // filter tile: fewest padded filters among 128/96/64/32; k tile 128, or 160 when that pads less.
   int ft = 128, pad = divup(p.F, 128) * 128;
   const int cands[3] = {96, 64, 32};
@@ -1875,11 +1807,11 @@ void wg_launch(WGParams& p, bool vec) {
     }
   }
   const bool k160 = divup(p.K, 160) * 160 < divup(p.K, 128) * 128;
-  if (ft == 128) wg_launch_cfg<2, 2, 2, 2>(p, vec);
-  else if (ft == 96 && k160) wg_launch_cfg<2, 2, 5, 3, 16>(p, vec);   // 160 x 96 as 2x2 waves of 80 x 48 (16x16x4 MFMA)
-  else if (ft == 96) wg_launch_cfg<4, 1, 1, 3>(p, vec);
-  else if (ft == 64) wg_launch_cfg<4, 1, 1, 2>(p, vec);
-  else wg_launch_cfg<4, 1, 1, 1>(p, vec);
+  if (ft == 128) wg_launch_cfg<2, 2, 2, 2>(p, vec, tm);
+  else if (ft == 96 && k160) wg_launch_cfg<2, 2, 5, 3, 16>(p, vec, tm);   // 160 x 96 as 2x2 waves of 80 x 48 (16x16x4 MFMA)
+  else if (ft == 96) wg_launch_cfg<4, 1, 1, 3>(p, vec, tm);
+  else if (ft == 64) wg_launch_cfg<4, 1, 1, 2>(p, vec, tm);
+  else wg_launch_cfg<4, 1, 1, 1>(p, vec, tm);
 }
 
 struct ConvGeo {
@@ -1909,10 +1841,6 @@ ConvGeo conv_geo(const Shape4D* img, const Shape4D* flt, const Shape4D* out, con
   CHIP_REQUIRE((size_t)g.N * g.H * g.W * g.C < (1ull << 31) && (size_t)g.N * g.My * g.Mx * g.F < (1ull << 31));
   return g;
 }
-
-// Row-tile height gg_run / gg_run_classes pick for an R-row problem on the producer-wave kernels (the pre-split filter planes are laid
-// out per row tile of this height, filter_planes_rt_kernel).
-inline int gg_tile_rows(int R) { return CHIP_DIAG_KNOB("CONVNET_GG_ROWS64", 0) ? 64 : R > 96 ? 128 : R > 64 ? 96 : R > 32 ? 64 : 32; }
 
 inline bool gg_presplit_mode() {
   return gg_split_mode() && !CHIP_DIAG_KNOB("CONVNET_GG_NO_PRESPLIT", 0);
@@ -1952,9 +1880,11 @@ void conv_up_impl(cudamat* images, cudamat* filters, cudamat* bias, cudamat* tar
   p.DW = g.Mx; p.DP = g.My * g.Mx; p.dsy = 1; p.dsx = 1; p.dy0 = 0; p.dx0 = 0;
   p.scaleTargets = scaleTargets; p.relu = relu;
   const bool vec = g.N % 4 == 0 && g.F % 4 == 0 && aligned16(p.A) && aligned16(p.src) && aligned16(p.dst);
+  const size_t dst_elems = (size_t)g.N * p.DP * g.F;
+  const GGTimer tm{"conv_fprop", 2.0 * g.N * p.G * (double)g.F * p.K, 0.0};
   if (vec && gg_presplit_mode() && gg_producer_mode() &&
       gfc_try(images->data_device, filters->data_device, p.bias, targets->data_device, g.N, g.C, g.H, g.W, g.F, g.Ky, g.Kx, g.sy, g.sx, -g.py, -g.px,
-              g.My, g.Mx, scaleTargets, relu, 2.0 * g.N * p.G * (double)g.F * p.K))
+              g.My, g.Mx, scaleTargets, relu, tm.flops))
     return;
   if (vec && gg_presplit_mode() && gg_producer_mode() && g.C % BK != 0 && g.F > 32 && CHIP_KNOB("CONVNET_GG_GK", 1) &&
       (size_t)g.C * g.H * g.W * g.N < (size_t(1) << 30)) {
@@ -1968,22 +1898,17 @@ void conv_up_impl(cudamat* images, cudamat* filters, cudamat* bias, cudamat* tar
     p.ktab = gk_table(g.C, g.H, g.W, g.N, g.Ky, g.Kx);
     p.K = KP;
     p.KC = KP;   // selects the producer-wave kernels in the launchers; the reduction itself is the table's
-    t_op = "conv_fprop";
-    t_flops = 2.0 * g.N * p.G * (double)g.F * K;
-    t_exec = 0.0;
-    gg_run<false>(p, vec, (size_t)g.N * p.DP * g.F);
-    note_kernel("gg_kernel(fprop)", t_flops, p.row_tiles * p.col_tiles, p.splits);
+    gg_run<false>(p, vec, dst_elems, tm);
+    note_kernel("gg_kernel(fprop)", tm.flops, p.row_tiles * p.col_tiles, p.splits);
     return;
   }
   if (vec && ggp_shape_ok(g.F, g.C) && gg_presplit_mode()) {
     // patch-resident gather on pre-split source planes (patch_gemm.hip) where the geometry has one
     p.KC = g.C;
-    if (patch_shape_ok(p, (size_t)g.N * p.DP * g.F)) {
-      t_op = "conv_fprop";
-      t_flops = 2.0 * g.N * p.G * (double)g.F * p.K;
+    if (patch_shape_ok(p, dst_elems)) {
       const PatchBank bank{filters->data_device, g.F, g.C, g.Ky, g.Kx, 0, 0, 1, 1, g.Ky, g.Kx, false};
-      patch_run(p, (size_t)g.N * p.DP * g.F, t_op, t_flops, bank);
-      note_kernel(convnet_hip_get_patch_mode() >= 3 ? "gpw_kernel(fprop)" : "gpp_kernel(fprop)", t_flops, p.row_tiles * p.col_tiles, p.splits);
+      patch_run(p, dst_elems, tm.op, tm.flops, bank);
+      note_kernel(convnet_hip_get_patch_mode() >= 3 ? "gpw_kernel(fprop)" : "gpp_kernel(fprop)", tm.flops, p.row_tiles * p.col_tiles, p.splits);
       return;
     }
     p.KC = 0;
@@ -2012,11 +1937,8 @@ void conv_up_impl(cudamat* images, cudamat* filters, cudamat* bias, cudamat* tar
     }
     p.KC = g.C;
   }
-  t_op = "conv_fprop";
-  t_flops = 2.0 * g.N * p.G * (double)g.F * p.K;
-  t_exec = 0.0;
-  gg_run<false>(p, vec, (size_t)g.N * p.DP * g.F);
-  note_kernel("gg_kernel(fprop)", 2.0 * g.N * p.G * (double)g.F * p.K, p.row_tiles * p.col_tiles, p.splits);
+  gg_run<false>(p, vec, dst_elems, tm);
+  note_kernel("gg_kernel(fprop)", tm.flops, p.row_tiles * p.col_tiles, p.splits);
 }
 
 }  // namespace
@@ -2056,16 +1978,15 @@ static bool park_conv(int kind, void (*launch)(PendingOp&), cudamat* a, cudamat*
   return true;
 }
 
-void convUpGemm(cudamat* images, cudamat* filters, cudamat* targets, Shape4D* is, Shape4D* fs, Shape4D* ts, ConvDesc d,
-                float scaleTargets) {
-  if (park_conv(1, launch_conv_up, images, filters, targets, is, fs, ts, d, scaleTargets)) return;
-  conv_up_impl(images, filters, nullptr, targets, is, fs, ts, d, scaleTargets, 0);
-}
-
 void convUp(cudamat* images, cudamat* filters, cudamat* targets, Shape4D* is, Shape4D* fs, Shape4D* ts, ConvDesc d,
             float scaleTargets) {
   if (park_conv(1, launch_conv_up, images, filters, targets, is, fs, ts, d, scaleTargets)) return;
   conv_up_impl(images, filters, nullptr, targets, is, fs, ts, d, scaleTargets, 0);
+}
+
+void convUpGemm(cudamat* images, cudamat* filters, cudamat* targets, Shape4D* is, Shape4D* fs, Shape4D* ts, ConvDesc d,
+                float scaleTargets) {
+  convUp(images, filters, targets, is, fs, ts, d, scaleTargets);
 }
 
 void convUpBiasAct(cudamat* images, cudamat* filters, cudamat* bias, cudamat* targets, Shape4D* is, Shape4D* fs, Shape4D* ts,
@@ -2105,115 +2026,111 @@ static void conv_down_impl(cudamat* derivs, cudamat* filters, cudamat* targets, 
   float* const planes = wt + wt_floats;
   if (pre) base.apre = 1;
   const bool multi = g.sy * g.sx > 1 && g.sy * g.sx <= kMaxClasses;   // all classes in one launch (no wave-quantisation per class)
-  t_op = "conv_dgrad";
   // Work accounting.  ALGORITHMIC = the transposed convolution's MACs, 2*N*My*Mx*F*C*Ky*Kx (every output pixel meets every tap
   // once — the same count as fprop).  EXECUTED = what the gather issues: every INPUT pixel of a class runs the class's whole tap
   // set, border pixels on the zero page (conv5, pad 0: 169*9 vs 121*9 taps = 1.40x; conv2: 1.13x).  bench.py's roofline uses the
   // algorithmic figure; the executed one travels beside it.
   const double alg_flops = 2.0 * g.N * (double)g.My * g.Mx * (double)g.F * g.C * g.Ky * g.Kx;
+  // the stride classes that own input pixels: taps, first source row / column, first input pixel, grid of input pixels
+  struct StrideClass {
+    int cy, cx, TYc, TXc, jy0, jx0, iy0, ix0, GY, GX;
+  };
+  std::vector<StrideClass> classes;
   double exec_total = 0;
+  // iy = cy + pad + sy*j >= 0  ->  j >= ceil((-pad - cy)/sy)
+  auto first_j = [](int cls, int pad, int s) {
+    const int need = -pad - cls;
+    return need > 0 ? (need + s - 1) / s : 0;
+  };
   for (int cy = 0; cy < g.sy; ++cy)
     for (int cx = 0; cx < g.sx; ++cx) {
-      const int TYc = cy < g.Ky ? divup(g.Ky - cy, g.sy) : 0, TXc = cx < g.Kx ? divup(g.Kx - cx, g.sx) : 0;
-      const int ny = -g.py - cy, nx = -g.px - cx;
-      const int jy0 = ny > 0 ? (ny + g.sy - 1) / g.sy : 0, jx0 = nx > 0 ? (nx + g.sx - 1) / g.sx : 0;
-      const int iy0 = cy + g.py + g.sy * jy0, ix0 = cx + g.px + g.sx * jx0;
-      if (iy0 >= g.H || ix0 >= g.W) continue;
-      exec_total += 2.0 * g.N * (double)(((g.H - 1 - iy0) / g.sy + 1) * ((g.W - 1 - ix0) / g.sx + 1)) * g.C * (double)(g.F * TYc * TXc);
+      StrideClass c{};
+      c.cy = cy; c.cx = cx;
+      c.TYc = cy < g.Ky ? divup(g.Ky - cy, g.sy) : 0;
+      c.TXc = cx < g.Kx ? divup(g.Kx - cx, g.sx) : 0;
+      c.jy0 = first_j(cy, g.py, g.sy); c.jx0 = first_j(cx, g.px, g.sx);
+      c.iy0 = cy + g.py + g.sy * c.jy0; c.ix0 = cx + g.px + g.sx * c.jx0;
+      if (c.iy0 >= g.H || c.ix0 >= g.W) continue;
+      c.GY = (g.H - 1 - c.iy0) / g.sy + 1; c.GX = (g.W - 1 - c.ix0) / g.sx + 1;
+      exec_total += 2.0 * g.N * (double)(c.GY * c.GX) * g.C * (double)(g.F * c.TYc * c.TXc);
+      classes.push_back(c);
     }
-  for (int cy = 0; cy < g.sy; ++cy) {
-    for (int cx = 0; cx < g.sx; ++cx) {
-      const int TYc = cy < g.Ky ? divup(g.Ky - cy, g.sy) : 0;
-      const int TXc = cx < g.Kx ? divup(g.Kx - cx, g.sx) : 0;
-      // iy = cy + pad + sy*j >= 0  ->  j >= ceil((-pad - cy)/sy)
-      auto first_j = [](int c, int pad, int s) {
-        const int need = -pad - c;
-        return need > 0 ? (need + s - 1) / s : 0;
-      };
-      const int jy0 = first_j(cy, g.py, g.sy), jx0 = first_j(cx, g.px, g.sx);
-      const int iy0 = cy + g.py + g.sy * jy0, ix0 = cx + g.px + g.sx * jx0;
-      if (iy0 >= g.H || ix0 >= g.W) continue;
-      const int GY = (g.H - 1 - iy0) / g.sy + 1, GX = (g.W - 1 - ix0) / g.sx + 1;
-      float* wc = wt + woff;
-      const size_t welems = (size_t)g.C * g.F * TYc * TXc;
-      woff += (welems + 63) / 64 * 64;
-      GGClass k{};
-      k.A = wc; k.K = g.F * TYc * TXc;
-      if (!multi && pre && welems > 0) {
-        // a stride-1 convolution: one class, a stride-1 gather over the derivatives -> the patch-resident kernel where it applies
-        GGParams p = base;
-        p.K = k.K; p.GX = GX; p.G = GY * GX; p.TX = TXc; p.TYX = TYc * TXc;
-        p.y0 = jy0; p.x0 = jx0; p.dy0 = iy0; p.dx0 = ix0;
-        const bool whole = g.sy == 1 && g.sx == 1 && GY == g.H && GX == g.W;
-        if (patch_shape_ok(p, whole ? (size_t)g.N * g.H * g.W * g.C : 0)) {
-          const double cflops = 2.0 * g.N * p.G * (double)g.C * p.K;
-          flops += cflops;
-          t_flops = exec_total > 0 ? alg_flops * (cflops / exec_total) : 0.0;
-          const PatchBank bank{filters->data_device, g.F, g.C, g.Ky, g.Kx, cy, cx, g.sy, g.sx, TYc, TXc, true};
-          patch_run(p, whole ? (size_t)g.N * g.H * g.W * g.C : 0, t_op, t_flops, bank);
-          patched = true;
-          blocks += p.row_tiles * p.col_tiles;
-          continue;
-        }
-      }
-      if (pre && welems > 0) {
-        // class bank straight to bf16 planes (re-layout + exact split in one pass)
-        float* pc = planes + poff;
-        poff += ((size_t)24 * (g.F / 16) * TYc * TXc * divup(g.C, TH) * TH + 63) / 64 * 64;
-        const PatchBank bank{filters->data_device, g.F, g.C, g.Ky, g.Kx, cy, cx, g.sy, g.sx, TYc, TXc, true};
-        filter_planes_rt_launch(bank, pc, TYc * TXc, TH, "conv_dgrad");
-        k.A = pc;
-      } else if (welems > 0) {
-        int nb = (int)((welems + 255) / 256);
-        if (nb > 2048) nb = 2048;
-        (void)filter_planes_shared(nullptr, 0);   // another writer of the aux arena: a shared preparation is forgotten
-        KernelTimer timer("dgrad_filter_kernel", "conv_dgrad", 0.0, 8.0 * welems);
-        hipLaunchKernelGGL(dgrad_filter_kernel, dim3(nb), dim3(256), 0, stream(), filters->data_device, wc, g.F, g.C, g.Ky,
-                           g.Kx, cy, cx, g.sy, g.sx, TYc, TXc, tapm ? 1 : 0);
-      }
-      k.GX = GX; k.G = GY * GX; k.TX = TXc > 0 ? TXc : 1; k.TYX = TYc * TXc > 0 ? TYc * TXc : 1;
-      k.y0 = jy0; k.x0 = jx0; k.dy0 = iy0; k.dx0 = ix0;
-      const double cflops = 2.0 * g.N * k.G * (double)g.C * k.K;
-      flops += cflops;
-      if (multi) {
-        ct.c[ct.n++] = k;
+  for (const StrideClass& c : classes) {
+    const int cy = c.cy, cx = c.cx, TYc = c.TYc, TXc = c.TXc;
+    float* wc = wt + woff;
+    const size_t welems = (size_t)g.C * g.F * TYc * TXc;
+    woff += (welems + 63) / 64 * 64;
+    GGClass k{};
+    k.A = wc; k.K = g.F * TYc * TXc;
+    k.GX = c.GX; k.G = c.GY * c.GX; k.TX = TXc > 0 ? TXc : 1; k.TYX = TYc * TXc > 0 ? TYc * TXc : 1;
+    k.y0 = c.jy0; k.x0 = c.jx0; k.dy0 = c.iy0; k.dx0 = c.ix0;
+    // a stride-1 convolution has a single class that owns every input pixel: split-K is legal there
+    const bool whole = g.sy == 1 && g.sx == 1 && c.GY == g.H && c.GX == g.W;
+    const size_t dst_elems = whole ? (size_t)g.N * g.H * g.W * g.C : 0;
+    const double cflops = 2.0 * g.N * k.G * (double)g.C * k.K;
+    // this class's share of the call's algorithmic work, and what its launch executes
+    const GGTimer tm{"conv_dgrad", exec_total > 0 ? alg_flops * (cflops / exec_total) : 0.0, cflops};
+    const PatchBank bank{filters->data_device, g.F, g.C, g.Ky, g.Kx, cy, cx, g.sy, g.sx, TYc, TXc, true};
+    if (!multi && pre && welems > 0) {
+      // a stride-1 convolution: one class, a stride-1 gather over the derivatives -> the patch-resident kernel where it applies
+      GGParams p = base;
+      p.K = k.K; p.GX = c.GX; p.G = k.G; p.TX = TXc; p.TYX = TYc * TXc;
+      p.y0 = k.y0; p.x0 = k.x0; p.dy0 = k.dy0; p.dx0 = k.dx0;
+      if (patch_shape_ok(p, dst_elems)) {
+        flops += cflops;
+        patch_run(p, dst_elems, tm.op, tm.flops, bank);
+        patched = true;
+        blocks += p.row_tiles * p.col_tiles;
         continue;
       }
-      GGParams p = base;
-      p.A = k.A; p.K = k.K; p.GX = k.GX; p.G = k.G; p.TX = k.TX; p.TYX = k.TYX;
-      p.y0 = k.y0; p.x0 = k.x0; p.dy0 = k.dy0; p.dx0 = k.dx0;
-      t_flops = exec_total > 0 ? alg_flops * (cflops / exec_total) : 0.0;
-      t_exec = cflops;
-      // a stride-1 convolution has a single class that owns every input pixel: split-K is legal there
-      const bool whole = g.sy == 1 && g.sx == 1 && GY == g.H && GX == g.W;
-      gg_run<false>(p, vec, whole ? (size_t)g.N * g.H * g.W * g.C : 0);
-      blocks += p.row_tiles * p.col_tiles;
     }
+    if (pre && welems > 0) {
+      // class bank straight to bf16 planes (re-layout + exact split in one pass)
+      float* pc = planes + poff;
+      poff += ((size_t)24 * (g.F / 16) * TYc * TXc * divup(g.C, TH) * TH + 63) / 64 * 64;
+      filter_planes_rt_launch(bank, pc, TYc * TXc, TH, "conv_dgrad");
+      k.A = pc;
+    } else if (welems > 0) {
+      int nb = (int)((welems + 255) / 256);
+      if (nb > 2048) nb = 2048;
+      (void)filter_planes_shared(nullptr, 0);   // another writer of the aux arena: a shared preparation is forgotten
+      KernelTimer timer("dgrad_filter_kernel", "conv_dgrad", 0.0, 8.0 * welems);
+      hipLaunchKernelGGL(dgrad_filter_kernel, dim3(nb), dim3(256), 0, stream(), filters->data_device, wc, g.F, g.C, g.Ky,
+                         g.Kx, cy, cx, g.sy, g.sx, TYc, TXc, tapm ? 1 : 0);
+    }
+    flops += cflops;
+    if (multi) {
+      ct.c[ct.n++] = k;
+      continue;
+    }
+    GGParams p = base;
+    p.A = k.A; p.K = k.K; p.GX = k.GX; p.G = k.G; p.TX = k.TX; p.TYX = k.TYX;
+    p.y0 = k.y0; p.x0 = k.x0; p.dy0 = k.dy0; p.dx0 = k.dx0;
+    gg_run<false>(p, vec, dst_elems, tm);
+    blocks += p.row_tiles * p.col_tiles;
   }
   if (multi && ct.n > 0) {
-    t_flops = alg_flops;
-    t_exec = flops;
+    // one launch: the call's whole algorithmic work, and what the classes execute together
     if (pre && patch_classes_ok(base, ct)) {
-      patch_run_classes(base, ct, t_op, t_flops, t_exec);   // the wide tile over 3- and 2-tap rows (patch_gemm.hip: gpv_kernel)
+      patch_run_classes(base, ct, "conv_dgrad", alg_flops, flops);   // the wide tile over 3- and 2-tap rows (patch_gemm.hip: gpv_kernel)
       patched = true;
     } else {
-      gg_run_classes(base, ct, vec);
+      gg_run_classes(base, ct, vec, GGTimer{"conv_dgrad", alg_flops, flops});
     }
     blocks = ct.c[ct.n - 1].tile_end;
   }
   note_kernel(!patched ? "gg_kernel(dgrad)" : convnet_hip_get_patch_mode() >= 3 ? "gpw_kernel(dgrad)" : "gpp_kernel(dgrad)", alg_flops, blocks, 1);
 }
 
-void convDownGemm(cudamat* derivs, cudamat* filters, cudamat* targets, Shape4D* ds, Shape4D* fs, Shape4D* ts, ConvDesc d,
-                  float scaleTargets) {
-  if (park_conv(2, launch_conv_down, derivs, filters, targets, ds, fs, ts, d, scaleTargets)) return;
-  conv_down_impl(derivs, filters, targets, ds, fs, ts, d, scaleTargets, nullptr, 1.0f);
-}
-
 void convDown(cudamat* derivs, cudamat* filters, cudamat* targets, Shape4D* ds, Shape4D* fs, Shape4D* ts, ConvDesc d,
               float scaleTargets) {
   if (park_conv(2, launch_conv_down, derivs, filters, targets, ds, fs, ts, d, scaleTargets)) return;
   conv_down_impl(derivs, filters, targets, ds, fs, ts, d, scaleTargets, nullptr, 1.0f);
+}
+
+void convDownGemm(cudamat* derivs, cudamat* filters, cudamat* targets, Shape4D* ds, Shape4D* fs, Shape4D* ts, ConvDesc d,
+                  float scaleTargets) {
+  convDown(derivs, filters, targets, ds, fs, ts, d, scaleTargets);
 }
 
 void convDownMask(cudamat* derivs, cudamat* filters, cudamat* state, cudamat* targets, Shape4D* ds, Shape4D* fs, Shape4D* ts, ConvDesc d,
@@ -2236,11 +2153,9 @@ static void conv_outp_impl(cudamat* images, cudamat* derivs, cudamat* targets, c
   p.nchunk = divup(g.N, WG_NB); p.chunks_total = p.M * p.nchunk;
   p.scaleTargets = scaleTargets; p.scaleOutput = scaleOutput;
   const bool vec = g.N % 4 == 0 && aligned16(p.src) && aligned16(p.dout);
-  t_op = "conv_wgrad";
-  t_flops = 2.0 * g.N * p.M * (double)g.F * p.K;
-  t_exec = 0.0;
-  wg_launch(p, vec);
-  note_kernel("wg_kernel(wgrad)", 2.0 * g.N * p.M * (double)g.F * p.K, p.k_tiles * p.f_tiles, p.splits);
+  const GGTimer tm{"conv_wgrad", 2.0 * g.N * p.M * (double)g.F * p.K, 0.0};
+  wg_launch(p, vec, tm);
+  note_kernel("wg_kernel(wgrad)", tm.flops, p.k_tiles * p.f_tiles, p.splits);
   if (bias_grad && !p.bias_dst) {
     // the tile had no spare row: db = scaleTargets*db + scaleOutput * colsum over (N*M, F) view of derivs
     cudamat view = *derivs;
@@ -2304,20 +2219,18 @@ static int dot_impl(cudamat* mat1, cudamat* mat2, cudamat* bias, cudamat* target
     if (mask && numel(mask) != numel(target)) return ERROR_INCOMPATIBLE_DIMENSIONS;
     p.mask = mask ? mask->data_device : nullptr; p.post_scale = post_scale;
     const bool base_vec = m % 4 == 0 && aligned16(p.src) && aligned16(p.dst) && aligned16(p.A) && aligned16(p.mask);
-    t_op = t2 ? "fc_fprop" : "fc_dgrad";
-    t_flops = 2.0 * m * (double)n * K;
-    t_exec = 0.0;
+    const GGTimer tm{t2 ? "fc_fprop" : "fc_dgrad", 2.0 * m * (double)n * K, 0.0};
     // the 128-row x 64-column tile of a small per-GPU batch, for layers that fill its rows: an FC head with few outputs (R <= 64)
     // keeps the 32- / 64-row tiles instead of padding to 128 rows
     p.skinny = m <= 128 && n > 64 && !CHIP_DIAG_KNOB("CONVNET_GG_NO_SKINNY", 0);
     if (t2) {   // NT: A[r=f + F*k=d]
       const bool v = base_vec && n % 4 == 0;
       if (v && !p.skinny && ggp_shape_ok(n, K)) p.KC = K;   // one tap: tap-major IS channel-major, no re-layout
-      gg_run<false>(p, v, (size_t)m * n);
+      gg_run<false>(p, v, (size_t)m * n, tm);
     } else {    // NN: A[k=f + F*r=d]
-      gg_run<true>(p, base_vec && K % 4 == 0 && mat2->size[0] % 4 == 0, (size_t)m * n);
+      gg_run<true>(p, base_vec && K % 4 == 0 && mat2->size[0] % 4 == 0, (size_t)m * n, tm);
     }
-    note_kernel(t2 ? "gg_kernel(fc NT)" : "gg_kernel(fc NN)", 2.0 * m * (double)n * K, p.row_tiles * p.col_tiles, p.splits);
+    note_kernel(t2 ? "gg_kernel(fc NT)" : "gg_kernel(fc NN)", tm.flops, p.row_tiles * p.col_tiles, p.splits);
     return launch_status();
   }
   if (t1 && !t2) {
@@ -2330,11 +2243,9 @@ static int dot_impl(cudamat* mat1, cudamat* mat2, cudamat* bias, cudamat* target
     p.nchunk = divup(K, WG_NB); p.chunks_total = p.nchunk;
     p.scaleTargets = beta; p.scaleOutput = alpha;
     const bool vec = K % 4 == 0 && aligned16(p.src) && aligned16(p.dout);
-    t_op = "fc_wgrad";
-    t_flops = 2.0 * m * (double)n * K;
-    t_exec = 0.0;
-    wg_launch(p, vec);
-    note_kernel("wg_kernel(fc TN)", 2.0 * m * (double)n * K, p.k_tiles * p.f_tiles, p.splits);
+    const GGTimer tm{"fc_wgrad", 2.0 * m * (double)n * K, 0.0};
+    wg_launch(p, vec, tm);
+    note_kernel("wg_kernel(fc TN)", tm.flops, p.k_tiles * p.f_tiles, p.splits);
     return launch_status();
   }
   return ERROR_UNSUPPORTED;   // unreachable: every transpose combination is handled above

@@ -1773,8 +1773,7 @@ inline WidePlan wide_plan(const GGParams& p, size_t dst_elems, int slots) {
     int best_sp = 1;
     double best_t = 1e30;
     for (int sp = 1; sp <= 16 && tiles * sp <= slots && (sp == 1 || (dst_elems > 0 && kchunks / sp >= 8 && nsc / sp >= 1)); ++sp) {
-      double t = (fl / sp) / block_rate;
-      if (sp > 1) t += sizeof(float) * (double)dst_elems * (2.0 * sp + 1) / 4.0e12 + 4e-6;
+      const double t = gg_split_time(tiles, sp, slots, fl, block_rate, dst_elems);   // (one round)
       if (t < best_t * 0.97) {
         best_t = t;
         best_sp = sp;
@@ -1784,20 +1783,7 @@ inline WidePlan wide_plan(const GGParams& p, size_t dst_elems, int slots) {
     const double fill = (double)tiles * sp / slots;
     if (fill >= (wide_is_var(p) ? 0.85 : sp > 1 ? 0.60 : 0.75)) return {sp, true};
   }
-  int splits = 1;
-  if (dst_elems > 0 && kchunks >= 16) {
-    double best_t = 1e30;
-    for (int sp = 1; sp <= 16 && kchunks / sp >= 8 && nsc / sp >= 1; ++sp) {
-      const double rounds = std::ceil(tiles * (double)sp / slots);
-      double t = rounds * (fl / sp) / block_rate;
-      if (sp > 1) t += sizeof(float) * (double)dst_elems * (2.0 * sp + 1) / 4.0e12 + 4e-6;
-      if (t < best_t * 0.97) {
-        best_t = t;
-        splits = sp;
-      }
-    }
-  }
-  splits = finish(splits);
+  const int splits = finish(gg_split_k(tiles, slots, fl, block_rate, dst_elems, kchunks, nsc));
   const long long blocks = (long long)tiles * splits;
   const long long rounds = (blocks + slots - 1) / slots;
   const bool fill = (double)blocks >= 0.85 * (double)(rounds * slots) || (splits == 1 && rounds >= 4);   // (many rounds: the tail split evens the last)
@@ -1894,23 +1880,9 @@ void patch_run(GGParams& p, size_t dst_elems, const char* op, double flops, cons
   const int nsc = CB * TYn * p.ng;                    // superchunks of a whole reduction
   const int kchunks = CB * p.TYX;                     // 16-deep chunks
   const double block_rate = 230e12 / slots;
+  const double fl = 2.0 * ROWS * (double)TCOLS * (double)p.K;   // per tile, all K
   // split-K by wave quantisation, as gg_launch_cfg; the unit of a K-range is the superchunk
-  int splits = 1;
-  if (wide) {
-    splits = wide_plan(p, dst_elems, slots).splits;
-  } else if (dst_elems > 0 && kchunks >= 16) {
-    const double fl = 2.0 * ROWS * (double)TCOLS * (double)p.K;
-    double best_t = 1e30;
-    for (int sp = 1; sp <= 16 && kchunks / sp >= 8 && nsc / sp >= 1; ++sp) {
-      const double rounds = std::ceil(tiles * (double)sp / slots);
-      double t = rounds * (fl / sp) / block_rate;
-      if (sp > 1) t += sizeof(float) * (double)dst_elems * (2.0 * sp + 1) / 4.0e12 + 4e-6;
-      if (t < best_t * 0.97) {
-        best_t = t;
-        splits = sp;
-      }
-    }
-  }
+  int splits = wide ? wide_plan(p, dst_elems, slots).splits : gg_split_k(tiles, slots, fl, block_rate, dst_elems, kchunks, nsc);
   p.chunks_per_split = divup(nsc, splits);
   splits = divup(nsc, p.chunks_per_split);
   p.splits = splits;
@@ -1918,30 +1890,12 @@ void patch_run(GGParams& p, size_t dst_elems, const char* op, double flops, cons
   p.partial = splits > 1 ? static_cast<float*>(workspace(sizeof(float) * dst_elems * splits)) : nullptr;
   p.tail_splits = 1;
   p.tail_partial = nullptr;
-  if (splits == 1 && dst_elems > 0 && tiles > slots && tiles % slots != 0 && kchunks >= 32) {
-    const int full = (tiles / slots) * slots, rem = tiles - full;
-    const double tile_bytes = sizeof(float) * (double)ROWS * TCOLS;
-    const double t_round = 2.0 * ROWS * (double)TCOLS * (double)p.K / block_rate;
-    double best = 0.95;
-    int best_s = 1;
-    for (int s = 2; s <= 8 && kchunks / s >= 8; ++s) {
-      const double cost = std::ceil(rem * (double)s / slots) / s + (rem * (s + 1.0) * tile_bytes / 4.0e12 + 6e-6) / t_round;
-      if (cost < best) {
-        best = cost;
-        best_s = s;
-      }
-    }
+  if (splits == 1 && dst_elems > 0 && gg_partial_last_round(tiles, slots, kchunks)) {
+    int best_s = gg_tail_split(tiles, slots, fl, block_rate, ROWS * TCOLS, kchunks);
 #ifdef CONVNET_EMU
     if (const char* e = getenv("CONVNET_EMU_TAIL")) best_s = atoi(e);   // tests/emu: the cost model never picks it at emulation sizes
 #endif
-    if (best_s > 1) {
-      p.tail_first = full;
-      p.tail_cps = divup(nsc, best_s);
-      p.tail_splits = divup(nsc, p.tail_cps);
-      p.tail_tf8 = full / 8;
-      p.tail_tt8 = divup(rem * p.tail_splits, 8);
-      p.tail_partial = static_cast<float*>(workspace(sizeof(float) * (size_t)rem * p.tail_splits * ROWS * TCOLS));
-    }
+    if (best_s > 1) gg_set_tail(p, tiles, slots, nsc, best_s, ROWS * TCOLS);
   }
   dim3 grid(p.tail_splits > 1 ? 8 * (p.tail_tf8 + p.tail_tt8) : ((tiles + 7) / 8) * 8, splits);
   static const GGClassTable kNone = {};

@@ -26,6 +26,7 @@ import oracle  # noqa: E402
 from oracle import Geom  # noqa: E402
 from golden_cases import rel_err  # noqa: E402
 from fp64_ref import ref_up as _ref_up, ref_down as _ref_down, ref_outp as _ref_outp  # noqa: E402
+from gemm_launch_trace import alex_geoms as _alex_geoms  # noqa: E402
 
 TOL = 1e-4
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -177,21 +178,6 @@ def test_config0_and_config1_nets_at_their_batch_sizes(gpu, which, N, fused):
 
 
 # ---- per-layer, exact AlexNet sizes, N = 256 -----------------------------------------------------------------------------
-def _alex_geoms(N=256):
-    """The conv geometries of the real model at N images, read off the built graph."""
-    from convnet_amd import models, pbtxt
-    from convnet_amd.edge import ConvEdge
-    from convnet_amd.convnet import ConvNet
-    net = ConvNet(pbtxt.parse(models.alexnet()))
-    out = {}
-    for e in net.edges_:
-        if isinstance(e, ConvEdge):
-            s, d = e.GetSource(), e.conv_desc_
-            out[e.GetDest().GetName()] = Geom(N, s.GetNumChannels(), s.GetSizeY(), s.GetSizeX(), d.num_output_channels, d.kernel_size_y,
-                                              d.kernel_size_x, d.stride_y, d.stride_x, -d.padding_y, -d.padding_x)
-    return out
-
-
 def _dot64(a, b, chunk=1 << 24):
     a, b = a.reshape(-1), b.reshape(-1)
     return float(sum(np.dot(a[i:i + chunk].astype(np.float64), b[i:i + chunk].astype(np.float64)) for i in range(0, a.size, chunk)))

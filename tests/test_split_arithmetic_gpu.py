@@ -31,6 +31,8 @@ pytestmark = pytest.mark.gpu
 
 import oracle  # noqa: E402
 from oracle import Geom  # noqa: E402
+from gemm_launch_trace import (both_paths as _both_paths, run_case as _run_case, call_conv_fprop, call_conv_dgrad,  # noqa: E402
+                               call_conv_wgrad, call_dot)
 
 BF16_MAX = np.array([0x7F7F0000], np.uint32).view(np.float32)[0]         # 3.3895314e38
 BF16_RNE_LIMIT = np.array([0x7F7F7FFF], np.uint32).view(np.float32)[0]   # 3.3961773e38: the largest fp32 that rounds to a finite bf16
@@ -63,19 +65,6 @@ def _check(tag, kind, es, ef, table, bound=None):
     assert np.isfinite(es) and np.isfinite(ef), (tag, kind, es, ef)
     assert es <= cap * u, (tag, kind, "absolute cap", es / u, cap)
     assert es <= max(ratio * ef, floor * u), (tag, kind, "ratio to the fp32 path", es / u, ef / u, ratio)
-
-
-def _both_paths(fn):
-    """fn() on the bf16-split path and on the fp32-instruction path."""
-    from convnet_amd import _lib
-    out = {}
-    try:
-        for name, v in (("split", 1), ("fp32", 0)):
-            _lib.lib.convnet_hip_set_matrix_path(v)
-            out[name] = fn()
-    finally:
-        _lib.lib.convnet_hip_set_matrix_path(1)
-    return out["split"], out["fp32"]
 
 
 TABLE = []   # every measured row of this process (tools/profile_round.sh copies the -s output into profiles/)
@@ -319,36 +308,6 @@ from split_cases import CASES  # noqa: E402
 ROW_TABLE = []
 
 
-def _run_case(case, fn):
-    """fn() on both paths with the patch / wgrad-tile modes of the row; the split path's timer names"""
-    from convnet_amd import _lib
-    names = set()
-    pm, wt = _lib.lib.convnet_hip_get_patch_mode(), _lib.lib.convnet_hip_get_wgrad_tile()
-
-    def call():
-        on_split = _lib.lib.convnet_hip_get_matrix_path() == 1
-        if on_split:
-            _lib.profile_report()
-            _lib.profile_enable(True)
-        try:
-            out = fn()
-        finally:
-            if on_split:
-                names.update(r["kernel"] for r in _lib.profile_report())
-                _lib.profile_enable(False)
-        return out
-    try:
-        if case.patch_mode >= 0:
-            _lib.lib.convnet_hip_set_patch_mode(case.patch_mode)
-        if case.wgrad_tile >= 0:
-            _lib.lib.convnet_hip_set_wgrad_tile(case.wgrad_tile)
-        s, f = _both_paths(call)
-    finally:
-        _lib.lib.convnet_hip_set_patch_mode(pm)
-        _lib.lib.convnet_hip_set_wgrad_tile(wt)
-    return s, f, names
-
-
 def _cancel(kind, rng, a, b, axis_a, axis_b):
     """pair the terms of every dot product along (axis_a of a, axis_b of b): a's odd slices repeat the even ones up to 2^-12, b's odd
     slices negate them — the pairs cancel to ~2^-12 of their magnitude.  Each operand is paired over its whole axis; an odd last
@@ -442,8 +401,6 @@ def _conv_wgrad_at(g, x, dy, taps):
 
 
 def _conv_case(hip, case, kind, rng):
-    from convnet_amd.matrix import Matrix
-    from hip_adapter import _desc, _mat
     N, C, H, W, F, Ky, Kx, sy, sx, pad = case.shape
     g = Geom(N=N, C=C, H=H, W=W, F=F, Ky=Ky, Kx=Kx, sy=sy, sx=sx, pady=pad, padx=pad)
     x, w, dy = _data("normal" if kind == "cancellation" else kind, rng, g)
@@ -469,15 +426,7 @@ def _conv_case(hip, case, kind, rng):
         t0 = _scaled(kind, rng, g.out_shape(), _scale_of(x), _scale_of(w), g.K) if case.st else None
         bias = _scaled(kind, rng, (F,), _scale_of(x), _scale_of(w), g.K) if case.entry == "convUpBiasAct" else None
 
-        def fn():
-            X, Wm = hip._act(x, N, W, H, C), _mat(w, F, g.K, (F, Kx, Ky, C))
-            T = hip._act(t0 if t0 is not None else np.zeros(g.out_shape(), np.float32), N, g.Mx, g.My, F)
-            if bias is not None:
-                Matrix.ConvUpBiasAct(X, Wm, _mat(bias, 1, F), T, _desc(g), case.st, bool(case.relu))
-            else:
-                Matrix.ConvUp(X, Wm, T, _desc(g), case.st)
-            return T.ToNumpy().reshape(g.out_shape())
-        ys, yf, names = _run_case(case, fn)
+        ys, yf, names = _run_case(case, lambda: call_conv_fprop(case, g, x, w, t0, bias))
         sums = _conv_fprop_at(g, x, w, opix)
 
         def err(y):
@@ -488,15 +437,7 @@ def _conv_case(hip, case, kind, rng):
         t0 = _scaled(kind, rng, g.in_shape(), _scale_of(dy), _scale_of(w), F * Ky * Kx // (sy * sx)) if case.st else None
         mask = rng.standard_normal(g.in_shape()).astype(np.float32) if case.entry == "convDownMask" else None
 
-        def fn():
-            D, Wm = hip._act(dy, N, g.Mx, g.My, F), _mat(w, F, g.K, (F, Kx, Ky, C))
-            T = hip._act(t0 if t0 is not None else np.zeros(g.in_shape(), np.float32), N, W, H, C)
-            if mask is not None:
-                Matrix.ConvDownMask(D, Wm, hip._act(mask, N, W, H, C), T, _desc(g), case.st, case.post_scale)
-            else:
-                Matrix.ConvDown(D, Wm, T, _desc(g), case.st)
-            return T.ToNumpy().reshape(g.in_shape())
-        ds, df, names = _run_case(case, fn)
+        ds, df, names = _run_case(case, lambda: call_conv_dgrad(case, g, dy, w, t0, mask))
         sums = _conv_dgrad_at(g, dy, w, ipix)
 
         def err(d):
@@ -508,13 +449,7 @@ def _conv_case(hip, case, kind, rng):
     t0 = _scaled(kind, rng, g.filt_shape(), _scale_of(x), _scale_of(dy), M) if case.st else np.zeros(g.filt_shape(), np.float32)
     b0 = _scaled(kind, rng, (F,), 1.0, _scale_of(dy), M)
     with_bias = case.entry == "convOutpBias"
-
-    def fn():
-        from hip_adapter import conv_outp_bias
-        if with_bias:
-            return conv_outp_bias(g, x, dy, t0, b0, case.st, case.so)
-        return hip.conv_outp(g, x, dy, t0, case.st, case.so), None
-    (ws, bs), (wf, bf), names = _run_case(case, fn)
+    (ws, bs), (wf, bf), names = _run_case(case, lambda: call_conv_wgrad(case, g, x, dy, t0, b0))
     sums = _conv_wgrad_at(g, x, dy, taps)
     dyf = dy.astype(np.float64).reshape(F, -1)
     bacc, bmag = dyf.sum(1), np.abs(dyf).sum(1)
@@ -529,8 +464,6 @@ def _conv_case(hip, case, kind, rng):
 
 def _fc_case(hip, case, kind, rng):
     """every output against float64.  numpy layouts: in (D, N), W (D, F), dout (F, N) — the column-major (N, D), (F, D), (N, F)."""
-    from convnet_amd.matrix import Matrix
-    from hip_adapter import _mat
     N, D, F = case.shape
     a = rng.standard_normal((D, N), dtype=np.float32)
     w = rng.standard_normal((D, F), dtype=np.float32) * np.float32(0.05)
@@ -571,29 +504,11 @@ def _fc_case(hip, case, kind, rng):
     bias = _scaled(kind, rng, (rows,), _scale_of(A), _scale_of(B), k) if case.entry == "dotBiasAct" else None
     mask = rng.standard_normal(out_shape).astype(np.float32) if case.entry == "dotMask" else None
 
-    def fn():
-        Am, Bm, T = _mat(A, A.shape[1], A.shape[0]), _mat(B, B.shape[1], B.shape[0]), _mat(t0, out_shape[1], out_shape[0])
-        if case.entry == "dotBiasAct":
-            Matrix.DotBiasAct(Am, Bm, _mat(bias, 1, rows), T, case.st, case.so, ta, tb, bool(case.relu))
-        elif case.entry == "dotMask":
-            _dot_mask(Am, Bm, mask, T, case, out_shape, ta, tb)
-        else:
-            Matrix.Dot(Am, Bm, T, case.st, case.so, ta, tb)
-        return T.ToNumpy().reshape(out_shape)
-    ys, yf, names = _run_case(case, fn)
+    ys, yf, names = _run_case(case, lambda: call_dot(case, A, B, t0, out_shape, ta, tb, bias, mask))
 
     def err(y):
         return _epilogue_err(y, exact, mag, case, t0 if case.st else None, None if bias is None else bias[:, None], mask)
     return err(ys), err(yf), names
-
-
-def _dot_mask(Am, Bm, mask, T, case, out_shape, ta, tb):
-    from convnet_amd._lib import lib
-    from hip_adapter import _mat
-    am = Am.GetMatTranspose() if ta else Am.GetMat()
-    bm = Bm.GetMatTranspose() if tb else Bm.GetMat()
-    rc = lib.dotMask(am, bm, _mat(mask, out_shape[1], out_shape[0]).GetMat(), T.GetMat(), float(case.st), float(case.so), float(case.post_scale))
-    assert rc == 0, rc
 
 
 def _local_case(case, kind, rng):
