@@ -40,7 +40,7 @@ class LayerPlan(NamedTuple):
     output_entry: Optional[Callable]   # train: the state keeps the logits for this entry (activation + loss derivative + metric, ComputeDeriv)
     logistic_dropout: bool             # train: LogisticDropout instead of ApplyActivation + ApplyDropout (a logistic layer never stores its noise)
     dropout_scale: float               # Layer.TrainDropoutScale()
-    down_scale: Optional[float]        # ComputeDown's post-scale: ReLU' and dropout' ride in the only outgoing edge's epilogue (None: they do not)
+    down_scale: Optional[float]        # ComputeDown's post-scale: ReLU' and dropout' ride in the outgoing edges' epilogues (None: they do not)
     logistic_deriv: bool               # LogisticDerivScaled instead of ApplyDerivativeofDropout + ApplyDerivativeOfActivation
 
 
@@ -137,11 +137,11 @@ class ConvNet(TrainLoopMixin):
                 if l.GetName() == e.GetSourceName():
                     l.AddOutgoing(e)
                     e.SetSource(l)
-                    e.SetInputChannels(l.GetNumChannels())
+                    e.SetInputChannels(l.GetNumChannels(e.GetSourceSliceName()))
                 if l.GetName() == e.GetDestName():
                     l.AddIncoming(e)
                     e.SetDest(l)
-                    e.SetOutputChannels(l.GetNumChannels())
+                    e.SetOutputChannels(l.GetNumChannels(e.GetDestSliceName()))
         self.Sort()
         # the edges, the layers and their optimizers all switch on ``fused`` (fused host: the plain steps, a batch-normalised layer's
         # gamma / beta steps included, are planned into the step's one multi launch, PlanFusedStep)
@@ -153,6 +153,7 @@ class ConvNet(TrainLoopMixin):
         for l in self.layers_:
             if l.UseBatchNormalization():
                 self._check_batch_norm(l)
+            self._check_slices(l)
             if not l.incoming_edge_:
                 self.input_layers_.append(l)
                 self.data_layers_.append(l)
@@ -175,6 +176,10 @@ class ConvNet(TrainLoopMixin):
             if t > 1 and l.UseBatchNormalization():
                 # the (-1, C) view of the state groups by channel only for one frame (time is the outermost index)
                 raise SystemExit(f"batch_normalize on layer {l.GetName()}: not supported on a layer with image_size_t > 1 ({t} frames)")
+            if t > 1 and l.HasSlices():
+                # the reference cuts pixels * T * channels contiguous columns, which is no channel range of a time-major tensor
+                raise SystemExit(f"layer_slice on layer {l.GetName()}: not supported on a layer with image_size_t > 1 ({t} frames): "
+                                 "time is the outermost index, so a channel range is not one column range")
             self.log(f"Layer {l.GetName()}: {y}x{x}")
             for e in l.outgoing_edge_:
                 e.SetImageSize(y, x, t)
@@ -199,9 +204,11 @@ class ConvNet(TrainLoopMixin):
             if isinstance(e, MaxPoolEdge):
                 # the mask pair equals the reference's MaxPoolUndo only if backprop sees the raw maxima (edge.MaxPoolEdge)
                 e.mask_legal_ = l.dropprob_ == 0 and type(l) in (LinearLayer, ReLULayer)
-        # forward.  The only incoming edge's epilogue takes the bias, and the ReLU unless batch normalisation sits in between; a sigmoid
-        # is a pass of its own, a softmax layer takes the reference's calls
-        fuse_up = fused and len(l.incoming_edge_) == 1 and not isinstance(l, SoftmaxLayer) and l.incoming_edge_[0].CanFuseUp(l)
+        # forward.  The incoming edges' epilogues take the bias, and the ReLU unless batch normalisation sits in between, when every one of
+        # them is the only writer of its destination — the whole layer, or a slice of a layer whose written slices are all of it; a
+        # sigmoid is a pass of its own, a softmax layer takes the reference's calls.  All or nothing per layer
+        fuse_up = (fused and self._each_alone_and_all_of(l, [e.GetDestSliceName() for e in l.incoming_edge_])
+                   and not isinstance(l, SoftmaxLayer) and all(e.CanFuseUp(l) for e in l.incoming_edge_))
         activate = not fused if bn else not l.IsInput() and (not fuse_up or logistic)
         # output: softmax always; logistic and softmax-distribution for a single output without dropout whose loss and metric are the
         # ones the entry computes.  Anything else runs the reference's calls
@@ -215,15 +222,46 @@ class ConvNet(TrainLoopMixin):
             elif single and isinstance(l, SoftmaxDistLayer) and l.loss_function_ == l.performance_metric_ == "CROSS_ENTROPY_MULTINOMIAL_DISTRIBUTED":
                 entry = Matrix.SoftmaxDistCEGrad
         # backward.  The reference applies dropout' and ReLU' after ALL outgoing edges have accumulated (src/convnet.cc:390-404), so they
-        # ride in a ComputeDown epilogue only with exactly one edge; a max-pool undo masks but does not scale
+        # ride in the ComputeDown epilogues only where every edge is the only reader of what it reads — the whole layer, or a slice of a
+        # layer whose read slices are all of it; a max-pool undo masks but does not scale
         down_scale = None
-        if fused and hidden and l.is_relu and len(l.outgoing_edge_) == 1:
-            e = l.outgoing_edge_[0]
-            if e.can_fuse_mask and not e.IsBackPropBlocked() and not l.store_dropout_noise_ and not (isinstance(e, MaxPoolEdge) and scale != 1.0):
+        if fused and hidden and l.is_relu and self._each_alone_and_all_of(l, [e.GetSourceSliceName() for e in l.outgoing_edge_]):
+            if all(e.can_fuse_mask and not e.IsBackPropBlocked() and not l.store_dropout_noise_
+                   and not (isinstance(e, MaxPoolEdge) and scale != 1.0) for e in l.outgoing_edge_):
                 down_scale = scale
         return LayerPlan(fuse_relu=(l.is_relu and not bn) if fuse_up else None, bn_relu=(fused and l.is_relu) if bn else None,
                          activate=activate, output_entry=entry, logistic_dropout=fused and logistic and not l.IsInput() and l.dropprob_ > 0,
                          dropout_scale=scale, down_scale=down_scale, logistic_deriv=fused and logistic and hidden)
+
+    @staticmethod
+    def _each_alone_and_all_of(l, slice_names):
+        """Whether the edges that name these slices of layer l ("" = the whole layer) each have theirs to themselves and together touch
+        every channel of l: one edge on the whole layer, or one edge per slice of a layer that has no channels outside its slices."""
+        if slice_names == [""]:
+            return True
+        if not slice_names:
+            return False
+        return (len(set(slice_names)) == len(slice_names) and set(slice_names) == set(l.slice_channels_)
+                and l.GetNumChannels() == sum(l.slice_channels_.values()))
+
+    @staticmethod
+    def _check_slices(l):
+        """The supported set of sliced layers; anything else stops with the reason."""
+        name = l.GetName()
+        for what, edges, get in (("read", l.outgoing_edge_, Edge.GetSourceSliceName), ("written", l.incoming_edge_, Edge.GetDestSliceName)):
+            whole = [e.GetName() for e in edges if not get(e)]
+            part = [e.GetName() for e in edges if get(e)]
+            if whole and part:
+                # the whole-layer flag and the slice flags are independent (src/layer.cc:307-327): the second writer overwrites where it
+                # should add, and in Bprop the second reader's gradient replaces the first's
+                raise SystemExit(f"layer_slice on layer {name}: the layer is {what} both whole (edge {whole[0]}) and by slice (edge {part[0]}); "
+                                 "their add-or-overwrite flags are independent, so one would overwrite what the other has written")
+        if l.UseBatchNormalization():
+            if l.HasSlices():
+                raise SystemExit(f"batch_normalize on layer {name}: not supported on a layer with slices")
+            for e in l.incoming_edge_:
+                if e.GetSourceSliceName():
+                    raise SystemExit(f"batch_normalize on layer {name}: not supported on a layer fed from a slice (edge {e.GetName()})")
 
     @staticmethod
     def _check_batch_norm(l):
@@ -338,7 +376,8 @@ class ConvNet(TrainLoopMixin):
             p = self.plan_[l]
             for e in l.incoming_edge_:
                 overwrite = l.AddOrOverwriteState(e.GetDestSliceName())
-                e.ComputeUp(e.GetSource().GetState(), l.GetState(), overwrite, train, fuse_relu=p.fuse_relu)
+                e.ComputeUp(e.GetSource().GetState(e.GetSourceSliceName()), l.GetState(e.GetDestSliceName()), overwrite, train,
+                            fuse_relu=p.fuse_relu)
             if p.bn_relu is not None:
                 l.ApplyBatchNormalization(train, relu=p.bn_relu)   # src/convnet.cc:382-384
             if train and p.output_entry is not None:
@@ -365,11 +404,15 @@ class ConvNet(TrainLoopMixin):
         # owner's slice (edge_with_weight.cc:66-90), so the slice is final only when the last sharing edge has added its part —
         # whichever of them comes last in backward order.
         owner = edge.tied_edge_ if edge.IsTied() else edge
+        # the edge works on the slices it names ("" = the whole layer): src/convnet.cc:364-367
+        src_slice, dst_slice = edge.GetSourceSliceName(), edge.GetDestSliceName()
+        input_state, output_state = input.GetState(src_slice), output.GetState(dst_slice)
+        output_deriv = output.GetDeriv(dst_slice)
 
         def dgrad():
             if not input.IsInput():
-                overwrite = input.AddOrOverwriteDeriv(edge.GetSourceSliceName())
-                edge.ComputeDown(output.GetDeriv(), input.GetState(), output.GetState(), input.GetDeriv(), overwrite, fuse_mask=fuse_mask)
+                overwrite = input.AddOrOverwriteDeriv(src_slice)
+                edge.ComputeDown(output_deriv, input_state, output_state, input.GetDeriv(src_slice), overwrite, fuse_mask=fuse_mask)
 
         if side and self.overlap_wgrad_ and isinstance(edge, EdgeWithWeight):
             # weight gradient on the second stream, behind everything enqueued so far (the derivative it reads); the all-reduce of
@@ -383,14 +426,14 @@ class ConvNet(TrainLoopMixin):
             here.record(torch.cuda.current_stream())
             self.side_stream_.wait_event(here)
             with Matrix.OnStream(self.side_stream_):
-                edge.ComputeOuter(input.GetState(), output.GetDeriv())
+                edge.ComputeOuter(input_state, output_deriv)
                 complete = isinstance(owner, EdgeWithWeight) and owner.GetNumGradsReceived() >= owner.num_shares_
                 if self.exchange_ is not None and owner in self.edge_slices_ and complete:
                     self.exchange_.GradReady(owner)
             if not late:
                 dgrad()
         else:
-            edge.ComputeOuter(input.GetState(), output.GetDeriv())
+            edge.ComputeOuter(input_state, output_deriv)
             complete = isinstance(owner, EdgeWithWeight) and owner.GetNumGradsReceived() >= owner.num_shares_
             if self.exchange_ is not None and owner in self.edge_slices_ and complete:
                 self.exchange_.GradReady(owner)     # the slice is final: start its all-reduce

@@ -71,6 +71,8 @@ class Edge:
         self.dest_ = None
         self.source_node_ = c.source
         self.dest_node_ = c.dest
+        self.source_node_slice_ = c.source_slice   # the slice of the source layer this edge reads, of the destination it writes;
+        self.dest_node_slice_ = c.dest_slice       # "" = the whole layer (layer.py)
         self.tied_edge_name_ = c.tied_to
         self.tied_edge_ = None
         self.num_input_channels_ = 0
@@ -83,10 +85,10 @@ class Edge:
         self.grad_check_ = c.grad_check
         self.grad_check_num_params_ = c.grad_check_num_params
         self.grad_check_epsilon_ = list(c.grad_check_epsilon)
-        self.name_ = f"{self.source_node_}:{self.dest_node_}"
+        # src/edge.cc:150-155: <source>[_<slice>]:<dest>[_<slice>]
+        self.name_ = ":".join(n + ("_" + sl if sl else "") for n, sl in ((self.source_node_, self.source_node_slice_),
+                                                                         (self.dest_node_, self.dest_node_slice_)))
         self.fused = False
-        if c.source_slice or c.dest_slice:
-            raise SystemExit("layer slices are out of hot-path scope")
 
     def GetDescription(self):
         return "Default edge."
@@ -164,10 +166,10 @@ class Edge:
         return self.dest_node_
 
     def GetSourceSliceName(self):
-        return ""
+        return self.source_node_slice_
 
     def GetDestSliceName(self):
-        return ""
+        return self.dest_node_slice_
 
     def GetName(self):
         return self.name_
@@ -278,15 +280,24 @@ class EdgeWithWeight(Edge):
         if self.bias_optimizer_:
             self.bias_optimizer_.ReduceLearningRate(factor)
 
+    def _checkpoint_prefix(self):
+        """The prefix of this edge's datasets in a checkpoint.  The reference's is <source>:<dest> (src/edge_with_weight.cc:27-64),
+        kept for every edge on whole layers: their files stay the reference's.  It does not tell the groups of a grouped convolution
+        apart (two edges between the same two layers), so an edge that names a slice uses its name, <source>[_<slice>]:<dest>[_<slice>]
+        — the reference cannot write a checkpoint of such a net, so there is no file of its to stay compatible with."""
+        if self.source_node_slice_ or self.dest_node_slice_:
+            return self.name_
+        return f"{self.source_node_}:{self.dest_node_}"
+
     def SaveParameters(self, file):
-        # src/edge_with_weight.cc:27-40: "<source>:<dest>:weight" / ":bias" + the optimizers' state under the same prefix
+        # src/edge_with_weight.cc:27-40: "<prefix>:weight" / ":bias" + the optimizers' state under the same names
         if self.is_tied_:
             return
-        name = f"{self.source_node_}:{self.dest_node_}:weight"
+        name = f"{self._checkpoint_prefix()}:weight"
         self.weights_.WriteHDF5(file, name)
         self.weight_optimizer_.SaveParameters(file, name)
         if not self.has_no_bias_:
-            name = f"{self.source_node_}:{self.dest_node_}:bias"
+            name = f"{self._checkpoint_prefix()}:bias"
             self.bias_.WriteHDF5(file, name)
             self.bias_optimizer_.SaveParameters(file, name)
 
@@ -294,7 +305,7 @@ class EdgeWithWeight(Edge):
         # src/edge_with_weight.cc:42-64 (optimizer state only if the optimizer has been allocated, i.e. when training)
         if self.is_tied_:
             return
-        edge_name = edge_name or f"{self.source_node_}:{self.dest_node_}"
+        edge_name = edge_name or self._checkpoint_prefix()
         self.weights_.ReadHDF5(file, f"{edge_name}:weight")
         if self.weight_optimizer_.IsAllocated():
             self.weight_optimizer_.LoadParameters(file, f"{edge_name}:weight")
@@ -782,7 +793,10 @@ class MaxPoolEdge(_PoolEdge):
             if Matrix.ConvMaxPoolMask(input, output, self.mask_, self.conv_desc_):
                 self.mask_for_ = (input.mat_.data_device, output.mat_.data_device, output.GetRows())
                 return
-            self.mask_refused_.add(key)   # refused by geometry and batch (the alignment it also checks holds for whole layer buffers)
+            # refused by geometry and batch.  The 16-byte alignment it also checks holds for whole layer buffers, and for the slices
+            # of a layer whenever the batch is a multiple of 4 (a slice starts batch * pixels * channels floats in) — which the
+            # kernel asks for anyway; the key holds for this edge's own matrices, which never change
+            self.mask_refused_.add(key)
             self.mask_ = None
         Matrix.ConvMaxPool(input, output, self.conv_desc_)
 

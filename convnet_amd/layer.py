@@ -1,6 +1,11 @@
 """Layers — mirror of src/layer.{h,cc} for the hot path: Linear / ReLU / Logistic / Softmax / Softmax-distribution layers with
-binary dropout, batch normalisation, their losses and metrics.  Slices, Gaussian dropout and the model-parallel state copies are
-out of scope."""
+binary dropout, batch normalisation, their losses and metrics, and layer slices (``layer_slice``): named channel ranges of one layer
+that edges read (``source_slice``) or write (``dest_slice``) on their own — grouped convolutions and channel concatenation.  In the
+CHWN layout a channel range is a contiguous column range, so a slice is a get_slice view of the state and of the derivative with its
+own Shape4D and its own add-or-overwrite flags; the slices lie in NAME order from column 0 (the reference keeps them in std::maps), a
+non-zero ``num_channels`` of the layer itself sits behind the last slice.  Layer-level passes (activation, dropout, loss) stay on the
+whole layer.  DESIGN.md §2.9 has the supported and the refused sets.  Gaussian dropout and the model-parallel state copies are out of
+scope."""
 import numpy as np
 
 from .loss_functions import LossFunction
@@ -49,10 +54,18 @@ class Layer:
         self.deriv_ = Matrix()
         self.data_ = Matrix()
         self.dropout_noise_ = Matrix()
-        self.add_or_overwrite_state_ = True
-        self.add_or_overwrite_deriv_ = True
-        if config.layer_slice or self.gaussian_dropout_:
-            raise SystemExit("layer_slice / gaussian_dropout are out of hot-path scope")
+        if self.gaussian_dropout_:
+            # (the reference runs it on a noise matrix it never allocates for every layer class that clears store_dropout_noise_)
+            raise SystemExit(f"gaussian_dropout on layer {self.name_} is out of hot-path scope")
+        # slices: src/layer.cc:66-73.  name -> channels in NAME order (std::map), which is also the order of their columns
+        self.slice_channels_ = {}
+        for s in config.layer_slice:
+            self.slice_channels_[s.name] = s.num_channels
+            self.num_channels_ += s.num_channels
+        self.slice_channels_ = dict(sorted(self.slice_channels_.items()))
+        self.state_slices_, self.deriv_slices_ = {}, {}
+        self.add_or_overwrite_state_ = {n: True for n in ("", *self.slice_channels_)}
+        self.add_or_overwrite_deriv_ = dict(self.add_or_overwrite_state_)
         # batch normalisation (src/layer.cc:60-64; the optimizer configs were merged with the model's defaults by ConvNet)
         self.batch_normalize_ = bool(config.batch_normalize)
         self.bn_f_ = config.bn_f
@@ -77,8 +90,29 @@ class Layer:
     def GetName(self):
         return self.name_
 
+    def _no_slice(self, slice_):
+        raise SystemExit(f"Layer {self.name_} does not contain a slice called {slice_}")
+
     def GetNumChannels(self, slice_=""):
-        return self.num_channels_
+        # src/layer.cc:334-348
+        if not slice_:
+            return self.num_channels_
+        if slice_ not in self.slice_channels_:
+            self._no_slice(slice_)
+        return self.slice_channels_[slice_]
+
+    def HasSlices(self):
+        return bool(self.slice_channels_)
+
+    def GetSliceChannelRange(self, slice_):
+        """(first channel, one past the last) of a slice: name order from channel 0 (SetupSlices)."""
+        if slice_ not in self.slice_channels_:
+            self._no_slice(slice_)
+        start = 0
+        for n, c in self.slice_channels_.items():
+            if n == slice_:
+                return start, start + c
+            start += c
 
     def IsInput(self):
         return self.is_input_
@@ -99,28 +133,42 @@ class Layer:
         self.image_size_y_, self.image_size_x_, self.image_size_t_ = y, x, t
 
     def GetState(self, slice_=""):
-        return self.state_
+        # src/layer.cc:294-305
+        if not slice_:
+            return self.state_
+        if slice_ not in self.state_slices_:
+            self._no_slice(slice_)
+        return self.state_slices_[slice_]
 
     def GetDeriv(self, slice_=""):
-        return self.deriv_
+        if not slice_:
+            return self.deriv_
+        if slice_ not in self.deriv_slices_:
+            self._no_slice(slice_)
+        return self.deriv_slices_[slice_]
 
     def GetData(self):
         return self.data_
 
-    # add-or-overwrite bookkeeping: src/layer.cc:307-332
+    # add-or-overwrite bookkeeping: src/layer.cc:307-332.  One flag for the whole layer ("") and one per slice, independent of each other
     def AddOrOverwriteState(self, slice_=""):
-        v = self.add_or_overwrite_state_
-        self.add_or_overwrite_state_ = False
+        if slice_ not in self.add_or_overwrite_state_:
+            self._no_slice(slice_)
+        v = self.add_or_overwrite_state_[slice_]
+        self.add_or_overwrite_state_[slice_] = False
         return v
 
     def AddOrOverwriteDeriv(self, slice_=""):
-        v = self.add_or_overwrite_deriv_
-        self.add_or_overwrite_deriv_ = False
+        if slice_ not in self.add_or_overwrite_deriv_:
+            self._no_slice(slice_)
+        v = self.add_or_overwrite_deriv_[slice_]
+        self.add_or_overwrite_deriv_[slice_] = False
         return v
 
     def ResetAddOrOverwrite(self):
-        self.add_or_overwrite_state_ = True
-        self.add_or_overwrite_deriv_ = True
+        for flags in (self.add_or_overwrite_state_, self.add_or_overwrite_deriv_):
+            for n in flags:
+                flags[n] = True
 
     def UseBatchNormalization(self):
         return self.batch_normalize_
@@ -131,7 +179,18 @@ class Layer:
             self.gamma_optimizer_.NotifyStart(self.gamma_)
             self.beta_optimizer_.NotifyStart(self.beta_)
 
-    # ---- memory: src/layer.cc:252-288 ----------------------------------------------------------------
+    # ---- memory: src/layer.cc:238-288 ----------------------------------------------------------------
+    def SetupSlices(self):
+        """src/layer.cc:238-250: slice s is the column range [start, start + pixels * channels_s) of the state and of the derivative."""
+        num_pixels = self.image_size_y_ * self.image_size_x_ * self.image_size_t_
+        batch_size = self.state_.GetRows()
+        for n, c in self.slice_channels_.items():
+            first, last = self.GetSliceChannelRange(n)
+            for whole, views in ((self.state_, self.state_slices_), (self.deriv_, self.deriv_slices_)):
+                v = views[n] = Matrix()
+                whole.GetSlice(v, num_pixels * first, num_pixels * last)
+                v.SetShape4D(batch_size, self.image_size_x_, self.image_size_y_, c * self.image_size_t_)
+
     def AllocateMemory(self, batch_size):
         num_pixels = self.image_size_y_ * self.image_size_x_ * self.image_size_t_
         self.state_.AllocateGPUMemory(batch_size, num_pixels * self.num_channels_, self.name_ + " state")
@@ -159,6 +218,7 @@ class Layer:
             self.sigma_.Set(1)
             for m in (self.grad_gamma_, self.grad_beta_, self.batch_mu_, self.batch_sigma_):
                 m.Set(0)
+        self.SetupSlices()
 
     # ---- batch normalisation: src/layer.cc:452-510 --------------------------------------------------------------------
     def ApplyBatchNormalization(self, train, relu=False):

@@ -17,6 +17,10 @@ text so they can also be written to disk and fed to the reference's own binaries
 * ``multilabel_small()`` — a small multi-label net: conv -> LOGISTIC -> average pool -> FC LOGISTIC -> FC LOGISTIC output of independent
                      yes/no units (CROSS_ENTROPY_BINARY / CLASSIFICATION_BINARY; a negative target means "don't care").
 * ``softdist_small()`` — the same trunk with ReLU and a SOFTMAX_DIST output trained on a target distribution per case.
+* ``alexnet_grouped()`` — ``alexnet()`` with conv2, conv4 and conv5 as two groups each (the two-tower net of the AlexNet paper), written
+                     with layer slices: grouped convolutions.
+* ``inception_small()`` — a small net with one module of three branches (1x1, 3x3, 5x5; as a stride-2 reduction module also a pooled
+                     fourth) concatenated into one layer through ``dest_slice``.
 tests/test_models.py checks the first two against the reference's files when they are mounted.
 """
 
@@ -311,6 +315,80 @@ def softdist_small(image_size=12, num_classes=10, dropprob=0.0, grad_check=False
     out = _layer("output", num_classes, "SOFTMAX_DIST", extra="  loss_function: CROSS_ENTROPY_MULTINOMIAL_DISTRIBUTED\n"
                  "  performance_metric: CROSS_ENTROPY_MULTINOMIAL_DISTRIBUTED\n")
     return _small_head_trunk("softdist_small", "RECTIFIED_LINEAR", dropprob, image_size, out, 1.0, _gc(grad_check, 6))
+
+
+def _slices(**channels):
+    """The layer_slice blocks of a layer (``extra`` of _layer; the layer's own num_channels is then 0): name=channels."""
+    return "".join(f'  layer_slice {{\n    name: "{n}"\n    num_channels: {c}\n  }}\n' for n, c in channels.items())
+
+
+def _on(edge, source_slice="", dest_slice=""):
+    """The same edge reading ``source_slice`` of its source layer and / or writing ``dest_slice`` of its destination."""
+    extra = (f'  source_slice: "{source_slice}"\n' if source_slice else "") + (f'  dest_slice: "{dest_slice}"\n' if dest_slice else "")
+    head, sep, tail = edge.rpartition("}")
+    return head + extra + sep + tail
+
+
+def alexnet_grouped(image_size=224, num_classes=1000, dropprob=0.4, grad_check=False):
+    """alexnet() with conv2, conv4 and conv5 in two groups each, as the two GPUs of the AlexNet paper had them: each half of the filters
+    sees half of the input channels (48 -> 128, 192 -> 192, 192 -> 128 per group).  A layer that feeds a grouped convolution is written
+    whole and read by slice ``a`` / ``b`` (hidden1_rnorm, hidden3_conv); a grouped layer is written by slice and read whole by its pool
+    or, by slice again, by the next group (hidden4_conv).  60,944,488 parameters (alexnet(): 62,357,608)."""
+    gc = _gc(grad_check)
+    R = "RECTIFIED_LINEAR"
+    s = _header("CLS_net_grouped")
+    s += _layer("input", 3, size=image_size)
+    s += _layer("hidden1_conv", 96, R) + _layer("hidden1_maxpool", 96) + _layer("hidden1_rnorm", 0, R, extra=_slices(a=48, b=48))
+    s += _layer("hidden2_conv", 0, R, extra=_slices(a=128, b=128)) + _layer("hidden2_maxpool", 256) + _layer("hidden2_rnorm", 256, R)
+    s += _layer("hidden3_conv", 0, R, extra=_slices(a=192, b=192)) + _layer("hidden4_conv", 0, R, extra=_slices(a=192, b=192))
+    s += _layer("hidden5_conv", 0, R, extra=_slices(a=128, b=128)) + _layer("hidden5_maxpool", 256)
+    s += _layer("hidden6", 4096, R, dropprob) + _layer("hidden7", 4096, R, dropprob)
+    s += _layer("output", num_classes, "SOFTMAX")
+    s += _conv("input", "hidden1_conv", 7, 2, 1, grad_check=gc)
+    s += _pool("hidden1_conv", "hidden1_maxpool", 3, 2, 1) + _rnorm("hidden1_maxpool", "hidden1_rnorm")
+    for g in "ab":
+        s += _on(_conv("hidden1_rnorm", "hidden2_conv", 5, 2, 0, init_bias=1.0, grad_check=gc), g, g)
+    s += _pool("hidden2_conv", "hidden2_maxpool", 3, 2, 1) + _rnorm("hidden2_maxpool", "hidden2_rnorm")
+    for g in "ab":   # conv3 sees every channel: one edge per half of ITS filters, so that conv4's groups read slices
+        s += _on(_conv("hidden2_rnorm", "hidden3_conv", 3, 1, 1, grad_check=gc), "", g)
+    for g in "ab":
+        s += _on(_conv("hidden3_conv", "hidden4_conv", 3, 1, 1, init_bias=1.0, grad_check=gc), g, g)
+    for g in "ab":
+        s += _on(_conv("hidden4_conv", "hidden5_conv", 3, 1, 0, init_bias=1.0, grad_check=gc), g, g)
+    s += _pool("hidden5_conv", "hidden5_maxpool", 3, 2, 1)
+    s += _fc("hidden5_maxpool", "hidden6", norm_limit=4, grad_check=gc) + _fc("hidden6", "hidden7", norm_limit=4, grad_check=gc)
+    s += _fc("hidden7", "output", norm_limit=4, grad_check=gc)
+    return s
+
+
+def inception_small(image_size=12, num_classes=10, relu=True, pooled_branch=False, dropprob=0.0, grad_check=False, init_wt=1.0):
+    """A small net with one inception-style module: conv3p1/8 ``stem`` -> {1x1 CONV_ONETOONE / 6, 3x3 p1 / 10, 5x5 p2 / 5} concatenated
+    into one layer ``mix`` (slices ``b1x1``, ``b3x3``, ``b5x5``: every branch writes its own) -> 3x3 s2 pool -> FC softmax.
+    pooled_branch=True makes it a reduction module: the 3x3 and 5x5 branches run at stride 2, a 3x3 s2 p1 pooling edge writes the
+    stem's 8 channels straight into a fourth slice ``pool``, and the 1x1 branch reads a pooled copy of the stem (``stem_pool``).
+    relu=False: LINEAR layers and average pooling (a smooth net, for grad checks)."""
+    gc = _gc(grad_check, 6)
+    act, kind = ("RECTIFIED_LINEAR", "MAXPOOL") if relu else ("LINEAR", "AVERAGE_POOL")
+    widths = dict(b1x1=6, b3x3=10, b5x5=5)
+    stride = 1
+    if pooled_branch:
+        widths["pool"] = 8
+        stride = 2
+    s = _header("inception_small")
+    s += _layer("input", 3, size=image_size)
+    s += _layer("stem", 8, act) + (_layer("stem_pool", 8) if pooled_branch else "")
+    s += _layer("mix", 0, act, dropprob, extra=_slices(**widths)) + _layer("pool", sum(widths.values()))
+    s += _layer("output", num_classes, "SOFTMAX")
+    s += _conv("input", "stem", 3, 1, 1, init_wt=init_wt, grad_check=gc)
+    if pooled_branch:
+        s += _pool("stem", "stem_pool", 3, 2, 1, kind=kind)
+    s += _on(_nin("stem_pool" if pooled_branch else "stem", "mix", init_wt=init_wt, grad_check=gc), "", "b1x1")
+    s += _on(_conv("stem", "mix", 3, stride, 1, init_wt=init_wt, grad_check=gc), "", "b3x3")
+    s += _on(_conv("stem", "mix", 5, stride, 2, init_wt=init_wt, grad_check=gc), "", "b5x5")
+    if pooled_branch:
+        s += _on(_pool("stem", "mix", 3, 2, 1, kind=kind), "", "pool")
+    s += _pool("mix", "pool", 3, 2, kind=kind) + _fc("pool", "output", init_wt=init_wt, grad_check=gc)
+    return s
 
 
 # forward MACs per image of a built net (for roofline accounting): see bench.py
