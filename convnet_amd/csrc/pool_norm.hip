@@ -7,6 +7,7 @@
 // read-once/write-once bytes plus L2-absorbed window overlap.
 #include <cfloat>
 #include <cstdlib>
+#include <initializer_list>
 #include <mutex>
 #include <utility>
 
@@ -1086,7 +1087,20 @@ __global__ void pool3d_undo_kernel(const float* __restrict__ images, const float
 
 namespace {
 
-inline bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// The float4 arm of a kernel: `n` (images per pixel, or locations per channel) a multiple of 4 and every operand 16-byte aligned
+// (an operand the call does not have is passed as nullptr, which counts as aligned)
+inline bool vec4(size_t n, std::initializer_list<const void*> operands) {
+  bool ok = n % 4 == 0;
+  for (const void* p : operands) ok = ok && aligned16(p);
+  return ok;
+}
+
+// What a launch reports through note_kernel: the kernel build and the arm that the grid size cannot show.  convnet_hip_last_kernel_info
+// hands the pointer out, so every name is a string literal; nothing is formatted on the launch path.
+#define ARM_NAME(vec, name) ((vec) ? name "/vec" : name "/scalar")
+#define POOL_NAME(max, vec, kernel) ((max) ? ARM_NAME(vec, kernel "<max>") : ARM_NAME(vec, kernel "<avg>"))
+#define FIXED_NAME(max, kernel, ks) ((max) ? kernel "<max, " ks ">" : kernel "<avg, " ks ">")
+inline void note_launch(const char* name, dim3 grid) { note_kernel(name, 0.0, (int)(grid.x * grid.y * grid.z), 1); }
 
 // Channel segmentation of the response-norm walk: a lane slides its window over `cseg` channels only
 // (its first window is summed directly), so (location quads) x (segments) lanes are in flight instead of
@@ -1107,6 +1121,10 @@ inline int grid_for(size_t items) {
   size_t b = (items + 255) / 256;
   if (b > 4096) b = 4096;
   return b ? (int)b : 1;
+}
+inline dim3 rnorm_walk_grid(size_t locs, int C, int sizeF, int& cseg, int& nseg) {
+  rnorm_segments((locs + 3) / 4, C, sizeF, cseg, nseg);
+  return dim3(grid_for((locs + 3) / 4 * nseg));
 }
 
 // The dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) belongs to the kernel, not to one launch: one instantiation serves
@@ -1154,7 +1172,7 @@ inline unsigned rn_pipe_grid(const void* kernel, unsigned tiles, size_t smem, in
 struct RnFast {
   int CG, LT, threads, SZ;
 };
-inline bool rn_fast_shape(int C, int sizeF, bool blocked, bool vec, bool undo, RnFast& f) {
+inline bool rn_fast_shape(int C, int sizeF, bool blocked, bool vec, RnFast& f) {
   if (!CHIP_KNOB("CONVNET_RNORM_FAST", 1) || blocked || !vec || C < sizeF) return false;
   f.SZ = sizeF;
   if (sizeF == 24) {
@@ -1171,7 +1189,6 @@ inline bool rn_fast_shape(int C, int sizeF, bool blocked, bool vec, bool undo, R
   while (f.LT > 16 && G * f.LT > 512) f.LT /= 2;
   if (f.LT == 128 && f.CG != 24) f.LT = 64;
   f.threads = G * f.LT;
-  (void)undo;
   return f.threads <= 512;
 }
 inline size_t rn_fast_rows(const RnFast& f, int C, bool undo) {
@@ -1180,81 +1197,69 @@ inline size_t rn_fast_rows(const RnFast& f, int C, bool undo) {
   return undo ? (size_t)2 * R + 2 * seg : (size_t)R + C + f.CG + seg;
 }
 
-bool rnorm_fwd_fast(const float* in, float* out, size_t locs, int C, int sizeF, float addScale, float powScale, bool blocked, bool vec, bool relu) {
+// The (LT, CG, SZ) builds of the fast kernels, forward and undo: every shape rn_fast_shape can ask for
+#define RN_FAST_BUILDS(X) X(128, 24, 24) X(64, 12, 24) X(32, 12, 24) X(64, 6, 24) X(32, 6, 24) X(16, 6, 24) X(64, 8, 64) X(32, 8, 64) X(16, 8, 64)
+
+// The call through the fast kernel of its shape (forward: dout is unused; undo: relu is).  false: no build takes it.
+template <bool UNDO>
+bool rnorm_fast(const float* dout, const float* in, float* out, size_t locs, int C, int sizeF, float addScale, float powScale, bool blocked, bool vec,
+                bool relu) {
   RnFast f;
-  if (!rn_fast_shape(C, sizeF, blocked, vec, false, f)) return false;
-  const size_t smem = sizeof(float) * (size_t)f.LT * rn_fast_rows(f, C, false);
+  if (!rn_fast_shape(C, sizeF, blocked, vec, f)) return false;
+  const size_t smem = sizeof(float) * (size_t)f.LT * rn_fast_rows(f, C, UNDO);
   if (smem > 160 * 1024) return false;
   const unsigned tiles = (unsigned)((locs + f.LT - 1) / f.LT);
   const dim3 block(f.threads);
-#define RN_F(L, G, S)                                                                                                           \
-  do {                                                                                                                          \
-    const dim3 grid(rn_pipe_grid((const void*)rnorm_fwd_fast_kernel<L, G, S>, tiles, smem, f.threads));                          \
-    hipLaunchKernelGGL((rnorm_fwd_fast_kernel<L, G, S>), grid, block, smem, stream(), in, out, locs, C, addScale, powScale, relu, tiles); \
-  } while (0)
-  if (f.SZ == 24 && f.CG == 24 && f.LT == 128) RN_F(128, 24, 24);
-  else if (f.SZ == 24 && f.CG == 12 && f.LT == 64) RN_F(64, 12, 24);
-  else if (f.SZ == 24 && f.CG == 12 && f.LT == 32) RN_F(32, 12, 24);
-  else if (f.SZ == 24 && f.CG == 6 && f.LT == 64) RN_F(64, 6, 24);
-  else if (f.SZ == 24 && f.CG == 6 && f.LT == 32) RN_F(32, 6, 24);
-  else if (f.SZ == 24 && f.CG == 6 && f.LT == 16) RN_F(16, 6, 24);
-  else if (f.SZ == 64 && f.LT == 64) RN_F(64, 8, 64);
-  else if (f.SZ == 64 && f.LT == 32) RN_F(32, 8, 64);
-  else if (f.SZ == 64 && f.LT == 16) RN_F(16, 8, 64);
-  else return false;
-#undef RN_F
-  return true;
+#define RN_FAST_TRY(L, G, S)                                                                                                      \
+  if (f.LT == L && f.CG == G && f.SZ == S) {                                                                                      \
+    if constexpr (UNDO) {                                                                                                         \
+      const dim3 grid(rn_pipe_grid((const void*)rnorm_undo_fast_kernel<L, G, S>, tiles, smem, f.threads));                         \
+      hipLaunchKernelGGL((rnorm_undo_fast_kernel<L, G, S>), grid, block, smem, stream(), dout, in, out, locs, C, addScale, powScale, tiles); \
+      note_launch("rnorm_undo_fast_kernel<" #L ", " #G ", " #S ">", grid);                                                        \
+    } else {                                                                                                                      \
+      const dim3 grid(rn_pipe_grid((const void*)rnorm_fwd_fast_kernel<L, G, S>, tiles, smem, f.threads));                          \
+      hipLaunchKernelGGL((rnorm_fwd_fast_kernel<L, G, S>), grid, block, smem, stream(), in, out, locs, C, addScale, powScale, relu, tiles); \
+      note_launch("rnorm_fwd_fast_kernel<" #L ", " #G ", " #S ">", grid);                                                         \
+    }                                                                                                                             \
+    return true;                                                                                                                  \
+  }
+  RN_FAST_BUILDS(RN_FAST_TRY)
+#undef RN_FAST_TRY
+  return false;
 }
 
-bool rnorm_undo_fast(const float* dout, const float* in, float* out, size_t locs, int C, int sizeF, float addScale, float powScale, bool blocked, bool vec) {
-  RnFast f;
-  if (!rn_fast_shape(C, sizeF, blocked, vec, true, f)) return false;
-  const size_t smem = sizeof(float) * (size_t)f.LT * rn_fast_rows(f, C, true);
-  if (smem > 160 * 1024) return false;
-  const unsigned tiles = (unsigned)((locs + f.LT - 1) / f.LT);
-  const dim3 block(f.threads);
-#define RN_U(L, G, S)                                                                                                           \
-  do {                                                                                                                          \
-    const dim3 grid(rn_pipe_grid((const void*)rnorm_undo_fast_kernel<L, G, S>, tiles, smem, f.threads));                         \
-    hipLaunchKernelGGL((rnorm_undo_fast_kernel<L, G, S>), grid, block, smem, stream(), dout, in, out, locs, C, addScale, powScale, tiles); \
-  } while (0)
-  if (f.SZ == 24 && f.CG == 24 && f.LT == 128) RN_U(128, 24, 24);
-  else if (f.SZ == 24 && f.CG == 12 && f.LT == 64) RN_U(64, 12, 24);
-  else if (f.SZ == 24 && f.CG == 12 && f.LT == 32) RN_U(32, 12, 24);
-  else if (f.SZ == 24 && f.CG == 6 && f.LT == 64) RN_U(64, 6, 24);
-  else if (f.SZ == 24 && f.CG == 6 && f.LT == 32) RN_U(32, 6, 24);
-  else if (f.SZ == 24 && f.CG == 6 && f.LT == 16) RN_U(16, 6, 24);
-  else if (f.SZ == 64 && f.LT == 64) RN_U(64, 8, 64);
-  else if (f.SZ == 64 && f.LT == 32) RN_U(32, 8, 64);
-  else if (f.SZ == 64 && f.LT == 16) RN_U(16, 8, 64);
-  else return false;
-#undef RN_U
-  return true;
-}
+// The tile lengths the LDS-tiled kernels are built for.  Any other length (a diag knob's) runs the <8> build, as it always has.
+#define RN_LDS_BUILDS(X) X(64) X(32) X(16) X(8)
+#define RN_UNDO_LDS_NAME(L, threads, vec)                                              \
+  ((threads) == 512   ? ARM_NAME(vec, "rnorm_undo_lds_kernel<" #L ">/512")             \
+   : (threads) == 256 ? ARM_NAME(vec, "rnorm_undo_lds_kernel<" #L ">/256")             \
+                      : ARM_NAME(vec, "rnorm_undo_lds_kernel<" #L ">/diag"))
 
-void pool3d_fwd_launch(bool max, const float* in, float* out, const Pool3DGeo& g, float scaleTargets, float scaleOutput, bool vec) {
-  const size_t total = (size_t)g.Mt * g.C * g.My * g.Mx * g.nvec;
-  // algorithmic bytes: read the input once, write the output once
-  KernelTimer timer(max ? "pool3d_fwd_kernel<max>" : "pool3d_fwd_kernel<avg>", "pool_fwd", 0.0,
-                    4.0 * g.N * g.C * ((double)g.H * g.W * g.T + (double)g.My * g.Mx * g.Mt));
-  if (max)
-    hipLaunchKernelGGL(pool3d_fwd_kernel<true>, dim3(grid_for(total)), dim3(256), 0, stream(), in, out, g, scaleTargets, scaleOutput, vec);
-  else
-    hipLaunchKernelGGL(pool3d_fwd_kernel<false>, dim3(grid_for(total)), dim3(256), 0, stream(), in, out, g, scaleTargets, scaleOutput, vec);
-}
-
-void pool3d_undo_launch(bool max, const float* images, const float* grads, const float* acts, float* out, const Pool3DGeo& g,
-                        float scaleTargets, bool vec, bool relu_mask) {
-  const size_t total = (size_t)g.T * g.C * g.H * g.W * g.nvec;
-  const double in_el = (double)g.H * g.W * g.T, out_el = (double)g.My * g.Mx * g.Mt;
-  KernelTimer timer(max ? "pool3d_undo_kernel<max>" : "pool3d_undo_kernel<avg>", "pool_undo", 0.0,
-                    4.0 * g.N * g.C * ((max ? 2.0 : 1.0) * in_el + (max ? 2.0 : 1.0) * out_el + (scaleTargets != 0.f ? in_el : 0.0)));
-  if (max)
-    hipLaunchKernelGGL(pool3d_undo_kernel<true>, dim3(grid_for(total)), dim3(256), 0, stream(), images, grads, acts, out, g, scaleTargets,
-                       vec, relu_mask);
-  else
-    hipLaunchKernelGGL(pool3d_undo_kernel<false>, dim3(grid_for(total)), dim3(256), 0, stream(), images, grads, acts, out, g, scaleTargets,
-                       vec, false);
+// The call through the LDS-tiled kernel with tiles of LT locations (forward: C x LT floats of LDS; undo: three times that)
+template <bool UNDO>
+void rnorm_lds(const float* dout, const float* in, float* out, size_t locs, int C, int sizeF, float addScale, float powScale, bool blocked, bool vec,
+               bool relu, int LT) {
+  const size_t smem = sizeof(float) * (UNDO ? 3 : 1) * (size_t)C * LT;
+  const bool xcd = !CHIP_DIAG_KNOB("CONVNET_RNORM_NO_XCD", 0);   // A/B switch for the XCD-contiguous tile order
+  const unsigned tiles = (unsigned)((locs + LT - 1) / LT);
+  // undo: (rnorm2, C = 256: 75 -> 58 us with 8 instead of 16 channels per thread; C = 96: no difference)
+  const int threads = !UNDO ? 256 : CHIP_DIAG_KNOB("CONVNET_RNORM_UNDO_THREADS", 0) ? CHIP_DIAG_KNOB("CONVNET_RNORM_UNDO_THREADS", 0) : C > 128 ? 512 : 256;
+  const dim3 grid(xcd ? (tiles + 7) / 8 * 8 : tiles), block(threads);
+  if (UNDO) CHIP_REQUIRE(smem <= 160 * 1024);
+  const int build = LT == 64 || LT == 32 || LT == 16 ? LT : 8;
+#define RN_LDS_TRY(L)                                                                                                             \
+  if (build == L) {                                                                                                               \
+    if constexpr (UNDO) {                                                                                                         \
+      rn_raise_lds_limit((const void*)rnorm_undo_lds_kernel<L>, smem);   /* >64 KiB of dynamic LDS needs an explicit opt-in */      \
+      hipLaunchKernelGGL(rnorm_undo_lds_kernel<L>, grid, block, smem, stream(), dout, in, out, locs, C, sizeF, addScale, powScale, blocked, vec, tiles, xcd); \
+      note_launch(RN_UNDO_LDS_NAME(L, threads, vec), grid);                                                                       \
+    } else {                                                                                                                      \
+      hipLaunchKernelGGL(rnorm_fwd_lds_kernel<L>, grid, block, smem, stream(), in, out, locs, C, sizeF, addScale, powScale, blocked, vec, relu, tiles, xcd); \
+      note_launch(ARM_NAME(vec, "rnorm_fwd_lds_kernel<" #L ">"), grid);                                                           \
+    }                                                                                                                             \
+  }
+  RN_LDS_BUILDS(RN_LDS_TRY)
+#undef RN_LDS_TRY
 }
 
 PoolGeo pool_geo(const Shape4D* in, const Shape4D* out, const ConvDesc& d, const cudamat* mi, const cudamat* mo) {
@@ -1306,82 +1311,107 @@ inline int fixed_window(const PoolGeo& g, bool vec) {
 }
 
 // Switches a fixed-window launch to the XCD-aware 1-D order (CONVNET_POOL_NO_XCD=1 keeps the plain 3-D grid, for A/B runs).
-inline dim3 pool_xcd_grid(PoolGeo& g, int xblocks, int rows, dim3 plain) {
+inline dim3 pool_xcd_grid(PoolGeo& g, int xblocks, int rows) {
   const bool off = CHIP_DIAG_KNOB("CONVNET_POOL_NO_XCD", 0) != 0;
   const long long total = (long long)xblocks * rows * g.C;
-  g.xper = g.xtotal = g.xrows = g.xbx = 0;   // a second call on the same geometry (the 2 x 2-block undo) starts clean
-  if (off || total < 64 || total > (1ll << 30)) return plain;
+  g.xper = g.xtotal = g.xrows = g.xbx = 0;
+  if (off || total < 64 || total > (1ll << 30)) return dim3(xblocks, rows, g.C);
   g.xbx = xblocks; g.xrows = rows; g.xtotal = (int)total; g.xper = (int)((total + 7) / 8);
   return dim3(8 * g.xper);
 }
 
+// The 2-D pooling kernel that takes a call, with its grid (g gets the XCD order of that grid).  rows x cols: the extent the grid
+// walks (the pooled map forward, the input map for an undo).  allow_block, block_from: whether, and from which rows * cols on,
+// 3 x 3 stride-2 max pooling takes the 2 x 2-block kernel, whose grid is computed here and nowhere else (small maps keep the
+// per-element kernel's parallelism: 11 x 11 maps, undo, 17.7 vs 16.5 us; the mask pair has block kernels only: true, 0).
+enum PoolKernel { POOL_GENERIC, POOL_FIXED32, POOL_FIXED22, POOL_BLOCK };
+struct PoolLaunch {
+  PoolKernel kernel;
+  dim3 grid;
+};
+inline PoolLaunch pool_choose(PoolGeo& g, bool vec, bool max, int rows, int cols, bool allow_block, int block_from) {
+  const int fx = fixed_window(g, vec);
+  if (!fx) return {POOL_GENERIC, dim3(grid_for((size_t)g.C * rows * cols * g.nvec))};
+  if (fx == 32 && max && allow_block && rows * cols >= block_from) {
+    const int hb = (rows + 1) / 2;
+    return {POOL_BLOCK, pool_xcd_grid(g, divup(((cols + 1) / 2) * g.nvec, 256), hb)};
+  }
+  return {fx == 32 ? POOL_FIXED32 : POOL_FIXED22, pool_xcd_grid(g, divup(cols * g.nvec, 256), rows)};
+}
+
 template <bool MAX>
 void pool_fwd(cudamat* images, cudamat* targets, Shape4D* is, Shape4D* ts, const ConvDesc& d, float st, float so) {
+  const float* in = images->data_device;
+  float* out = targets->data_device;
   Pool3DGeo g3;
-  if (pool_time_geo(is, ts, d, images, targets, g3)) {
-    pool3d_fwd_launch(MAX, images->data_device, targets->data_device, g3, st, so, g3.N % 4 == 0 && a16(images->data_device) && a16(targets->data_device));
-    return;
+  if (pool_time_geo(is, ts, d, images, targets, g3)) {   // a window with a time extent
+    const bool vec = vec4(g3.N, {in, out});
+    const dim3 grid(grid_for((size_t)g3.Mt * g3.C * g3.My * g3.Mx * g3.nvec));
+    // algorithmic bytes: read the input once, write the output once
+    KernelTimer timer(MAX ? "pool3d_fwd_kernel<max>" : "pool3d_fwd_kernel<avg>", "pool_fwd", 0.0,
+                      4.0 * g3.N * g3.C * ((double)g3.H * g3.W * g3.T + (double)g3.My * g3.Mx * g3.Mt));
+    hipLaunchKernelGGL(pool3d_fwd_kernel<MAX>, grid, dim3(256), 0, stream(), in, out, g3, st, so, vec);
+    return note_launch(POOL_NAME(MAX, vec, "pool3d_fwd_kernel"), grid);
   }
   PoolGeo g = pool_geo(is, ts, d, images, targets);
-  const bool vec = g.N % 4 == 0 && a16(images->data_device) && a16(targets->data_device);
-  const size_t total = (size_t)g.C * g.My * g.Mx * g.nvec;
+  const bool vec = vec4(g.N, {in, out});
   // algorithmic bytes: read input once, write output once
   KernelTimer timer(MAX ? "pool_fwd_kernel<max>" : "pool_fwd_kernel<avg>", "pool_fwd", 0.0, 4.0 * g.N * g.C * ((double)g.H * g.W + (double)g.My * g.Mx));
-  const int fx = fixed_window(g, vec);
-  dim3 fgrid(divup(g.Mx * g.nvec, 256), g.My, g.C);
-  if (fx) fgrid = pool_xcd_grid(g, fgrid.x, g.My, fgrid);
-  if (fx == 32 && MAX && g.My * g.Mx >= 400 && CHIP_KNOB("CONVNET_POOL_FWD_BLOCK", 1)) {
-    // one thread per 2 x 2 output block: 25 loads for four outputs instead of 36 (small maps keep the per-output kernel's parallelism)
-    const int hb = (g.My + 1) / 2;
-    dim3 bgrid(divup(((g.Mx + 1) / 2) * g.nvec, 256), hb, g.C);
-    bgrid = pool_xcd_grid(g, bgrid.x, hb, bgrid);
-    hipLaunchKernelGGL(pool_fwd_max32_block_kernel, bgrid, dim3(256), 0, stream(), images->data_device, targets->data_device, g, st, so);
-  } else if (fx == 32)
-    hipLaunchKernelGGL((pool_fwd_fixed_kernel<MAX, 3, 2>), fgrid, dim3(256), 0, stream(), images->data_device, targets->data_device, g, st, so);
-  else if (fx == 22)
-    hipLaunchKernelGGL((pool_fwd_fixed_kernel<MAX, 2, 2>), fgrid, dim3(256), 0, stream(), images->data_device, targets->data_device, g, st, so);
-  else
-    hipLaunchKernelGGL(pool_fwd_kernel<MAX>, dim3(grid_for(total)), dim3(256), 0, stream(), images->data_device, targets->data_device, g,
-                       st, so, vec);
+  // block: one thread per 2 x 2 output block, 25 loads for four outputs instead of 36
+  const PoolLaunch l = pool_choose(g, vec, MAX, g.My, g.Mx, CHIP_KNOB("CONVNET_POOL_FWD_BLOCK", 1) != 0, 400);
+  switch (l.kernel) {
+    case POOL_BLOCK:
+      hipLaunchKernelGGL(pool_fwd_max32_block_kernel, l.grid, dim3(256), 0, stream(), in, out, g, st, so);
+      return note_launch("pool_fwd_max32_block_kernel", l.grid);
+    case POOL_FIXED32:
+      hipLaunchKernelGGL((pool_fwd_fixed_kernel<MAX, 3, 2>), l.grid, dim3(256), 0, stream(), in, out, g, st, so);
+      return note_launch(FIXED_NAME(MAX, "pool_fwd_fixed_kernel", "3, 2"), l.grid);
+    case POOL_FIXED22:
+      hipLaunchKernelGGL((pool_fwd_fixed_kernel<MAX, 2, 2>), l.grid, dim3(256), 0, stream(), in, out, g, st, so);
+      return note_launch(FIXED_NAME(MAX, "pool_fwd_fixed_kernel", "2, 2"), l.grid);
+    case POOL_GENERIC:
+      hipLaunchKernelGGL(pool_fwd_kernel<MAX>, l.grid, dim3(256), 0, stream(), in, out, g, st, so, vec);
+      return note_launch(POOL_NAME(MAX, vec, "pool_fwd_kernel"), l.grid);
+  }
 }
 
 template <bool MAX>
 void pool_undo(cudamat* images, cudamat* grads, cudamat* acts, cudamat* targets, Shape4D* in_shape, Shape4D* pooled_shape,
                const ConvDesc& d, float st, bool relu_mask = false) {
-  Pool3DGeo g3;
-  if (pool_time_geo(in_shape, pooled_shape, d, targets, grads, g3)) {
-    const bool v3 = g3.N % 4 == 0 && a16(grads->data_device) && a16(targets->data_device) &&
-                    (!MAX || (a16(images->data_device) && a16(acts->data_device)));
-    pool3d_undo_launch(MAX, MAX ? images->data_device : nullptr, grads->data_device, MAX ? acts->data_device : nullptr, targets->data_device, g3,
-                       st, v3, relu_mask);
-    return;
-  }
-  PoolGeo g = pool_geo(in_shape, pooled_shape, d, targets, grads);
-  const bool vec = g.N % 4 == 0 && a16(grads->data_device) && a16(targets->data_device) &&
-                   (!MAX || (a16(images->data_device) && a16(acts->data_device)));
-  const size_t total = (size_t)g.C * g.H * g.W * g.nvec;
-  KernelTimer timer(MAX ? "pool_undo_kernel<max>" : "pool_undo_kernel<avg>", "pool_undo", 0.0,
-                    4.0 * g.N * g.C * ((MAX ? 2.0 : 1.0) * g.H * g.W + (MAX ? 2.0 : 1.0) * g.My * g.Mx + (st != 0.f ? (double)g.H * g.W : 0.0)));
   const float* im = MAX ? images->data_device : nullptr;
   const float* ac = MAX ? acts->data_device : nullptr;
-  const int fx = fixed_window(g, vec);
-  dim3 fgrid(divup(g.W * g.nvec, 256), g.H, g.C);
-  if (fx) fgrid = pool_xcd_grid(g, fgrid.x, g.H, fgrid);
-  if (fx == 32 && MAX && g.H * g.W >= 400 && CHIP_KNOB("CONVNET_POOL_UNDO_BLOCK", 1)) {   // (11 x 11 maps: 17.7 vs 16.5 us)
-    // one thread per 2 x 2 input block: a third of the loads per output
-    const int hb = (g.H + 1) / 2;
-    dim3 bgrid(divup(((g.W + 1) / 2) * g.nvec, 256), hb, g.C);
-    bgrid = pool_xcd_grid(g, bgrid.x, hb, bgrid);
-    hipLaunchKernelGGL(pool_undo_max32_block_kernel, bgrid, dim3(256), 0, stream(), im, grads->data_device, ac, targets->data_device, g, st, relu_mask);
-  } else if (fx == 32)
-    hipLaunchKernelGGL((pool_undo_fixed_kernel<MAX, 3, 2>), fgrid, dim3(256), 0, stream(), im, grads->data_device, ac, targets->data_device, g,
-                       st, relu_mask);
-  else if (fx == 22)
-    hipLaunchKernelGGL((pool_undo_fixed_kernel<MAX, 2, 2>), fgrid, dim3(256), 0, stream(), im, grads->data_device, ac, targets->data_device, g,
-                       st, relu_mask);
-  else
-    hipLaunchKernelGGL(pool_undo_kernel<MAX>, dim3(grid_for(total)), dim3(256), 0, stream(), im, grads->data_device, ac,
-                       targets->data_device, g, st, vec, relu_mask);
+  const float* dy = grads->data_device;
+  float* out = targets->data_device;
+  Pool3DGeo g3;
+  if (pool_time_geo(in_shape, pooled_shape, d, targets, grads, g3)) {
+    const bool vec = vec4(g3.N, {dy, out, im, ac});
+    const dim3 grid(grid_for((size_t)g3.T * g3.C * g3.H * g3.W * g3.nvec));
+    const double in_el = (double)g3.H * g3.W * g3.T, out_el = (double)g3.My * g3.Mx * g3.Mt;
+    KernelTimer timer(MAX ? "pool3d_undo_kernel<max>" : "pool3d_undo_kernel<avg>", "pool_undo", 0.0,
+                      4.0 * g3.N * g3.C * ((MAX ? 2.0 : 1.0) * in_el + (MAX ? 2.0 : 1.0) * out_el + (st != 0.f ? in_el : 0.0)));
+    hipLaunchKernelGGL(pool3d_undo_kernel<MAX>, grid, dim3(256), 0, stream(), im, dy, ac, out, g3, st, vec, MAX && relu_mask);
+    return note_launch(POOL_NAME(MAX, vec, "pool3d_undo_kernel"), grid);
+  }
+  PoolGeo g = pool_geo(in_shape, pooled_shape, d, targets, grads);
+  const bool vec = vec4(g.N, {dy, out, im, ac});
+  KernelTimer timer(MAX ? "pool_undo_kernel<max>" : "pool_undo_kernel<avg>", "pool_undo", 0.0,
+                    4.0 * g.N * g.C * ((MAX ? 2.0 : 1.0) * g.H * g.W + (MAX ? 2.0 : 1.0) * g.My * g.Mx + (st != 0.f ? (double)g.H * g.W : 0.0)));
+  // block: one thread per 2 x 2 input block, a third of the loads per output
+  const PoolLaunch l = pool_choose(g, vec, MAX, g.H, g.W, CHIP_KNOB("CONVNET_POOL_UNDO_BLOCK", 1) != 0, 400);
+  switch (l.kernel) {
+    case POOL_BLOCK:
+      hipLaunchKernelGGL(pool_undo_max32_block_kernel, l.grid, dim3(256), 0, stream(), im, dy, ac, out, g, st, relu_mask);
+      return note_launch("pool_undo_max32_block_kernel", l.grid);
+    case POOL_FIXED32:
+      hipLaunchKernelGGL((pool_undo_fixed_kernel<MAX, 3, 2>), l.grid, dim3(256), 0, stream(), im, dy, ac, out, g, st, relu_mask);
+      return note_launch(FIXED_NAME(MAX, "pool_undo_fixed_kernel", "3, 2"), l.grid);
+    case POOL_FIXED22:
+      hipLaunchKernelGGL((pool_undo_fixed_kernel<MAX, 2, 2>), l.grid, dim3(256), 0, stream(), im, dy, ac, out, g, st, relu_mask);
+      return note_launch(FIXED_NAME(MAX, "pool_undo_fixed_kernel", "2, 2"), l.grid);
+    case POOL_GENERIC:
+      hipLaunchKernelGGL(pool_undo_kernel<MAX>, l.grid, dim3(256), 0, stream(), im, dy, ac, out, g, st, vec, relu_mask);
+      return note_launch(POOL_NAME(MAX, vec, "pool_undo_kernel"), l.grid);
+  }
 }
 
 }  // namespace
@@ -1397,8 +1427,8 @@ void MaxPoolGemm(cudamat* images, cudamat* targets, Shape4D* is, Shape4D* ts, Co
 void AvgPoolGemm(cudamat* images, cudamat* targets, Shape4D* is, Shape4D* ts, ConvDesc d, float scaleTargets, float scaleOutput) {
   pool_fwd<false>(images, targets, is, ts, d, scaleTargets, scaleOutput);
 }
-void MaxPool(cudamat* images, cudamat* targets, Shape4D* is, Shape4D* ts, ConvDesc d) { pool_fwd<true>(images, targets, is, ts, d, 0.f, 1.f); }
-void AvgPool(cudamat* images, cudamat* targets, Shape4D* is, Shape4D* ts, ConvDesc d) { pool_fwd<false>(images, targets, is, ts, d, 0.f, 1.f); }
+void MaxPool(cudamat* images, cudamat* targets, Shape4D* is, Shape4D* ts, ConvDesc d) { MaxPoolGemm(images, targets, is, ts, d, 0.f, 1.f); }
+void AvgPool(cudamat* images, cudamat* targets, Shape4D* is, Shape4D* ts, ConvDesc d) { AvgPoolGemm(images, targets, is, ts, d, 0.f, 1.f); }
 
 // deferred epilogues (common.h: PendingOp): the parked form of MaxPoolUndo — the ReLU' of the layer below can join it
 static void launch_pool_undo(PendingOp& o) {
@@ -1425,28 +1455,27 @@ void MaxPoolUndoRelu(cudamat* images, cudamat* maxGrads, cudamat* maxActs, cudam
 }
 void MaxPoolUndo(cudamat* images, cudamat* maxGrads, cudamat* maxActs, cudamat* targets, Shape4D* images_shape, Shape4D* maxGrads_shape,
                  ConvDesc d, float scaleTargets) {
-  if (park_pool_undo(images, maxGrads, maxActs, targets, images_shape, maxGrads_shape, d, scaleTargets)) return;
-  pool_undo<true>(images, maxGrads, maxActs, targets, images_shape, maxGrads_shape, d, scaleTargets);
+  MaxPoolUndoGemm(images, maxGrads, maxActs, targets, images_shape, maxGrads_shape, d, scaleTargets);
 }
 // ---- max pooling with a window mask (the kernels' header has the format) ------------------------------------------------------------------
-static bool mask_geo_ok(const PoolGeo& g, const cudamat* images, const cudamat* pooled_a, const cudamat* pooled_b, const cudamat* mask) {
-  const bool vec = g.N % 4 == 0 && a16(images->data_device) && a16(pooled_a->data_device) && (!pooled_b || a16(pooled_b->data_device)) &&
-                   a16(mask->data_device);
-  // (negated paddings: py, px <= 0 is what the 2 x 2-block undo assumes)
-  return fixed_window(g, vec) == 32 && g.py <= 0 && g.px <= 0 && numel(mask) * 2 >= (size_t)g.N * g.C * g.My * g.Mx;
+// The mask pair's geometry and its block grid, or false: 3 x 3 stride 2 on float4 rows, non-positive (negated) paddings, which is what the
+// 2 x 2-block undo assumes, and a mask matrix that holds 2 bytes per pooled element
+static bool mask_launch(PoolGeo& g, int rows, int cols, std::initializer_list<const void*> operands, const cudamat* mask, dim3& grid) {
+  if (fixed_window(g, vec4(g.N, operands)) != 32 || g.py > 0 || g.px > 0 || numel(mask) * 2 < (size_t)g.N * g.C * g.My * g.Mx) return false;
+  grid = pool_choose(g, true, true, rows, cols, true, 0).grid;
+  return true;
 }
 int MaxPoolMask(cudamat* images, cudamat* targets, cudamat* mask, Shape4D* images_shape, Shape4D* targets_shape, ConvDesc conv_desc) {
   if (!images->on_device || !targets->on_device || !mask->on_device) return ERROR_NOT_ON_DEVICE;
   Pool3DGeo g3;
   if (pool_time_geo(images_shape, targets_shape, conv_desc, images, targets, g3)) return ERROR_UNSUPPORTED;   // the mask pair is 2-D only
   PoolGeo g = pool_geo(images_shape, targets_shape, conv_desc, images, targets);
-  if (!mask_geo_ok(g, images, targets, nullptr, mask)) return ERROR_UNSUPPORTED;
+  dim3 grid;
+  if (!mask_launch(g, g.My, g.Mx, {images->data_device, targets->data_device, mask->data_device}, mask, grid)) return ERROR_UNSUPPORTED;
   KernelTimer timer("pool_fwd_mask_kernel<max>", "pool_fwd", 0.0, (double)g.N * g.C * (4.0 * g.H * g.W + 6.0 * g.My * g.Mx));
-  const int hb = (g.My + 1) / 2;
-  dim3 bgrid(divup(((g.Mx + 1) / 2) * g.nvec, 256), hb, g.C);
-  bgrid = pool_xcd_grid(g, bgrid.x, hb, bgrid);
-  hipLaunchKernelGGL(pool_fwd_max32_mask_kernel, bgrid, dim3(256), 0, stream(), images->data_device, targets->data_device,
+  hipLaunchKernelGGL(pool_fwd_max32_mask_kernel, grid, dim3(256), 0, stream(), images->data_device, targets->data_device,
                      reinterpret_cast<u32x2*>(mask->data_device), g);
+  note_launch("pool_fwd_max32_mask_kernel", grid);
   return launch_status();
 }
 int MaxPoolUndoMask(cudamat* maxGrads, cudamat* mask, cudamat* targets, Shape4D* targets_shape, Shape4D* maxGrads_shape, ConvDesc conv_desc,
@@ -1458,54 +1487,41 @@ int MaxPoolUndoMask(cudamat* maxGrads, cudamat* mask, cudamat* targets, Shape4D*
   Pool3DGeo g3;
   if (pool_time_geo(targets_shape, maxGrads_shape, conv_desc, targets, maxGrads, g3)) return ERROR_UNSUPPORTED;
   PoolGeo g = pool_geo(targets_shape, maxGrads_shape, conv_desc, targets, maxGrads);
-  if (!mask_geo_ok(g, targets, maxGrads, nullptr, mask)) return ERROR_UNSUPPORTED;
+  dim3 grid;
+  if (!mask_launch(g, g.H, g.W, {targets->data_device, maxGrads->data_device, mask->data_device}, mask, grid)) return ERROR_UNSUPPORTED;
   KernelTimer timer("pool_undo_mask_kernel<max>", "pool_undo", 0.0,
                     (double)g.N * g.C * ((scaleTargets != 0.f ? 8.0 : 4.0) * g.H * g.W + 6.0 * g.My * g.Mx));
-  const int hb = (g.H + 1) / 2;
-  dim3 bgrid(divup(((g.W + 1) / 2) * g.nvec, 256), hb, g.C);
-  bgrid = pool_xcd_grid(g, bgrid.x, hb, bgrid);
-  hipLaunchKernelGGL(pool_undo_max32_mask_kernel, bgrid, dim3(256), 0, stream(), maxGrads->data_device,
+  hipLaunchKernelGGL(pool_undo_max32_mask_kernel, grid, dim3(256), 0, stream(), maxGrads->data_device,
                      reinterpret_cast<const u32x2*>(mask->data_device), targets->data_device, g, scaleTargets, relu != 0);
+  note_launch("pool_undo_max32_mask_kernel", grid);
   return launch_status();
 }
 void AvgPoolUndoGemm(cudamat* avgGrads, cudamat* targets, Shape4D* avgGrads_shape, Shape4D* targets_shape, ConvDesc d, float scaleTargets) {
   pool_undo<false>(nullptr, avgGrads, nullptr, targets, targets_shape, avgGrads_shape, d, scaleTargets);
 }
 void AvgPoolUndo(cudamat* avgGrads, cudamat* targets, Shape4D* avgGrads_shape, Shape4D* targets_shape, ConvDesc d, float scaleTargets) {
-  pool_undo<false>(nullptr, avgGrads, nullptr, targets, targets_shape, avgGrads_shape, d, scaleTargets);
+  AvgPoolUndoGemm(avgGrads, targets, avgGrads_shape, targets_shape, d, scaleTargets);
 }
 
 static void rnorm_fwd_impl(cudamat* images, cudamat* targets, int numFilters, int sizeF, float addScale, float powScale, bool blocked, bool relu) {
   const size_t total = numel(images);
   CHIP_REQUIRE(numel(targets) == total && numFilters > 0 && total % numFilters == 0 && sizeF > 0);
   const size_t locs = total / numFilters;
-  const bool vec = locs % 4 == 0 && a16(images->data_device) && a16(targets->data_device);
+  const int C = numFilters;
+  const float* in = images->data_device;
+  float* out = targets->data_device;
+  const bool vec = vec4(locs, {in, out});
   KernelTimer timer("rnorm_fwd_kernel", "rnorm_fwd", 0.0, 8.0 * total);
-  {
-    const int C = numFilters;
-    int LT = C <= 192 ? 64 : (C <= 384 ? 32 : (C <= 768 ? 16 : 0));
-    if (const int f = CHIP_DIAG_KNOB("CONVNET_RNORM_FWD_LT", 0)) LT = f;   // tuning knob (tools/pool_bench.py, -DCONVNET_DIAG builds)
-    if (rnorm_fwd_fast(images->data_device, targets->data_device, locs, C, sizeF, addScale, powScale, blocked, vec, relu)) return;
-    if (LT) {   // LDS-tiled, read-once/write-once
-      const size_t smem = sizeof(float) * (size_t)C * LT;
-      const bool xcd = !CHIP_DIAG_KNOB("CONVNET_RNORM_NO_XCD", 0);   // A/B switch for the XCD-contiguous tile order
-      const unsigned tiles = (unsigned)((locs + LT - 1) / LT);
-      const dim3 grid(xcd ? (tiles + 7) / 8 * 8 : tiles), block(256);
-#define RN_FWD(L) hipLaunchKernelGGL(rnorm_fwd_lds_kernel<L>, grid, block, smem, stream(), images->data_device, targets->data_device, locs, C, sizeF, addScale, powScale, blocked, vec, relu, tiles, xcd)
-      if (LT == 64) RN_FWD(64);
-      else if (LT == 32) RN_FWD(32);
-      else if (LT == 16) RN_FWD(16);
-      else RN_FWD(8);
-#undef RN_FWD
-      return;
-    }
-  }
+  int LT = C <= 192 ? 64 : (C <= 384 ? 32 : (C <= 768 ? 16 : 0));
+  if (const int f = CHIP_DIAG_KNOB("CONVNET_RNORM_FWD_LT", 0)) LT = f;   // tuning knob (tools/pool_bench.py, -DCONVNET_DIAG builds)
+  if (rnorm_fast<false>(nullptr, in, out, locs, C, sizeF, addScale, powScale, blocked, vec, relu)) return;
+  if (LT) return rnorm_lds<false>(nullptr, in, out, locs, C, sizeF, addScale, powScale, blocked, vec, relu, LT);   // read-once / write-once
   // the walker below subtracts channels it has already written and reads other segments' channels while they are written
-  CHIP_REQUIRE(images->data_device != targets->data_device);   // in place: numFilters <= 768 only (include/convnet_hip.h)
+  CHIP_REQUIRE(in != out);   // in place: numFilters <= 768 only (include/convnet_hip.h)
   int cseg, nseg;
-  rnorm_segments((locs + 3) / 4, numFilters, sizeF, cseg, nseg);
-  hipLaunchKernelGGL(rnorm_fwd_kernel, dim3(grid_for((locs + 3) / 4 * nseg)), dim3(256), 0, stream(), images->data_device, targets->data_device, locs,
-                     numFilters, sizeF, addScale, powScale, blocked, vec, cseg, nseg, relu);
+  const dim3 grid = rnorm_walk_grid(locs, C, sizeF, cseg, nseg);
+  hipLaunchKernelGGL(rnorm_fwd_kernel, grid, dim3(256), 0, stream(), in, out, locs, C, sizeF, addScale, powScale, blocked, vec, cseg, nseg, relu);
+  note_launch(ARM_NAME(vec, "rnorm_fwd_kernel"), grid);
 }
 static void launch_rnorm_fwd(PendingOp& o) { rnorm_fwd_impl(&o.m[0], &o.m[1], o.i0, o.i1, o.f0, o.f1, o.b0, o.relu != 0); }
 void ResponseNormCrossMapGemm(cudamat* images, cudamat* targets, int numFilters, int sizeF, float addScale, float powScale, bool blocked) {
@@ -1529,48 +1545,29 @@ void ResponseNormCrossMapUndoGemm(cudamat* outGrads, cudamat* inputs, cudamat* t
   const size_t total = numel(inputs);
   CHIP_REQUIRE(numel(targets) == total && numel(outGrads) == total && numFilters > 0 && total % numFilters == 0 && sizeF > 0);
   const size_t locs = total / numFilters;
-  {
-    const int C = numFilters;
-    // measured (N=256): C=96 LT 8/16/32 -> 484/291/324 us, C=256 LT 8/16/32 -> 104/83/166 us: more, smaller blocks per CU
-    // (the three phases of a block do not overlap) beat longer contiguous rows
-    int LT = C <= 64 ? 64 : (C <= 256 ? 16 : (C <= 512 ? 8 : 0));
-    if (const int f = CHIP_DIAG_KNOB("CONVNET_RNORM_UNDO_LT", 0)) LT = f;   // tuning knob (tools/pool_bench.py, -DCONVNET_DIAG builds)
-    if (LT) {
-      const bool vec = locs % 4 == 0 && a16(outGrads->data_device) && a16(inputs->data_device) && a16(targets->data_device);
-      KernelTimer timer("rnorm_undo_kernels", "rnorm_undo", 0.0, 12.0 * total);
-      if (rnorm_undo_fast(outGrads->data_device, inputs->data_device, targets->data_device, locs, C, sizeF, addScale, powScale, blocked, vec)) return;
-      const size_t smem = sizeof(float) * 3 * (size_t)C * LT;
-      const bool xcd = !CHIP_DIAG_KNOB("CONVNET_RNORM_NO_XCD", 0);   // A/B switch for the XCD-contiguous tile order
-      const unsigned tiles = (unsigned)((locs + LT - 1) / LT);
-      const dim3 grid(xcd ? (tiles + 7) / 8 * 8 : tiles), block(CHIP_DIAG_KNOB("CONVNET_RNORM_UNDO_THREADS", 0) ? CHIP_DIAG_KNOB("CONVNET_RNORM_UNDO_THREADS", 0) : C > 128 ? 512 : 256);   // (rnorm2, C = 256: 75 -> 58 us with 8 instead of 16 channels per thread; C = 96: no difference)
-      CHIP_REQUIRE(smem <= 160 * 1024);
-#define RN_UNDO(L)                                                                                                              \
-  do {                                                                                                                          \
-    if (smem > 64 * 1024)   /* >64 KiB of dynamic LDS needs an explicit opt-in */                                                \
-      CHIP_CHECK(hipFuncSetAttribute((const void*)rnorm_undo_lds_kernel<L>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
-    hipLaunchKernelGGL(rnorm_undo_lds_kernel<L>, grid, block, smem, stream(), outGrads->data_device, inputs->data_device,       \
-                       targets->data_device, locs, C, sizeF, addScale, powScale, blocked, vec, tiles, xcd);                      \
-  } while (0)
-      if (LT == 64) RN_UNDO(64);
-      else if (LT == 32) RN_UNDO(32);
-      else if (LT == 16) RN_UNDO(16);
-      else RN_UNDO(8);
-#undef RN_UNDO
-      return;
-    }
-  }
+  const int C = numFilters;
+  const float* dout = outGrads->data_device;
+  const float* in = inputs->data_device;
+  float* out = targets->data_device;
+  // measured (N=256): C=96 LT 8/16/32 -> 484/291/324 us, C=256 LT 8/16/32 -> 104/83/166 us: more, smaller blocks per CU
+  // (the three phases of a block do not overlap) beat longer contiguous rows
+  int LT = C <= 64 ? 64 : (C <= 256 ? 16 : (C <= 512 ? 8 : 0));
+  if (const int f = CHIP_DIAG_KNOB("CONVNET_RNORM_UNDO_LT", 0)) LT = f;   // tuning knob (tools/pool_bench.py, -DCONVNET_DIAG builds)
+  const bool vec = vec4(locs, {dout, in, out});
+  // the two temporaries of the walker pair (the arena may grow and synchronise: asked for before the timer starts)
   const size_t padded = (total + 63) / 64 * 64;
-  float* prod = static_cast<float*>(workspace(sizeof(float) * padded * 2));
-  float* scaled = prod + padded;
-  const bool vec = locs % 4 == 0 && a16(outGrads->data_device) && a16(inputs->data_device) && a16(targets->data_device);
-  int cseg, nseg;
-  rnorm_segments((locs + 3) / 4, numFilters, sizeF, cseg, nseg);
-  const int grid = grid_for((locs + 3) / 4 * nseg);
+  float* prod = LT ? nullptr : static_cast<float*>(workspace(sizeof(float) * padded * 2));
   KernelTimer timer("rnorm_undo_kernels", "rnorm_undo", 0.0, 12.0 * total);
-  hipLaunchKernelGGL(rnorm_undo1_kernel, dim3(grid), dim3(256), 0, stream(), outGrads->data_device, inputs->data_device, prod, scaled, locs,
-                     numFilters, sizeF, addScale, powScale, blocked, vec, cseg, nseg);
-  hipLaunchKernelGGL(rnorm_undo2_kernel, dim3(grid), dim3(256), 0, stream(), inputs->data_device, prod, scaled, targets->data_device, locs,
-                     numFilters, sizeF, addScale, powScale, blocked, vec, cseg, nseg);
+  if (LT) {
+    if (rnorm_fast<true>(dout, in, out, locs, C, sizeF, addScale, powScale, blocked, vec, false)) return;
+    return rnorm_lds<true>(dout, in, out, locs, C, sizeF, addScale, powScale, blocked, vec, false, LT);
+  }
+  float* scaled = prod + padded;
+  int cseg, nseg;
+  const dim3 grid = rnorm_walk_grid(locs, C, sizeF, cseg, nseg);
+  hipLaunchKernelGGL(rnorm_undo1_kernel, grid, dim3(256), 0, stream(), dout, in, prod, scaled, locs, C, sizeF, addScale, powScale, blocked, vec, cseg, nseg);
+  hipLaunchKernelGGL(rnorm_undo2_kernel, grid, dim3(256), 0, stream(), in, prod, scaled, out, locs, C, sizeF, addScale, powScale, blocked, vec, cseg, nseg);
+  note_launch(ARM_NAME(vec, "rnorm_undo1_kernel+rnorm_undo2_kernel"), grid);   // one report for the pair
 }
 void ResponseNormCrossMapUndo(cudamat* outGrads, cudamat* inputs, cudamat* /*acts*/, cudamat* targets, int numFilters, int sizeF,
                               float addScale, float powScale, bool blocked) {

@@ -596,12 +596,14 @@ void convOutpBias(cudamat* images, cudamat* derivs, cudamat* targets, cudamat* b
                   Shape4D* images_shape, Shape4D* derivs_shape, Shape4D* targets_shape,
                   ConvDesc conv_desc, float scaleTargets, float scaleOutput);
 
-/* ---- introspection for the roofline report: flops of the last MFMA launch family ----------------- */
+/* ---- introspection: what the last conv / dot / pooling / response-norm call launched ---------------
+ * A pooling or response-norm call overwrites the report of the conv / dot call before it: read it right after the call it is about. */
 typedef struct ConvnetHipKernelInfo {
-  const char* name;      /* kernel family of the last conv/dot call */
-  double flops;          /* algorithmic flops of that call (2*M*N*K) */
-  int grid_blocks;
-  int split_k;
+  const char* name;      /* conv / dot: kernel family.  Pooling / response norm: the kernel build and the arm the grid cannot show
+                            ("pool_undo_kernel<max>/scalar", "rnorm_undo_lds_kernel<16>/512/vec"; a string literal of the library) */
+  double flops;          /* algorithmic flops of that call (2*M*N*K); 0 for pooling / response norm */
+  int grid_blocks;       /* blocks launched (pooling / response norm: idle XCD-order blocks included) */
+  int split_k;           /* 1 for pooling / response norm */
 } ConvnetHipKernelInfo;
 void convnet_hip_last_kernel_info(ConvnetHipKernelInfo* out);
 /* Per-launch HIP-event timing on the library stream (used by bench.py's roofline leg).  While enabled

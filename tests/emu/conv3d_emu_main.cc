@@ -24,6 +24,7 @@ void* workspace(size_t bytes) {
   return (void*)(((uintptr_t)g_ws0.data() + 63) & ~(uintptr_t)63);
 }
 void set_last_error(const char*) {}
+void note_kernel(const char*, double, int, int) {}
 bool defer_begin(int, void (*)(PendingOp&)) { return false; }
 PendingOp& pending() {
   static PendingOp p = {};

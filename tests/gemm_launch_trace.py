@@ -259,9 +259,8 @@ def _recorded(fn):
     for line in buf.value.decode().splitlines() if n else []:
         k, op, cnt, _ms, fl, by, ex = line.split("|")
         lines.append("|".join((k, op, cnt, fl, by, ex)))
-    info = _lib.KernelInfo()
-    _lib.lib.convnet_hip_last_kernel_info(ctypes.byref(info))
-    rec = {"profile": lines, "kernel": [info.name.decode(), info.grid_blocks, info.split_k], "out": _sha(out)}
+    from hip_adapter import last_kernel
+    rec = {"profile": lines, "kernel": list(last_kernel()[:3]), "out": _sha(out)}
     if db is not None:
         rec["bias"] = _sha(db)
     return rec

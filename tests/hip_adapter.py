@@ -23,6 +23,15 @@ def _mat(arr, rows, cols, shape4=None, guard=(0, 0)):
     return (m, full) if before or after else m
 
 
+def last_kernel():
+    """(name, grid_blocks, split_k, flops): what the library's last conv / dot / pooling / response-norm call says it launched"""
+    import ctypes
+    from convnet_amd import _lib
+    info = _lib.KernelInfo()
+    _lib.lib.convnet_hip_last_kernel_info(ctypes.byref(info))
+    return info.name.decode(), info.grid_blocks, info.split_k, info.flops
+
+
 def _desc(g, pool=False):
     d = make_conv_desc(g.C, g.C if pool else g.F, g.Ky, g.Kx, g.sy, g.sx, g.pady, g.padx)
     if hasattr(g, "Kt"):

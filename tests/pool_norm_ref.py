@@ -3,7 +3,8 @@
 
 The operations themselves are tests/conv3d_ref.py's, called with one frame: they clip boxes, route every tie, divide by the clipped box
 and take any rectangular geometry.  Added here, from the header's definitions: the forward scales, MaxPoolUndoRelu, the per-element
-error scales and bounds of the averages and of the response norm, and `expected_path`.  2-D arrays are (C, H, W, N)."""
+error scales and bounds of the averages and of the response norm, and `expected_path` / `launched`.  2-D arrays are (C, H, W, N)."""
+import collections
 import functools
 
 import numpy as np
@@ -194,11 +195,22 @@ RNORM_CASES = {
 
 
 # ---- the dispatch, restated ---------------------------------------------------------------------------------------------------------------
+# name: what the library reports for the call (convnet_hip_last_kernel_info);  grid_blocks: the blocks it launched, idle XCD-order blocks
+# included, or None where the grid comes from the runtime's occupancy figure (the persistent fast kernels): then grid_cap bounds it;
+# label: name + the launch form, the vocabulary of the test ids and of REQUIRED_PATHS
+Path = collections.namedtuple("Path", "name grid_blocks grid_cap label")
+
+
 def _divup(a, b):
     return -(-a // b)
 
 
+def _grid_for(items):
+    return max(1, min(4096, _divup(items, 256)))
+
+
 def _rn_fast(C, size_f, blocked, vec, undo):
+    """(LT, CG) of the fast kernel build that takes the call, or None"""
     if blocked or not vec or C < size_f or size_f not in (24, 64):
         return None
     CG = 8 if size_f == 64 else (12 if C <= 96 else 6)
@@ -214,7 +226,7 @@ def _rn_fast(C, size_f, blocked, vec, undo):
     rows, seg = H + C + CG + H + 1, G * (CG // SS) + 2 * (H // SS)
     if 4 * LT * (2 * rows + 2 * seg if undo else rows + C + CG + seg) > 160 * 1024:
         return None
-    return f"<{LT}, {CG}, {size_f}>"
+    return LT, CG
 
 
 def _rn_segments(locs, C, size_f):
@@ -225,51 +237,76 @@ def _rn_segments(locs, C, size_f):
 
 
 def expected_path(op, g=None, aligned=True, C=0, size_f=0, blocked=False, locs=0):
-    """The kernel (and launch form) a call takes.  This RESTATES the dispatch of convnet_amd/csrc/pool_norm.hip at this commit
-    (pool_fwd / pool_undo / fixed_window / pool_xcd_grid, rnorm_fwd_impl / ResponseNormCrossMapUndoGemm / rn_fast_shape /
-    rnorm_segments) by hand and proves nothing about it: it names test ids and lets one assertion check that the case lists reach
-    every name in REQUIRED_PATHS.  op: max_fwd, avg_fwd, max_undo, avg_undo (g, aligned) or rnorm_fwd, rnorm_undo (C, size_f, blocked,
-    locs, aligned)."""
+    """The kernel a call takes and its grid, as a Path.  This RESTATES the dispatch of convnet_amd/csrc/pool_norm.hip by hand; the GPU
+    tests hold it against what the library reports after each call (launched), so a moved threshold fails them, and one assertion
+    checks that the case lists reach every label in REQUIRED_PATHS.  op: max_fwd, avg_fwd, max_undo, avg_undo (g, aligned), mask_fwd,
+    mask_undo (g: the mask pair, tests/test_pool_mask_gpu.py) or
+    rnorm_fwd, rnorm_undo (C, size_f, blocked, locs, aligned)."""
     if op.startswith("rnorm"):
         vec = locs % 4 == 0 and aligned
-        arm = "vec" if vec else "scalar"
-        if op == "rnorm_fwd":
-            fast = _rn_fast(C, size_f, blocked, vec, False)
-            LT = 64 if C <= 192 else 32 if C <= 384 else 16 if C <= 768 else 0
-            if fast:
-                return f"rnorm_fwd_fast_kernel{fast}"
-            if LT:
-                return f"rnorm_fwd_lds_kernel<{LT}>/{arm}"
-            cseg, nseg = _rn_segments(locs, C, size_f)
-            return f"rnorm_fwd_kernel/{arm}/{'segments' if nseg > 1 else 'one segment'}"
-        LT = 64 if C <= 64 else 16 if C <= 256 else 8 if C <= 512 else 0
+        arm, undo = "vec" if vec else "scalar", op == "rnorm_undo"
+        LT = (64 if C <= 64 else 16 if C <= 256 else 8 if C <= 512 else 0) if undo else (64 if C <= 192 else 32 if C <= 384 else 16 if C <= 768 else 0)
+        fast = _rn_fast(C, size_f, blocked, vec, undo) if LT or not undo else None
+        way = "undo" if undo else "fwd"
+        if fast:
+            name = f"rnorm_{way}_fast_kernel<{fast[0]}, {fast[1]}, {size_f}>"
+            return Path(name, None, 8 * _divup(_divup(locs, fast[0]), 8), name)
         if LT:
-            fast = _rn_fast(C, size_f, blocked, vec, True)
-            return f"rnorm_undo_fast_kernel{fast}" if fast else f"rnorm_undo_lds_kernel<{LT}>/{512 if C > 128 else 256}/{arm}"
-        return f"rnorm_undo1_kernel+rnorm_undo2_kernel/{arm}"
+            name = f"rnorm_undo_lds_kernel<{LT}>/{512 if C > 128 else 256}/{arm}" if undo else f"rnorm_fwd_lds_kernel<{LT}>/{arm}"
+            return Path(name, 8 * _divup(_divup(locs, LT), 8), None, name)
+        cseg, nseg = _rn_segments(locs, C, size_f)
+        grid = _grid_for((locs + 3) // 4 * nseg)
+        if undo:
+            name = f"rnorm_undo1_kernel+rnorm_undo2_kernel/{arm}"
+            return Path(name, grid, None, name)
+        name = f"rnorm_fwd_kernel/{arm}"
+        return Path(name, grid, None, f"{name}/{'segments' if nseg > 1 else 'one segment'}")
     kind, way = op.split("_")
+    if kind == "mask":      # MaxPoolMask / MaxPoolUndoMask: block kernels only, at every map size (refused unless 3 x 3 stride 2 on float4 rows)
+        rows, cols = (g.My, g.Mx) if way == "fwd" else (g.H, g.W)
+        total = _divup(((cols + 1) // 2) * _divup(g.N, 4), 256) * ((rows + 1) // 2) * g.C
+        xcd = 64 <= total <= 1 << 30
+        return Path(f"pool_{way}_max32_mask_kernel", 8 * _divup(total, 8) if xcd else total, None, f"pool_{way}_max32_mask_kernel/{'xcd' if xcd else 'grid3d'}")
     vec = g.N % 4 == 0 and aligned
     fixed = vec and g.Ky == g.Kx and g.sy == g.sx and (g.Ky, g.sy) in ((3, 2), (2, 2))
-    if not fixed:
-        return f"pool_{way}_kernel<{kind}>/{'vec' if vec else 'scalar'}"
     nvec = _divup(g.N, 4)
     rows, cols = (g.My, g.Mx) if way == "fwd" else (g.H, g.W)
+    if not fixed:
+        name = f"pool_{way}_kernel<{kind}>/{'vec' if vec else 'scalar'}"
+        return Path(name, _grid_for(g.C * rows * cols * nvec), None, name)
     if g.Ky == 3 and kind == "max" and rows * cols >= 400:
         name, xb, rows = f"pool_{way}_max32_block_kernel", _divup(((cols + 1) // 2) * nvec, 256), (rows + 1) // 2
     else:
         name, xb = f"pool_{way}_fixed_kernel<{kind}, {g.Ky}, {g.sy}>", _divup(cols * nvec, 256)
     total = xb * rows * g.C
-    return f"{name}/{'xcd' if 64 <= total <= 1 << 30 else 'grid3d'}" + (f"/{xb} x-blocks" if xb > 1 else "")
+    xcd = 64 <= total <= 1 << 30
+    return Path(name, 8 * _divup(total, 8) if xcd else total, None, f"{name}/{'xcd' if xcd else 'grid3d'}" + (f"/{xb} x-blocks" if xb > 1 else ""))
+
+
+def launched(path, name, grid_blocks, split_k=1, flops=0.0):
+    """asserts that what the library reported for its last call (convnet_hip_last_kernel_info) is `path`"""
+    assert (name, split_k, flops) == (path.name, 1, 0.0), ((name, split_k, flops), path)
+    if path.grid_blocks is not None:
+        assert grid_blocks == path.grid_blocks, (name, grid_blocks, path)
+    else:
+        assert grid_blocks > 0 and grid_blocks % 8 == 0 and grid_blocks <= path.grid_cap, (name, grid_blocks, path)
+
+
+def pool_path(name, mis, op):
+    return expected_path(op, POOL_GEOMS[name], not mis)
+
+
+def rnorm_path(name, op):
+    size_f, blocked, shape, mis = RNORM_CASES[name]
+    return expected_path(op, C=shape[0], size_f=size_f, blocked=blocked, locs=int(np.prod(shape[1:])), aligned=not mis)
 
 
 def pool_paths(name, mis):
-    return {op: expected_path(op, POOL_GEOMS[name], not mis) for op in ("max_fwd", "avg_fwd", "max_undo", "avg_undo")}
+    return {op: pool_path(name, mis, op).label for op in ("max_fwd", "avg_fwd", "max_undo", "avg_undo")}
 
 
 def rnorm_paths(name):
-    size_f, blocked, shape, mis = RNORM_CASES[name]
-    k = dict(C=shape[0], size_f=size_f, blocked=blocked, locs=int(np.prod(shape[1:])), aligned=not mis)
-    return {op: expected_path(op, **k) for op in ("rnorm_fwd", "rnorm_undo")}
+    return {op: rnorm_path(name, op).label for op in ("rnorm_fwd", "rnorm_undo")}
 
 
 REQUIRED_PATHS = (

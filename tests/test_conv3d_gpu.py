@@ -282,7 +282,7 @@ POOLS = [
 @pytest.mark.parametrize("g", POOLS, ids=str)
 def test_pooling_over_time(gpu, g):
     from convnet_amd.matrix import Matrix
-    from hip_adapter import _desc, _mat, _x, _y
+    from hip_adapter import _desc, _mat, _x, _y, last_kernel
     rng = np.random.default_rng(g.N)
     d = _desc(g, pool=True)
     # small integers: many ties, and every sum of routed derivatives is exact in fp32 -> max pooling compares exactly
@@ -292,6 +292,7 @@ def test_pooling_over_time(gpu, g):
     X, DY, (Y, FY) = _x(g, x), _y(g, dy, pool=True), _y(g, np.zeros(g.pooled_shape()), guard=GUARDED, pool=True)
     before = _bytes(X, DY)
     Matrix.ConvMaxPool(X, Y, d)
+    assert last_kernel()[0].startswith("pool3d_fwd_kernel<max>/")
     y = Y.ToNumpy().reshape(g.pooled_shape())
     assert np.array_equal(y, R.max_pool(g, x)) and _guards_intact(FY, g.N)
     for st in (0.0, 1.0):

@@ -5,7 +5,6 @@ refill and both barriers), two column groups with a ragged last one, fewer than 
 columns from the zero page), rectangular images, the fused bias + ReLU epilogue.  Every case asserts
 that gfc_kernel is what ran.  The full conv1 geometry at 256 images runs in tests/test_full_geometry_gpu.py on the default path.
 Tolerance: the reference's own kernel-test metric, max|a-b| / mean|a+b| < 1e-4 (py/test_conv.py:382-392)."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -33,10 +32,8 @@ def hip():
 
 
 def last_kernel():
-    from convnet_amd import _lib
-    info = _lib.KernelInfo()
-    _lib.lib.convnet_hip_last_kernel_info(ctypes.byref(info))
-    return info.name.decode()
+    import hip_adapter
+    return hip_adapter.last_kernel()[0]
 
 
 def rnd(rng, shape):

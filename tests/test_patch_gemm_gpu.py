@@ -4,7 +4,6 @@ conv_down, cudamat_conv_gemm.cu:545-825) on geometries chosen for ITS mechanisms
 from one 64-image block to the next, the ragged last tile, tap groups of a stride-2 row, partial row tiles, border tap rows.
 Every case asserts that the patch kernel is what ran (convnet_hip_last_kernel_info), so a silent fallback cannot pass.
 Tolerance: the reference's own kernel-test metric, max|a-b| / mean|a+b| < 1e-4 (py/test_conv.py:382-392)."""
-import ctypes
 import os
 
 import numpy as np
@@ -45,10 +44,8 @@ def patch_mode(request, hip):
 
 
 def last_kernel():
-    from convnet_amd import _lib
-    info = _lib.KernelInfo()
-    _lib.lib.convnet_hip_last_kernel_info(ctypes.byref(info))
-    return info.name.decode()
+    import hip_adapter
+    return hip_adapter.last_kernel()[0]
 
 
 def rnd(rng, shape):

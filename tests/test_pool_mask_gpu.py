@@ -10,6 +10,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import oracle  # noqa: E402
+import pool_norm_ref as P  # noqa: E402
 from oracle import Geom  # noqa: E402
 from golden_cases import rel_err  # noqa: E402
 
@@ -27,7 +28,7 @@ def hip():
 def _run(g, x, dy, t0, st, relu):
     """(y, dx) by the mask pair and by the classic pair on the same device tensors"""
     from convnet_amd.matrix import Matrix
-    from hip_adapter import _desc, _x, _y
+    from hip_adapter import _desc, _x, _y, last_kernel
     d = _desc(g, True)
     xm = _x(g, x)
     dym = _y(g, dy, pool=True)
@@ -39,7 +40,9 @@ def _run(g, x, dy, t0, st, relu):
             mk = Matrix()
             mk.AllocateGPUMemory(g.N, (g.Mx * g.My * g.C + 1) // 2)
             assert Matrix.ConvMaxPoolMask(xm, ym, mk, d), "this geometry must have a mask kernel"
+            P.launched(P.expected_path("mask_fwd", g), *last_kernel())
             Matrix.ConvMaxPoolUndoMask(dym, mk, tm, d, st, relu)
+            P.launched(P.expected_path("mask_undo", g), *last_kernel())
         else:
             Matrix.ConvMaxPool(xm, ym, d)
             (Matrix.ConvMaxPoolUndoRelu if relu else Matrix.ConvMaxPoolUndo)(xm, dym, ym, tm, d, st)

@@ -4,7 +4,8 @@ tests/pool_norm_ref.py (held against the oracle's compiled C by tests/test_pool_
 
 Every tensor sits between guard floats of 7.0 in one allocation: "aligned" four floats in, "misaligned" one float in
 (data_device % 16 == 4); guards and input operands are checked after every call.  Test ids carry the kernel that
-pool_norm_ref.expected_path expects (a restatement of the dispatch, not a measurement of it).
+pool_norm_ref.expected_path expects, a restatement of the dispatch; after every call the library's own report of the kernel and grid it
+launched (convnet_hip_last_kernel_info) is held against that restatement (_ran).
 
 Pooling.  Max pooling and its undo run on integer data (negative maxima, ties, an all -5 tensor whose padded taps must not count as 0)
 with the scales 0, 1, -2, 0.5: every result is exact in any float32 order (CPU file), so the comparison is np.array_equal.  The averages
@@ -93,16 +94,25 @@ def _pool_id(case):
     return f"{name}-{'misaligned' if mis else 'aligned'}-{p['max_fwd']}|{p['max_undo']}".replace(" ", "")
 
 
+def _ran(path):
+    """the library reports the kernel and the grid that pool_norm_ref.expected_path names for the call just made"""
+    from hip_adapter import last_kernel
+    P.launched(path, *last_kernel())
+
+
 def _fwd(lib, kind, g, X, T, st, so):
     (lib.MaxPoolGemm if kind == "max" else lib.AvgPoolGemm)(X.mat, T.mat, X.s4, T.s4, _desc(g), st, so)
+    _ran(P.expected_path(f"{kind}_fwd", g, X.g == 4))
 
 
 def _max_undo(lib, g, X, DY, Y, T, st, relu):
     (lib.MaxPoolUndoRelu if relu else lib.MaxPoolUndoGemm)(X.mat, DY.mat, Y.mat, T.mat, X.s4, DY.s4, _desc(g), st)
+    _ran(P.expected_path("max_undo", g, X.g == 4))
 
 
 def _avg_undo(lib, g, DY, T, st):
     lib.AvgPoolUndoGemm(DY.mat, T.mat, DY.s4, T.s4, _desc(g), st)
+    _ran(P.expected_path("avg_undo", g, DY.g == 4))
 
 
 # ======== pooling ===========================================================================================================================
@@ -242,10 +252,12 @@ def _rn_id(name):
 
 def _rn(lib, X, T, C, size_f, a, b, blocked, relu=False):
     (lib.ResponseNormCrossMapRelu if relu else lib.ResponseNormCrossMapGemm)(X.mat, T.mat, C, size_f, a, b, blocked)
+    _ran(P.expected_path("rnorm_fwd", C=C, size_f=size_f, blocked=blocked, locs=int(np.prod(X.shape[1:])), aligned=X.g == 4))
 
 
 def _rn_undo(lib, DY, X, T, C, size_f, a, b, blocked):
     lib.ResponseNormCrossMapUndoGemm(DY.mat, X.mat, T.mat, C, size_f, a, b, blocked)
+    _ran(P.expected_path("rnorm_undo", C=C, size_f=size_f, blocked=blocked, locs=int(np.prod(X.shape[1:])), aligned=X.g == 4))
 
 
 @pytest.mark.parametrize("ab", P.PARAMS, ids=lambda ab: f"a{ab[0]}b{ab[1]}")
