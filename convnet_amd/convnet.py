@@ -111,6 +111,7 @@ class ConvNet(TrainLoopMixin):
         self.second_history_ = Matrix()   # Adagrad / RMSProp second moments, flat like history_; allocated only if an edge optimizer keeps one
         self.edge_slices_ = {}   # edge -> (offset, length) in the flat buffers
         self.train_dataset_ = None
+        self.train_dataset_config_ = self.valid_dataset_config_ = None   # the DatasetConfigs of SetupDataset(train_pbtxt, val_pbtxt)
         self.correct_accum_ = None
         self._logits_pending = set()   # output layers whose state still holds logits (fused softmax / logistic / softmax-distribution)
         self._bn_steps = []            # fused host: the gamma / beta SGD steps planned during Bprop, run with the edges' batch
@@ -563,9 +564,45 @@ class ConvNet(TrainLoopMixin):
             RunFusedSteps(batch)
 
     # ---- data -------------------------------------------------------------------------------------------
-    def SetupDataset(self, dataset):
-        self.train_dataset_ = dataset
-        self.batch_size_ = dataset.GetBatchSize()
+    def SetupDataset(self, dataset, val_data_config_file=""):
+        """A handler object (anything with the DataHandler protocol), or — ConvNet::SetupDataset (src/convnet.cc:495-536) — the path of
+        the training set's DatasetConfig pbtxt and, optionally, the validation set's."""
+        if not isinstance(dataset, str):
+            self.train_dataset_ = dataset
+            self.batch_size_ = dataset.GetBatchSize()
+            return
+        # The reference keeps the two configs in model_.train_dataset / valid_dataset; pbtxt.Model has no such fields (the model
+        # files' schema stays as it is), so they live on the net.
+        if dataset:
+            self.train_dataset_config_ = pbtxt.read(dataset, pbtxt.DatasetConfig)
+        if val_data_config_file:
+            self.valid_dataset_config_ = pbtxt.read(val_data_config_file, pbtxt.DatasetConfig)
+        if self.train_dataset_config_ is None:
+            raise SystemExit("Error: No training set provided.")
+        if self.valid_dataset_config_ is None:
+            self.log("Warning: No validation set provided.")
+        self.train_dataset_ = self._build_data_handler(self.train_dataset_config_)
+        self.SetBatchsize(self.train_dataset_.GetBatchSize())
+        self.log("Training data set size", self.train_dataset_.GetDataSetSize())
+        if self.valid_dataset_config_ is not None:
+            self.val_dataset_ = self._build_data_handler(self.valid_dataset_config_)
+            self.log("Validation data set size", self.val_dataset_.GetDataSetSize())
+
+    def _build_data_handler(self, config):
+        from .datahandler import DataHandler
+        dh = DataHandler(config, seed=self.model_.seed + self.process_id_)
+        by_name = {l.GetName(): l for l in self.data_layers_}
+        for name, st in dh.streams_.items():
+            l = by_name.get(name)
+            if l is None:
+                raise SystemExit(f"Data stream for layer {name}: the model has no input or output layer of that name.")
+            if l.IsInput():
+                want = l.GetSizeY() * l.GetSizeX() * l.GetSizeT() * l.GetNumChannels()
+                if st.StagedDims() != want:
+                    raise SystemExit(f"Data stream for layer {name}: the stream stages {st.StagedDims()} values per case "
+                                     f"(rows of {st.GetDims()}, cropped to gpu_image_size), the layer holds {want}.")
+        dh.SetInputLayers([l.GetName() for l in self.data_layers_ if l.IsInput()])
+        return dh
 
     def GetBatch(self, dataset):
         dataset.GetBatch(self.data_layers_)

@@ -50,6 +50,70 @@ __global__ void __launch_bounds__(256) extract_patches_kernel(const float* __res
   }
 }
 
+// The same crop + flip + transpose from a chunk kept in its stored type (one unsigned byte per pixel), with the cast and the mean / std
+// normalisation of the SOURCE pixel on the way.  tile = 64 images x 64 patch columns of one (colour, patch row): twice the float
+// kernel's in both directions, because a byte run of 32 columns is only 32 B.  Read side: the 64 lanes of a wave walk the source
+// columns of one image (64 contiguous bytes, reversed when flipped, at any alignment; mean / std beside them as 256 contiguous bytes),
+// 16 images per wave with all their loads in flight.  Write side: the 64 lanes walk the images of one patch column (256 contiguous,
+// aligned bytes of the CHWN batch per wave store — the side that carries 4 of the 5 bytes per pixel).  What an image contributes to
+// every address of its row — chunk column, source row, first source column and walking direction — is worked out once per block by
+// the first wave and kept in LDS, so the pixel loop issues one global load per pixel (three with mean / std) instead of five (seven).
+// The case index, the source row and the source column are clamped into range: no value in case_index / offsets / flip reads outside
+// the chunk.
+template <bool NORM, bool JITTER>
+__global__ void __launch_bounds__(256) stage_patches_u8_kernel(const unsigned char* __restrict__ chunk, const float* __restrict__ case_index,
+                                                               const float* __restrict__ mean, const float* __restrict__ sdev,
+                                                               float* __restrict__ patches, const float* __restrict__ wo,
+                                                               const float* __restrict__ ho, const float* __restrict__ flip, int N,
+                                                               int num_cases, int W, int H, int pw, int ph, int colors) {
+  __shared__ float tile[64][65];
+  __shared__ size_t case_base[64];   // where the image's case starts in the chunk
+  __shared__ int row_base[64];       // where its source row starts inside a case (< dims)
+  __shared__ int col_first[64];      // source column of patch column 0 ...
+  __shared__ int col_step[64];       // ... and the direction the patch columns walk in (-1: flipped)
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;   // 64 x 4
+  const int c0 = blockIdx.x * 64;
+  const int row = blockIdx.y % ph, color = blockIdx.y / ph;
+  const int n0 = blockIdx.z * 64;
+  if (ty == 0 && n0 + tx < N) {
+    const int n = n0 + tx;
+    int sr = row, first = 0, step = 1;
+    if (JITTER) {
+      // (an offset beyond the image lands on the nearest border whatever its size: cut it short, so that nothing below overflows)
+      sr += min(max((int)ho[n], -H - ph), H + ph);
+      first = min(max((int)wo[n], -W - pw), W + pw);
+      if (flip[n] > 0.5f) {
+        first = W - first - 1;
+        step = -1;
+      }
+    }
+    sr = min(max(sr, 0), H - 1);
+    const int col = min(max((int)case_index[n], 0), num_cases - 1);
+    case_base[tx] = (size_t)colors * W * H * (size_t)col;
+    row_base[tx] = W * (sr + H * color);
+    col_first[tx] = first;
+    col_step[tx] = step;
+  }
+  __syncthreads();
+#pragma unroll 4
+  for (int j = ty; j < 64; j += 4) {
+    const int n = n0 + j, dc = c0 + tx;
+    if (n < N && dc < pw) {
+      const int sc = min(max(col_first[j] + col_step[j] * dc, 0), W - 1);
+      const int src = row_base[j] + sc;
+      float v = (float)chunk[case_base[j] + (size_t)src];
+      if (NORM) v = (v - mean[src]) / sdev[src];
+      tile[j][tx] = v;
+    }
+  }
+  __syncthreads();
+#pragma unroll 4
+  for (int j = ty; j < 64; j += 4) {
+    const int dc = c0 + j, n = n0 + tx;
+    if (n < N && dc < pw) patches[(size_t)n + (size_t)N * (dc + (size_t)pw * (row + (size_t)ph * color))] = tile[tx][j];
+  }
+}
+
 // one block per column pair (2j, 2j+1): swap columns idx[2j] and idx[2j+1] of the matrix in place
 __global__ void shuffle_columns_kernel(float* __restrict__ m, const float* __restrict__ idx, int height, int width) {
   const int c = 2 * blockIdx.x;
@@ -146,6 +210,44 @@ int extract_patches(cudamat* images, cudamat* patches, cudamat* width_offset, cu
   hipLaunchKernelGGL(extract_patches_kernel, grid, dim3(256), 0, stream(), images->data_device, patches->data_device,
                      width_offset->data_device, height_offset->data_device, flip->data_device, num_images, img_width, img_height,
                      patch_width, patch_height, num_colors);
+  return hipGetLastError() == hipSuccess ? 0 : CUDA_ERROR;
+}
+
+int stage_patches_u8(void* chunk, int dims, int num_cases, cudamat* case_index, cudamat* mean, cudamat* sdev, cudamat* patches,
+                     cudamat* width_offset, cudamat* height_offset, cudamat* flip, int img_width, int img_height, int patch_width,
+                     int patch_height) {
+  if (!chunk || !case_index || !patches) return ERROR_NOT_ON_DEVICE;
+  const bool norm = mean || sdev, jitter = width_offset || height_offset || flip;
+  if (norm && !(mean && sdev)) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (jitter && !(width_offset && height_offset && flip)) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (!case_index->on_device || !patches->on_device || (norm && (!mean->on_device || !sdev->on_device)) ||
+      (jitter && (!width_offset->on_device || !height_offset->on_device || !flip->on_device)))
+    return ERROR_NOT_ON_DEVICE;
+  if (patches->is_trans) return ERROR_TRANSPOSED;
+  if (dims <= 0 || num_cases <= 0 || img_width <= 0 || img_height <= 0 || patch_width <= 0 || patch_height <= 0)
+    return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (patch_width > img_width || patch_height > img_height) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (!jitter && (patch_width != img_width || patch_height != img_height)) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (dims % ((long)img_width * img_height) != 0) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  const int num_colors = dims / (img_width * img_height);
+  const int num_images = patches->size[0];
+  if ((long)patches->size[1] != (long)num_colors * patch_width * patch_height) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (numel(case_index) != (size_t)num_images) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (norm && (mean->size[0] != dims || mean->size[1] != 1 || sdev->size[0] != dims || sdev->size[1] != 1)) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (jitter && (numel(width_offset) != (size_t)num_images || numel(height_offset) != (size_t)num_images || numel(flip) != (size_t)num_images))
+    return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (num_cases > (1 << 24)) return ERROR_UNSUPPORTED;   // a column number must be exact as a float
+  if (num_images == 0) return 0;
+  if ((long)patch_height * num_colors > 65535 || divup(num_images, 64) > 65535) return ERROR_UNSUPPORTED;
+  KernelTimer timer("stage_patches_u8_kernel", "input_staging", 0.0, 5.0 * numel(patches));
+  const dim3 grid(divup(patch_width, 64), patch_height * num_colors, divup(num_images, 64));
+  auto kernel = norm ? (jitter ? stage_patches_u8_kernel<true, true> : stage_patches_u8_kernel<true, false>)
+                     : (jitter ? stage_patches_u8_kernel<false, true> : stage_patches_u8_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream(), static_cast<const unsigned char*>(chunk), case_index->data_device,
+                     norm ? mean->data_device : nullptr, norm ? sdev->data_device : nullptr, patches->data_device,
+                     jitter ? width_offset->data_device : nullptr, jitter ? height_offset->data_device : nullptr,
+                     jitter ? flip->data_device : nullptr, num_images, num_cases, img_width, img_height, patch_width, patch_height,
+                     num_colors);
   return hipGetLastError() == hipSuccess ? 0 : CUDA_ERROR;
 }
 

@@ -1,7 +1,8 @@
-"""Synthetic DataHandler.  The reference's input pipeline (src/datahandler.cc: HDF5/JPEG/video
-iterators, OpenCV) is out of hot-path scope; only its contract matters: ``GetBatch(data_layers)``
-leaves a batch in every input layer's ``state_`` (N, X*Y*C CHWN) and every output layer's ``data_``
-(src/datahandler.cc:145-198).  Inputs are N(0,1) (the real pipeline feeds mean/std-normalised
+"""Data handlers.  The contract is the reference's (src/datahandler.cc:145-198): ``GetBatch(data_layers)``
+leaves a batch in every input layer's ``state_`` (N, X*Y*C CHWN) and every output layer's ``data_``.
+``DataHandler`` (below) is the reference's own, for HDF5 streams: built from a DatasetConfig, it reads
+chunks from disk and stages batches on the GPU; JPEG / video / text streams are refused.
+``ChunkDataHandler`` stages from numpy arrays the caller holds; ``SyntheticDataHandler`` makes noise: inputs are N(0,1) (the real pipeline feeds mean/std-normalised
 pixels, :496-507), labels uniform ints stored as float (N,1); ``num_batches`` distinct batches are
 pre-generated on the device and cycled, so no host work sits inside a timed step."""
 import numpy as np
@@ -166,3 +167,456 @@ class ChunkDataHandler:
                 self.labels_.GetSlice(self.label_slice_, self.start_, end)
                 self.label_slice_.CopyTranspose(l.GetData())
         self.start_ = end % self.chunk_size_ if not self.randomize_ else end
+
+
+_REFUSED_TYPES = {
+    "DUMMY": "random numbers in place of data", "IMAGE_RAW": "JPEG files decoded and resized on the host",
+    "SLIDING_WINDOW": "sliding windows over raw images", "TXT": "text files of numbers", "BOUNDING_BOX": "bounding-box files",
+    "CROPS": "crops of raw images", "VIDEO_RAW": "video files decoded on the host"}
+
+
+class _Stream:
+    """DataIterator + HDF5DataIterator<T> for one ``data_config`` (src/datahandler.cc:415-570, 604-721)."""
+
+    def __init__(self, dsc):
+        from . import hdf5io
+        name = dsc.layer_name
+        if dsc.is_sequence:
+            raise SystemExit(f"Data stream for layer {name}: is_sequence (sequence data) is not supported.")
+        if dsc.data_type != "HDF5":
+            what = _REFUSED_TYPES.get(dsc.data_type)
+            if what is None:
+                raise SystemExit(f"Data stream for layer {name}: Unknown data type {dsc.data_type}")
+            raise SystemExit(f"Data stream for layer {name}: data_type {dsc.data_type} ({what}) is not supported; only HDF5 streams are.")
+        if dsc.noise_layer_name:
+            raise SystemExit(f"Data stream for layer {name}: noise_layer_name ({dsc.noise_layer_name}) is not supported: "
+                             "no stream takes its jitter from another.")
+        if dsc.gpu_id != 0:
+            raise SystemExit(f"Data stream for layer {name}: gpu_id {dsc.gpu_id} is not supported: one process drives one GPU, gpu_id 0.")
+        self.config_, self.layer_name_ = dsc, name
+        self.file_ = hdf5io.File(dsc.file_pattern)
+        self.reader_ = self.file_.RowReader(dsc.dataset_name)
+        self.image_size_y_ = dsc.image_size_y if dsc.has_image_size_y() else dsc.image_size
+        self.image_size_x_ = dsc.image_size_x if dsc.has_image_size_x() else dsc.image_size
+        self.gpu_image_size_y_ = dsc.gpu_image_size_y if dsc.has_gpu_image_size_y() else self.image_size_y_
+        self.gpu_image_size_x_ = dsc.gpu_image_size_x if dsc.has_gpu_image_size_x() else self.image_size_x_
+        self.num_colors_, self.translate_, self.flip_ = dsc.num_colors, dsc.can_translate, dsc.can_flip
+        self.normalize_ = dsc.normalize or dsc.pixelwise_normalize
+        self.pixelwise_normalize_, self.normalize_local_ = dsc.pixelwise_normalize, dsc.normalize_local
+        self.pca_noise_stddev_ = dsc.pca_noise_stddev
+        self.add_pca_noise_ = dsc.pca_noise_stddev > 0
+        self.raw_ = False            # the chunk form: bytes (True) or float (DataHandler.SetInputLayers decides)
+        self.mean_ = self.std_ = None
+        self.width_offset_, self.height_offset_, self.flip_bit_ = Matrix(), Matrix(), Matrix()
+        self.pca_noise1_, self.pca_noise2_ = Matrix(), Matrix()
+        self.slice_, self.index_slice_ = Matrix(), Matrix()
+
+    def GetDims(self):
+        return self.reader_.GetDims()
+
+    def Jitters(self):
+        return self.image_size_y_ != self.gpu_image_size_y_ or self.image_size_x_ != self.gpu_image_size_x_ or self.flip_
+
+    def StagedDims(self):
+        """The width of the batch this stream leaves in its layer."""
+        return self.num_colors_ * self.gpu_image_size_y_ * self.gpu_image_size_x_ if self.Jitters() else self.GetDims()
+
+    def CheckGeometry(self):
+        if self.Jitters() and self.GetDims() != self.num_colors_ * self.image_size_y_ * self.image_size_x_:
+            raise SystemExit(f"Data stream for layer {self.layer_name_}: rows of {self.GetDims()} values are not {self.num_colors_} colours of "
+                             f"{self.image_size_y_} x {self.image_size_x_} pixels.")
+        if self.gpu_image_size_y_ > self.image_size_y_ or self.gpu_image_size_x_ > self.image_size_x_:
+            raise SystemExit(f"Data stream for layer {self.layer_name_}: gpu_image_size exceeds image_size.")
+
+    # ---- DataIterator::LoadMeans (:445-474) ----
+    def LoadMeans(self):
+        from . import hdf5io
+        dims = self.GetDims()
+        with hdf5io.File(self.config_.mean_file) as f:
+            if self.pixelwise_normalize_:
+                # mean_ = zeros(num_pixels, num_channels) + the row vector pixel_mean, reshaped to a column: every channel's value repeated
+                # over its pixels (0 + x is exact, so the host does it)
+                pm, ps = (f.ReadHDF5CPU(int(np.prod(f.ReadHDF5Shape(n))), n) for n in ("pixel_mean", "pixel_std"))
+                if pm.size == 0 or dims % pm.size or ps.size != pm.size:
+                    raise SystemExit(f"Data stream for layer {self.layer_name_}: pixel_mean of {pm.size} channels does not divide {dims} dims.")
+                mean, std = np.repeat(pm, dims // pm.size), np.repeat(ps, dims // pm.size)
+                if self.add_pca_noise_:
+                    self.eig_values_, self.eig_vectors_ = Matrix(), Matrix()
+                    self.eig_values_.AllocateAndReadHDF5(f, "S")
+                    self.eig_vectors_.AllocateAndReadHDF5(f, "U")
+            else:
+                mean, std = f.ReadHDF5CPU(dims, "mean"), f.ReadHDF5CPU(dims, "std")
+        self.mean_, self.std_ = Matrix(), Matrix()
+        for m, v in ((self.mean_, mean), (self.std_, std)):
+            m.AllocateGPUMemory(dims, 1, "normalizer")
+            m.FromNumpy(v)
+
+    # ---- DataIterator::Preprocess (:496-507): the float chunk, once per load ----
+    def Preprocess(self, m):
+        if self.normalize_local_:
+            dims = m.GetRows()
+            m.Reshape(dims // self.num_colors_, -1)
+            m.NormalizeColumnwise()
+            m.Reshape(dims, -1)
+        if self.normalize_:
+            m.AddColVec(self.mean_, -1)
+            m.DivideByColVec(self.std_)
+
+    # ---- DataIterator::SampleNoise (:534-570) ----
+    def SampleNoise(self, batch_size, multiplicity_id):
+        if not self.Jitters():
+            return
+        max_offset_y = self.image_size_y_ - self.gpu_image_size_y_
+        max_offset_x = self.image_size_x_ - self.gpu_image_size_x_
+        if self.width_offset_.GetCols() != batch_size:
+            for m in (self.width_offset_, self.height_offset_, self.flip_bit_):
+                m.AllocateGPUMemory(1, batch_size)
+        if self.translate_:
+            self.height_offset_.FillWithRand()
+            self.width_offset_.FillWithRand()
+            self.height_offset_.Mult(max_offset_y + 1)
+            self.width_offset_.Mult(max_offset_x + 1)
+        else:
+            w, h = [(max_offset_x // 2, max_offset_y // 2), (0, 0), (max_offset_x, 0), (max_offset_x, max_offset_y),
+                    (0, max_offset_y)][multiplicity_id % 5]
+            self.height_offset_.Set(h)
+            self.width_offset_.Set(w)
+        if self.flip_:
+            self.flip_bit_.FillWithRand()
+        else:
+            self.flip_bit_.Set(multiplicity_id // 5)
+
+    # ---- DataIterator::AddPCANoise (:509-518) ----
+    def AddPCANoise(self, m):
+        if self.pca_noise1_.GetRows() != m.GetRows():
+            self.pca_noise1_.AllocateGPUMemory(m.GetRows(), self.eig_vectors_.GetRows())
+            self.pca_noise2_.AllocateGPUMemory(m.GetRows(), self.eig_vectors_.GetCols())
+        self.pca_noise1_.FillWithRandn()
+        self.pca_noise1_.MultByRowVec(self.eig_values_)
+        Matrix.Dot(self.pca_noise1_, self.eig_vectors_, self.pca_noise2_, 0, 1)
+        m.AddToEachPixel(self.pca_noise2_, self.pca_noise_stddev_)
+
+    # ---- DataIterator::AddNoise (:520-532), from either chunk form ----
+    def AddNoise(self, handler, start, end, output):
+        jit = self.Jitters()
+        if self.raw_:
+            handler.col_index_dev_.GetSlice(self.index_slice_, start, end)
+            dims = self.GetDims()
+            offs = (self.width_offset_, self.height_offset_, self.flip_bit_) if jit else (None, None, None)
+            # no jitter: a transpose of whole rows, whatever image_size says (the reference's CopyTranspose)
+            geom = ((self.image_size_y_, self.image_size_x_, self.gpu_image_size_y_, self.gpu_image_size_x_) if jit else (1, dims, 1, dims))
+            Matrix.StagePatchesU8(handler.raw_data_[self.layer_name_], dims, handler.chunk_size_, self.index_slice_,
+                                  self.mean_ if self.normalize_ else None, self.std_ if self.normalize_ else None, output, *offs, *geom)
+        else:
+            handler.data_[self.layer_name_].GetSlice(self.slice_, start, end)
+            if jit:
+                Matrix.ExtractPatches(self.slice_, output, self.width_offset_, self.height_offset_, self.flip_bit_, self.image_size_y_,
+                                      self.image_size_x_, self.gpu_image_size_y_, self.gpu_image_size_x_)
+            else:
+                self.slice_.CopyTranspose(output)
+        if self.add_pca_noise_:
+            self.AddPCANoise(output)
+
+    def close(self):
+        self.reader_.close()
+        self.file_.close()
+
+
+class _DiskSide:
+    """DataHandler::DiskAccess / LoadChunk (src/datahandler.cc:239-314): everything the preload thread touches — the row readers, the
+    host buffers and the random-row list.  libhdf5 and numpy only: no GPU call, no ``Matrix``, and no way back to the handler, so a
+    handler that is dropped while a preload runs is collected (and joins the thread) at once."""
+
+    def __init__(self, readers, chunk_size, dataset_size, randomize_cpu, random_access_chunk_size, rng):
+        self.readers_ = readers              # layer name -> RowReader, in data_config order
+        self.chunk_size_, self.dataset_size_ = chunk_size, dataset_size
+        self.randomize_cpu_, self.random_access_chunk_size_ = randomize_cpu, random_access_chunk_size
+        self.rng_ = rng
+        self.random_indices_ind_ = 0
+        if randomize_cpu:
+            self.random_indices_ = rng.permutation(dataset_size)
+        self.host_ = None                    # [buffer][layer name] -> (chunk_size, dims) array
+        self.error_ = None
+
+    def Preload(self, buf):
+        try:
+            self.DiskAccess(buf)
+        except BaseException as e:           # handed to the thread that joins
+            self.error_ = e
+
+    def DiskAccess(self, buf):
+        random_rows = None
+        if self.randomize_cpu_:
+            num_rand = (self.chunk_size_ + self.random_access_chunk_size_ - 1) // self.random_access_chunk_size_
+            if self.random_indices_ind_ + num_rand > self.dataset_size_:     # (:241-246)
+                self.rng_.shuffle(self.random_indices_)
+                self.random_indices_ind_ = 0
+            random_rows = self.random_indices_[self.random_indices_ind_:self.random_indices_ind_ + num_rand].tolist()
+            self.random_indices_ind_ += num_rand
+        for name, reader in self.readers_.items():
+            out = self.host_[buf][name]
+            if random_rows is None:
+                self._load_run(reader, out, 0, reader.Tell(), self.chunk_size_, seek=True)
+            else:
+                for i, row in enumerate(random_rows):
+                    at = i * self.random_access_chunk_size_
+                    # (the last run stops at the end of the chunk: the reference reads a whole run there, past its buffer)
+                    self._load_run(reader, out, at, row, min(self.random_access_chunk_size_, self.chunk_size_ - at))
+        return self.host_[buf]
+
+    def _load_run(self, reader, out, at, row, count, seek=False):
+        """``count`` consecutive rows from ``row``, wrapping at the end of the dataset (GetNext's wrap, :717-721; LoadChunk's, :305-311)."""
+        size = self.dataset_size_
+        while count > 0:
+            n = min(count, size - row)
+            reader.Get(out[at:at + n], row, row + n)
+            at, count, row = at + n, count - n, (row + n) % size
+        if seek:
+            reader.Seek(row)
+
+
+class DataHandler:
+    """DataHandler for HDF5 streams, built from a ``pbtxt.DatasetConfig`` (src/datahandler.cc:8-336): chunks of the dataset are read
+    from disk (sequentially, or ``randomize_cpu`` in runs of ``random_access_chunk_size`` rows), copied to the GPU, and every
+    ``GetBatch`` stages one batch from the resident chunk into the data layers.
+
+    Two chunk forms per stream.  **float** is the reference's: rows are cast to float on the host, the chunk is a (dims, cases)
+    ``Matrix``, ``Preprocess`` normalises all of it at load, ``randomize_gpu`` swaps its columns, and a batch is ``ExtractPatches`` /
+    ``CopyTranspose`` of a slice.  **bytes** — taken when the dataset is stored as unsigned 8-bit, its layer is an input layer and
+    ``normalize_local`` is off — keeps the chunk on the GPU exactly as read (a ``torch.uint8`` tensor, a quarter of the transfer and of
+    the memory); nothing touches it after the copy, ``randomize_gpu`` swaps entries of a column index instead, and a batch is ONE
+    ``StagePatchesU8``: cast, mean / std, crop, flip and transpose together, bit for bit what the float form leaves.
+    ``raw_chunks=False`` forces the float form everywhere.
+
+    The two host RNGs (random rows, column permutation) are numpy generators seeded from ``seed``; the device RNG calls are the
+    library's, in the reference's order.  ``pipeline_loads``: one preload thread reads the next chunk into the idle one of two pinned
+    host buffers; it calls libhdf5 and nothing else."""
+
+    def __init__(self, config, raw_chunks=True, seed=0):
+        self.config_ = config
+        self.raw_chunks_ = bool(raw_chunks)
+        self.preload_thread_ = None
+        self.batch_size_, self.chunk_size_ = config.batch_size, config.chunk_size
+        self.max_reuse_count_, self.reuse_counter_ = config.max_reuse_count, 0
+        self.random_access_chunk_size_ = max(config.random_access_chunk_size, 1)
+        self.dataset_size_ = -1
+        self.start_ = self.multiplicity_counter_ = 0
+        self.restart_, self.nothing_on_gpu_, self.fits_on_gpu_ = True, True, False
+        self.pipeline_loads_, self.randomize_cpu_, self.randomize_gpu_ = config.pipeline_loads, config.randomize_cpu, config.randomize_gpu
+        self.multiplicity_ = config.multiplicity
+        self.row_rng_, self.perm_rng_ = (np.random.default_rng(s) for s in np.random.SeedSequence(seed).spawn(2))
+        self.layer_names_, self.streams_ = [], {}
+        for dsc in config.data_config:
+            st = _Stream(dsc)
+            self.layer_names_.append(dsc.layer_name)
+            self.streams_[dsc.layer_name] = st
+            st.reader_.SetMaxDataSetSize(config.max_dataset_size)
+            size = st.reader_.GetDataSetSize()
+            if self.dataset_size_ == -1:
+                self.dataset_size_ = size
+            elif size != self.dataset_size_:
+                raise SystemExit("All data streams must have the same size.")
+            st.CheckGeometry()
+        if not self.streams_:
+            raise SystemExit("Error: the dataset has no data_config.")
+        if self.chunk_size_ <= 0 or self.chunk_size_ > self.dataset_size_:
+            self.chunk_size_, self.fits_on_gpu_ = self.dataset_size_, True
+        if self.batch_size_ > self.chunk_size_:
+            raise SystemExit(f"batch_size {self.batch_size_} exceeds the chunk of {self.chunk_size_} cases.")
+        self.disk_ = _DiskSide({n: self.streams_[n].reader_ for n in self.layer_names_}, self.chunk_size_, self.dataset_size_,
+                               self.randomize_cpu_, self.random_access_chunk_size_, self.row_rng_)
+        self.perm_host_ = np.arange(self.chunk_size_, dtype=np.float32)     # SetupShuffler: shuffled in place, again and again
+        self.col_index_ = np.arange(self.chunk_size_, dtype=np.float32)     # bytes form: where each column of the chunk sits now
+        self.data_, self.raw_data_ = {}, {}  # layer name -> device chunk (Matrix (dims, chunk) / torch.uint8 tensor)
+        self.input_layers_set_ = self.allocated_ = False
+        self.copy_done_ = [None, None]       # per host buffer: the event behind the last copy that read it
+        self.last_copied_, self.pending_ = -1, 0
+        self.Seek(0)
+
+    # ---- which streams keep their bytes ----
+    def SetInputLayers(self, names):
+        for name, st in self.streams_.items():
+            st.raw_ = (self.raw_chunks_ and name in names and st.reader_.GetStoredType() == np.uint8 and not st.normalize_local_)
+            if st.raw_ and self.chunk_size_ > 1 << 24:
+                raise SystemExit(f"Data stream for layer {name}: a byte chunk of more than 2^24 cases cannot be indexed; set chunk_size.")
+        self.input_layers_set_ = True
+
+    def AllocateHostMemory(self, pinned=True):
+        """One host buffer per stream, two with ``pipeline_loads``; ``pinned=False`` gives plain numpy arrays (no GPU needed)."""
+        if not self.input_layers_set_:
+            self.SetInputLayers(())
+        host, self.host_tensors_ = [], []
+        for _ in range(2 if self.pipeline_loads_ else 1):
+            arrays, tensors = {}, {}
+            for name, st in self.streams_.items():
+                shape, dtype = (self.chunk_size_, st.GetDims()), (np.uint8 if st.raw_ else np.float32)
+                if pinned:
+                    import torch
+                    tensors[name] = torch.empty(shape, dtype=torch.uint8 if st.raw_ else torch.float32, pin_memory=True)
+                    arrays[name] = tensors[name].numpy()
+                else:
+                    arrays[name] = np.zeros(shape, dtype)
+            host.append(arrays)
+            self.host_tensors_.append(tensors)
+        self.disk_.host_ = host
+
+    def AllocateMemory(self):
+        import torch
+        self.AllocateHostMemory(pinned=True)
+        for name, st in self.streams_.items():
+            if st.raw_:
+                self.raw_data_[name] = torch.empty(self.chunk_size_ * st.GetDims(), dtype=torch.uint8, device=Matrix()._dev())
+            else:
+                self.data_[name] = Matrix()
+                self.data_[name].AllocateGPUMemory(st.GetDims(), self.chunk_size_, "databuffer")
+            if st.normalize_:
+                st.LoadMeans()
+            elif st.add_pca_noise_:
+                raise SystemExit(f"Data stream for layer {name}: pca_noise_stddev needs pixelwise_normalize (S and U come from mean_file).")
+        if self.randomize_gpu_:
+            self.rand_perm_indices_ = Matrix()
+            self.rand_perm_indices_.AllocateGPUMemory(1, self.chunk_size_)
+        if any(st.raw_ for st in self.streams_.values()):
+            self.col_index_dev_ = Matrix()
+            self.col_index_dev_.AllocateGPUMemory(1, self.chunk_size_)
+            self.col_index_dev_.FromNumpy(self.col_index_)
+        self.copy_done_ = [torch.cuda.Event() for _ in self.host_]
+        self.allocated_ = True
+
+    # ---- the trainer's protocol ----
+    def GetBatchSize(self):
+        return self.batch_size_
+
+    def GetDataSetSize(self):
+        return self.dataset_size_
+
+    def GetDims(self, layer_name):
+        if layer_name not in self.streams_:
+            raise SystemExit(f"Layer name {layer_name} not found.")
+        return self.streams_[layer_name].GetDims()
+
+    def Seek(self, row):
+        self.Sync()
+        self.start_ = row
+        self.reuse_counter_ = self.multiplicity_counter_ = 0
+        self.restart_ = True
+        for st in self.streams_.values():
+            st.reader_.Seek(row)
+
+    def Sync(self):
+        if self.pipeline_loads_:
+            self.WaitForPreload()
+
+    def close(self):
+        self.WaitForPreload()
+        for st in self.streams_.values():
+            st.close()
+
+    def __del__(self):
+        t = getattr(self, "preload_thread_", None)
+        if t is not None:
+            t.join()
+
+    # ---- DataHandler::ShuffleIndices + the column shuffle (:139-144, 158-165) ----
+    def ShuffleIndices(self):
+        self.perm_rng_.shuffle(self.perm_host_)
+        self.rand_perm_indices_.FromNumpy(self.perm_host_)
+
+    def _shuffle_columns(self, data_layers):
+        self.ShuffleIndices()
+        for l in data_layers:
+            if l.GetName() in self.data_:
+                self.data_[l.GetName()].ShuffleColumns(self.rand_perm_indices_)
+        if self.raw_data_:
+            # shuffleColumns swaps columns idx[2j] and idx[2j+1] for every pair; a permutation's pairs are disjoint.  The byte chunk
+            # stays where it is: the same swaps go to the index of where each column sits
+            pairs = self.perm_host_[:2 * (self.chunk_size_ // 2)].astype(np.int64)
+            a, b = pairs[0::2], pairs[1::2]
+            self.col_index_[a], self.col_index_[b] = self.col_index_[b].copy(), self.col_index_[a].copy()
+            self.col_index_dev_.FromNumpy(self.col_index_)
+
+    # ---- DataHandler::GetBatch (:146-200) ----
+    def GetBatch(self, data_layers):
+        if not self.allocated_:
+            if not self.input_layers_set_:
+                self.SetInputLayers([l.GetName() for l in data_layers if l.IsInput()])
+            self.AllocateMemory()
+        end = self.start_ + self.batch_size_
+        if end > self.chunk_size_ or self.restart_:
+            if self.reuse_counter_ < self.max_reuse_count_ and not self.restart_:
+                self.reuse_counter_ += 1
+            elif self.nothing_on_gpu_ or not self.fits_on_gpu_:
+                if self.restart_ and self.pipeline_loads_:
+                    self.StartPreload()
+                self.nothing_on_gpu_ = False
+                self.reuse_counter_ = 0
+                self.PipelinedDiskAccess()
+            self.restart_ = False
+            if self.randomize_gpu_:
+                self._shuffle_columns(data_layers)
+            self.start_, end = 0, self.batch_size_
+        streams = [(l, self.streams_[l.GetName()]) for l in data_layers if l.GetName() in self.streams_]
+        for l, st in streams:            # all the noise first: a layer may need another's (:170-181)
+            st.SampleNoise(self.batch_size_, self.multiplicity_counter_)
+        for l, st in streams:
+            st.AddNoise(self, self.start_, end, l.GetState() if l.IsInput() else l.GetData())
+        self.multiplicity_counter_ += 1
+        if self.multiplicity_counter_ == self.multiplicity_:
+            self.multiplicity_counter_ = 0
+            self.start_ = end
+
+    # ---- DataHandler::PipelinedDiskAccess / StartPreload / WaitForPreload (:202-237) ----
+    def PipelinedDiskAccess(self):
+        import torch
+        if self.pipeline_loads_:
+            self.WaitForPreload()
+            buf = self.pending_
+        else:
+            buf = 0
+            self.copy_done_[0].synchronize()     # the last copy out of this buffer
+            self.DiskAccess(0)
+        for name, st in self.streams_.items():   # on the stream the step runs on
+            src = self.host_tensors_[buf][name].view(-1)
+            if st.raw_:
+                self.raw_data_[name].copy_(src, non_blocking=True)
+            else:
+                self.data_[name]._t[:src.numel()].copy_(src, non_blocking=True)
+                st.Preprocess(self.data_[name])
+        self.copy_done_[buf].record(torch.cuda.current_stream())
+        self.last_copied_ = buf
+        if any(st.raw_ for st in self.streams_.values()):
+            self.col_index_[:] = np.arange(self.chunk_size_, dtype=np.float32)
+            self.col_index_dev_.FromNumpy(self.col_index_)
+        if self.pipeline_loads_:
+            self.StartPreload()
+
+    def StartPreload(self):
+        import threading
+        if self.preload_thread_ is not None:
+            raise SystemExit("Trying to create new thread when previous one is still running.")
+        buf = (self.last_copied_ + 1) % 2        # the buffer no copy is reading — once its own last copy is over
+        if self.allocated_:
+            self.copy_done_[buf].synchronize()
+        self.pending_ = buf
+        if self.disk_.host_ is None:
+            self.AllocateHostMemory(pinned=False)
+        self.preload_thread_ = threading.Thread(target=self.disk_.Preload, args=(buf,), name="DataHandler preload", daemon=True)
+        self.preload_thread_.start()
+
+    def WaitForPreload(self):
+        if self.preload_thread_ is not None:
+            self.preload_thread_.join()
+            self.preload_thread_ = None
+            err, self.disk_.error_ = self.disk_.error_, None
+            if err is not None:
+                raise err
+
+    # ---- DataHandler::DiskAccess (:239-276): the host side, on this thread ----
+    def DiskAccess(self, buf=0):
+        if self.disk_.host_ is None:
+            self.AllocateHostMemory(pinned=False)
+        return self.disk_.DiskAccess(buf)
+
+    @property
+    def host_(self):
+        return self.disk_.host_

@@ -64,14 +64,30 @@ def _lib():
     sig("H5Aread", herr, hid, hid, ctypes.c_void_p)
     sig("H5Aclose", herr, hid)
     sig("H5Eset_auto2", herr, hid, ctypes.c_void_p, ctypes.c_void_p)
+    sig("H5Dget_type", hid, hid)
+    sig("H5Tget_size", sz, hid)
+    sig("H5Tget_class", ctypes.c_int, hid)
+    sig("H5Tget_sign", ctypes.c_int, hid)
+    sig("H5Tclose", herr, hid)
+    sig("H5Pcreate", hid, hid)
+    sig("H5Pset_chunk_cache", herr, hid, sz, sz, ctypes.c_double)
+    sig("H5Pclose", herr, hid)
+    sig("H5Sselect_hyperslab", herr, hid, ctypes.c_int, hs, hs, hs, hs)
     assert L.H5open() >= 0
     L.H5Eset_auto2(0, None, None)      # errors are reported through return codes below, not the library's stderr stack
     _T["float"] = ctypes.c_int64.in_dll(L, "H5T_NATIVE_FLOAT_g").value
     _T["int"] = ctypes.c_int64.in_dll(L, "H5T_NATIVE_INT_g").value
+    for dt, sym in _ROW_TYPES.items():
+        _T[dt] = ctypes.c_int64.in_dll(L, f"H5T_NATIVE_{sym}_g").value
+    _T["dapl"] = ctypes.c_int64.in_dll(L, "H5P_CLS_DATASET_ACCESS_ID_g").value
     return L
 
 
 H5F_ACC_RDONLY, H5F_ACC_TRUNC, H5P_DEFAULT, H5S_ALL, H5S_SCALAR = 0, 2, 0, 0, 0
+H5T_INTEGER, H5T_FLOAT, H5T_SGN_NONE, H5T_SGN_2, H5S_SELECT_SET = 0, 1, 0, 1, 0
+# the eight element types of DataIterator::ChooseDataIterator (src/datahandler.cc:361-389): numpy dtype -> libhdf5's native type
+_ROW_TYPES = {np.dtype(np.int8): "INT8", np.dtype(np.int32): "INT32", np.dtype(np.int64): "INT64", np.dtype(np.uint8): "UINT8",
+              np.dtype(np.uint32): "UINT32", np.dtype(np.uint64): "UINT64", np.dtype(np.float32): "FLOAT", np.dtype(np.float64): "DOUBLE"}
 
 
 class File:
@@ -171,3 +187,121 @@ class File:
         L.H5Aread(attr, _T["int"], ctypes.byref(v))
         L.H5Aclose(attr)
         return v.value
+
+    # ---- datasets of rows: what a DataHandler stream reads (src/datahandler.cc:604-721) ----
+    def WriteDataset(self, name, array):
+        """A 1-D or 2-D numpy array of one of the eight row types, stored in its own type."""
+        L = _lib()
+        a = np.ascontiguousarray(array)
+        if a.dtype not in _ROW_TYPES or a.ndim not in (1, 2):
+            raise ValueError(f"WriteDataset({name}): a 1-D or 2-D array of {sorted(str(d) for d in _ROW_TYPES)} is needed, not {a.dtype} {a.shape}")
+        dims = (ctypes.c_uint64 * a.ndim)(*a.shape)
+        space = L.H5Screate_simple(a.ndim, dims, None)
+        ds = L.H5Dcreate2(self.id, name.encode(), _T[a.dtype], space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT)
+        rc = L.H5Dwrite(ds, _T[a.dtype], H5S_ALL, H5S_ALL, H5P_DEFAULT, a.ctypes.data_as(ctypes.c_void_p)) if ds >= 0 else -1
+        L.H5Sclose(space)
+        if ds >= 0:
+            L.H5Dclose(ds)
+        if rc < 0:
+            raise OSError(f"cannot write dataset {name} to {self.path}")
+
+    def RowReader(self, name):
+        return RowReader(self, name)
+
+
+class RowReader:
+    """HDF5DataIterator<T> (src/datahandler.cc:604-721): the rows of one dataset, read as hyperslabs through a 1 GiB chunk cache.
+    ``Get`` fills a caller-owned buffer: a float32 one takes the reference's ``static_cast<float>`` of every element, whatever the
+    stored type; a uint8 one takes the bytes as they are and is accepted for an unsigned 8-bit dataset only."""
+
+    def __init__(self, file, name):
+        L = _lib()
+        self.file_, self.name_ = file, name
+        self.dapl_ = L.H5Pcreate(_T["dapl"])
+        L.H5Pset_chunk_cache(self.dapl_, ctypes.c_size_t(-1).value, 1024 * 1024 * 1024, -1.0)   # (:610-613; -1: the library's defaults)
+        self.dataset_ = L.H5Dopen2(file.id, name.encode(), self.dapl_)
+        if self.dataset_ < 0:
+            L.H5Pclose(self.dapl_)
+            raise KeyError(f"no dataset {name} in {file.path}")
+        space = L.H5Dget_space(self.dataset_)
+        self.ndims_ = L.H5Sget_simple_extent_ndims(space)
+        dims = (ctypes.c_uint64 * max(self.ndims_, 2))()
+        L.H5Sget_simple_extent_dims(space, dims, None)
+        L.H5Sclose(space)
+        self.dataset_size_ = int(dims[0])
+        self.num_dims_ = 1 if self.ndims_ == 1 else int(dims[1])    # (:619)
+        t = L.H5Dget_type(self.dataset_)
+        cls, size, sign = L.H5Tget_class(t), L.H5Tget_size(t), L.H5Tget_sign(t)
+        L.H5Tclose(t)
+        kind = {H5T_FLOAT: "f"}.get(cls) or ({H5T_SGN_2: "i", H5T_SGN_NONE: "u"}.get(sign) if cls == H5T_INTEGER else None)
+        self.dtype_ = np.dtype(f"{kind}{size}") if kind else None
+        if self.ndims_ not in (1, 2) or self.dtype_ not in _ROW_TYPES:
+            what = f"{'unsigned ' if kind == 'u' else ''}{ {'f': 'float', 'i': 'integer', 'u': 'integer'}.get(kind, 'class %d' % cls)} of {size} bytes"
+            self.close()
+            raise TypeError(f"dataset {name} in {file.path}: {self.ndims_}-D {what} is not a type a data stream can read "
+                            "(signed or unsigned integers of 1, 4 or 8 bytes, float, double)")
+        self.row_ = 0
+        self.num_reads_ = 0     # H5Dread calls so far
+
+    def close(self):
+        if self.dataset_ >= 0:
+            _lib().H5Dclose(self.dataset_)
+            _lib().H5Pclose(self.dapl_)
+            self.dataset_ = -1
+
+    def __del__(self):
+        if getattr(self, "dataset_", -1) >= 0 and self.file_.id >= 0:
+            self.close()
+
+    def GetDataSetSize(self):
+        return self.dataset_size_
+
+    def SetMaxDataSetSize(self, max_dataset_size):
+        if 0 < max_dataset_size < self.dataset_size_:
+            self.dataset_size_ = max_dataset_size
+
+    def GetDims(self):
+        return self.num_dims_
+
+    def GetStoredType(self):
+        return self.dtype_
+
+    def Seek(self, row):
+        self.row_ = row
+
+    def Tell(self):
+        return self.row_
+
+    def Get(self, out, row_start, row_end):
+        L = _lib()
+        num_rows = row_end - row_start
+        if row_start < 0 or row_end < 0 or num_rows <= 0 or row_end > self.dataset_size_:
+            raise IndexError(f"Invalid start / end {row_start} {row_end}")
+        n = num_rows * self.num_dims_
+        if not isinstance(out, np.ndarray) or not out.flags.c_contiguous or out.size < n or out.dtype not in (np.float32, np.uint8):
+            raise ValueError(f"dataset {self.name_}: Get needs a contiguous float32 or uint8 buffer of at least {n} elements")
+        if out.dtype == np.uint8 and self.dtype_ != np.uint8:
+            raise TypeError(f"dataset {self.name_} holds {self.dtype_}: only unsigned 8-bit rows can be read as stored")
+        flat = out.reshape(-1)[:n]
+        buf = flat if out.dtype == self.dtype_ else np.empty(n, self.dtype_)
+        rank = self.ndims_
+        start = (ctypes.c_uint64 * rank)(*[row_start, 0][:rank])
+        count = (ctypes.c_uint64 * rank)(*[num_rows, self.num_dims_][:rank])
+        fspace = L.H5Dget_space(self.dataset_)
+        mspace = L.H5Screate_simple(rank, count, None)
+        rc = L.H5Sselect_hyperslab(fspace, H5S_SELECT_SET, start, None, count, None)
+        if rc >= 0:
+            rc = L.H5Dread(self.dataset_, _T[self.dtype_], mspace, fspace, H5P_DEFAULT, buf.ctypes.data_as(ctypes.c_void_p))
+        L.H5Sclose(mspace)
+        L.H5Sclose(fspace)
+        if rc < 0:
+            raise OSError(f"Could not read from {row_start}:{row_end} of {self.name_}")
+        self.num_reads_ += 1
+        if buf is not flat:
+            flat[:] = buf      # the reference's static_cast<float> of every element (:701-704)
+
+    def GetNext(self, out):
+        self.Get(out, self.row_, self.row_ + 1)
+        self.row_ += 1
+        if self.row_ == self.dataset_size_:     # (:717-721)
+            self.row_ = 0

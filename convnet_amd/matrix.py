@@ -321,6 +321,21 @@ class Matrix:
         _chk(lib.extract_patches(source.GetMat(), dest.GetMat(), width_offset.GetMat(), height_offset.GetMat(), flip_bit.GetMat(),
                                  int(image_size_x), int(image_size_y), int(patch_size_x), int(patch_size_y)), "Error extracting patches")
 
+    @staticmethod
+    def StagePatchesU8(chunk, dims, num_cases, case_index, mean, std, dest, width_offset, height_offset, flip_bit, image_size_y,
+                       image_size_x, patch_size_y, patch_size_x):
+        """One batch out of a byte chunk (include/convnet_hip.h: stage_patches_u8).  ``chunk``: a torch.uint8 device tensor of
+        dims * num_cases bytes, one case per column; ``mean`` / ``std``: (dims, 1) or both None; the offsets and the flip bits: all three
+        None for no jitter.  (y, x) sizes in, like ExtractPatches."""
+        if chunk.dtype != torch.uint8 or not chunk.is_cuda or chunk.numel() != int(dims) * int(num_cases):
+            raise MatrixError(f"Error: stage_patches_u8 : the chunk must be {int(dims) * int(num_cases)} uint8 values on the device")
+        if num_cases > 1 << 24:
+            raise MatrixError("Error: stage_patches_u8 : a chunk of more than 2^24 cases cannot be indexed by a float")
+        opt = lambda m: m.GetMat() if m is not None else None   # noqa: E731
+        _chk(lib.stage_patches_u8(ctypes.c_void_p(chunk.data_ptr()), int(dims), int(num_cases), case_index.GetMat(), opt(mean), opt(std),
+                                  dest.GetMat(), opt(width_offset), opt(height_offset), opt(flip_bit), int(image_size_x), int(image_size_y),
+                                  int(patch_size_x), int(patch_size_y)), "Error staging patches")
+
     def Mult(self, val):
         if isinstance(val, Matrix):
             _chk(lib.mult_elementwise(self.GetMat(), val.GetMat(), self.GetMat(), 0.0), "mult")

@@ -110,6 +110,25 @@ class Edge(Msg):  # proto:115-222
     }
 
 
+class DataStreamConfig(Msg):  # proto:289-369
+    FIELDS = {
+        "file_pattern": "", "layer_name": "", "dataset_name": "", "data_type": "HDF5", "raw_image_size": 0, "image_size": 0,
+        "can_translate": False, "can_flip": False, "pixelwise_normalize": False, "pca_noise_stddev": 0.0, "normalize": False,
+        "gpu_id": 0, "stride": 1, "mean_file": "", "num_colors": 3, "parallel_disk_access": False, "jitter_raw_image": False,
+        "random_rotate_max_angle": 0.0, "min_scale": 0.0, "noise_layer_name": "", "avg10_full_image": False, "bbox_file": "",
+        "context_factor": 1.0, "center_on_bbox": False, "warp_bbox": False, "gpu_image_size_y": 0, "gpu_image_size_x": 0,
+        "raw_image_size_y": 0, "raw_image_size_x": 0, "image_size_y": 0, "image_size_x": 0, "is_sequence": False, "seq_length": 0,
+        "boundary_file": "", "pick_first": False, "normalize_local": False,
+    }
+
+
+class DatasetConfig(Msg):  # proto:371-382
+    FIELDS = {
+        "data_config": (list, DataStreamConfig), "batch_size": 1, "chunk_size": 0, "max_reuse_count": 0, "pipeline_loads": False,
+        "randomize_cpu": False, "randomize_gpu": False, "random_access_chunk_size": 1, "max_dataset_size": 0, "multiplicity": 1,
+    }
+
+
 class Model(Msg):  # proto:239-272
     FIELDS = {
         "name": "", "layer": (list, Layer), "edge": (list, Edge), "seed": 0, "max_iter": -1, "display_after": -1,

@@ -86,6 +86,19 @@ class TrainLoopMixin:
         if getattr(self, "parameters_backup_", None) is not None:
             self.parameters_.FromNumpy(self.parameters_backup_)
 
+    # ---- the two log files of a stamped run: src/convnet.cc:765-786 ("iter time acc..." / "iter acc...", one line per report) ----
+    def _append_log(self, attr, fields):
+        path = getattr(self, attr, None)
+        if path and self.model_.checkpoint_dir:      # named by TimestampModel; without a checkpoint_dir there is nowhere to write
+            with open(path, "a") as f:
+                f.write(" ".join(f"{v:.6g}" if isinstance(v, float) else str(v) for v in fields) + "\n")
+
+    def WriteLog(self, current_iter, time, error):
+        self._append_log("log_file_", [current_iter, float(time), *map(float, error)])
+
+    def WriteValLog(self, current_iter, error):
+        self._append_log("val_log_file_", [current_iter, *map(float, error)])
+
     # ---- the training loop: src/convnet.cc:866-1011 --------------------------------------------------------------------
     def SetupValidationDataset(self, dataset):
         self.val_dataset_ = dataset
@@ -135,6 +148,7 @@ class TrainLoopMixin:
                 now = time.time()
                 if self.is_root_:
                     log(f"Step {self.current_iter_} Time {now - start_t:.5g} s Train Acc : " + " ".join(f"{a:.5g}" for a in acc))
+                    self.WriteLog(self.current_iter_, now - start_t, acc)
                 history["train"].append((self.current_iter_, *acc))
                 start_t, train_error = now, None
             if polyak_after > 0 and (i + 1) % polyak_after == 0 and (
@@ -149,6 +163,7 @@ class TrainLoopMixin:
                 val_error.append(this_val[lr_reduce_layer_id])
                 if self.is_root_:
                     log(f"Step {self.current_iter_} Val Acc : " + " ".join(f"{v:.5g}" for v in this_val))
+                    self.WriteValLog(self.current_iter_, this_val)
                 history["val"].append((self.current_iter_, *this_val))
                 if m.reduce_lr_factor < 1.0:
                     # `reduce && counter < max && dont_reduce_lr-- < 0` (:977-978): the post-decrement only runs when the

@@ -186,6 +186,15 @@ float read_from(cudamat* mat, int row, int col, int* err_code);
  * width_offset / height_offset / flip hold one float per case (flip > 0.5 mirrors the source column). */
 int extract_patches(cudamat* images, cudamat* patches, cudamat* width_offset, cudamat* height_offset, cudamat* flip,
                     int img_width, int img_height, int patch_width, int patch_height);
+/* The same staging from a chunk kept in its stored type: `chunk` is dims x num_cases unsigned bytes on the device, one case per
+ * column as above.  case_index holds one float per batch case: the chunk column that case comes from (exact up to 2^24 columns; a
+ * wider chunk is ERROR_UNSUPPORTED).  Per element v = (float)byte, then — mean / std are (dims, 1), or both NULL — v = (v - mean[s]) /
+ * std[s] with s the SOURCE pixel: bit for bit what add_col_mult(-1), div_by_col_vec and extract_patches leave on the float cast of
+ * the chunk.  width_offset / height_offset / flip as in extract_patches, or all three NULL for no jitter (the patch is then the whole
+ * image).  The case index and the source row and column are clamped into range on the device. */
+int stage_patches_u8(void* chunk, int dims, int num_cases, cudamat* case_index, cudamat* mean, cudamat* std, cudamat* patches,
+                     cudamat* width_offset, cudamat* height_offset, cudamat* flip, int img_width, int img_height, int patch_width,
+                     int patch_height);
 /* in place: for every column pair (2j, 2j+1) swap columns idx[2j] and idx[2j+1] (cudamat.cu:2655, kShuffleColumns) */
 int shuffleColumns(cudamat* source, cudamat* rand_perm_indices);
 int add_col_vec(cudamat* mat, cudamat* vec, cudamat* target);                 /* cudamat.cuh:165 */
