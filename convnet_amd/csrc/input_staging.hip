@@ -114,6 +114,109 @@ __global__ void __launch_bounds__(256) stage_patches_u8_kernel(const unsigned ch
   }
 }
 
+// The same staging for CLIPS out of a buffer that holds every frame once (one frame per column, [colour][row][col]): plane
+// t * colours + c of a case is colour c of frame first_frame[case] + t, so a clip is clip_frames consecutive columns and overlapping
+// clips share them.  The tile, the LDS transpose and the wave stores are stage_patches_u8_kernel's.  What differs: the source pixel —
+// and with it mean / std — does not depend on t, so a block walks frames_per_block planes of its (colour, patch row, tile) with the 16
+// source offsets of every lane and their mean / std in registers: per patch pixel one byte in and four out, and the 8 B of mean / std
+// once per frames_per_block planes.  The bytes of plane t + 1 are loaded into registers before plane t is stored, so the gather's
+// latency lies behind the stores.  Write side: where N is a multiple of 4 a lane stores 4 images of a patch column as one 16-B store
+// (a quarter of the store instructions, which is what bounds the pass at small batches).  Rows of the tile past N and columns past the
+// patch are loaded with image 0's LDS terms or clamped (in range) and never stored.
+template <bool NORM, bool JITTER>
+__global__ void __launch_bounds__(256) stage_clips_u8_kernel(const unsigned char* __restrict__ frames, const float* __restrict__ first_frame,
+                                                             const float* __restrict__ mean, const float* __restrict__ sdev,
+                                                             float* __restrict__ patches, const float* __restrict__ wo,
+                                                             const float* __restrict__ ho, const float* __restrict__ flip, int N,
+                                                             int num_frames, int clip_frames, int frames_per_block, int W, int H, int pw,
+                                                             int ph, int colors) {
+  __shared__ float tile[64][65];
+  __shared__ int frame_first[64];    // the clip's first frame column, clamped into the buffer
+  __shared__ int row_base[64];       // where the source row starts inside a frame (< frame_dims)
+  __shared__ int col_first[64];      // source column of patch column 0 ...
+  __shared__ int col_step[64];       // ... and the direction the patch columns walk in (-1: flipped)
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;   // 64 x 4
+  const int c0 = blockIdx.x * 64;
+  const int rows = ph * colors;
+  const int rc = blockIdx.y % rows, t0 = (blockIdx.y / rows) * frames_per_block;
+  const int t1 = min(t0 + frames_per_block, clip_frames);
+  const int row = rc % ph, color = rc / ph;
+  const int n0 = blockIdx.z * 64;
+  if (ty == 0) {
+    const int n = n0 + tx < N ? n0 + tx : 0;
+    int sr = row, first = 0, step = 1;
+    if (JITTER) {
+      sr += min(max((int)ho[n], -H - ph), H + ph);
+      first = min(max((int)wo[n], -W - pw), W + pw);
+      if (flip[n] > 0.5f) {
+        first = W - first - 1;
+        step = -1;
+      }
+    }
+    sr = min(max(sr, 0), H - 1);
+    frame_first[tx] = min(max((int)first_frame[n], 0), num_frames - 1);
+    row_base[tx] = W * (sr + H * color);
+    col_first[tx] = first;
+    col_step[tx] = step;
+  }
+  __syncthreads();
+  const size_t frame_dims = (size_t)colors * W * H;
+  const bool wide = N - n0 > 32;   // rows 32 ... of the tile hold an image (not in a batch of 32 or a tail tile); the same for the whole block
+  auto each_row = [&](auto body) {   // this wave's tile rows j = ty + 4 i
+#pragma unroll
+    for (int i = 0; i < 8; ++i) body(i, ty + 4 * i);
+    if (wide) {
+#pragma unroll
+      for (int i = 8; i < 16; ++i) body(i, ty + 4 * i);
+    }
+  };
+  int src[16], px[16];
+  float mu[16], sd[16];
+  each_row([&](int i, int j) {
+    src[i] = row_base[j] + min(max(col_first[j] + col_step[j] * (c0 + tx), 0), W - 1);
+    if (NORM) {
+      mu[i] = mean[src[i]];
+      sd[i] = sdev[src[i]];
+    }
+  });
+  auto load_plane = [&](int t) {
+    each_row([&](int i, int j) { px[i] = frames[(size_t)min(frame_first[j] + t, num_frames - 1) * frame_dims + (size_t)src[i]]; });
+  };
+  load_plane(t0);
+  const bool vec = (N & 3) == 0 && (reinterpret_cast<uintptr_t>(patches) & 15) == 0;   // four images of a patch column are one aligned 16-B store
+  for (int t = t0; t < t1; ++t) {
+    each_row([&](int i, int j) {
+      float v = (float)px[i];
+      if (NORM) v = (v - mu[i]) / sd[i];
+      tile[j][tx] = v;
+    });
+    __syncthreads();
+    if (t + 1 < t1) load_plane(t + 1);   // in flight behind this plane's stores
+    float* out = patches + (size_t)N * pw * (row + (size_t)ph * ((size_t)t * colors + color));
+    if (vec) {   // a lane takes 4 images of one patch column, a wave 4 columns of all 64: four runs of 256 contiguous bytes per store
+      const int g = 4 * (tx & 15), n = n0 + g;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int j = 4 * (ty + 4 * k) + (tx >> 4), dc = c0 + j;
+        if (n < N && dc < pw) {
+          const f32x4 v = {tile[g][j], tile[g + 1][j], tile[g + 2][j], tile[g + 3][j]};
+          *reinterpret_cast<f32x4*>(out + (size_t)n + (size_t)N * dc) = v;
+        }
+      }
+    } else {
+#pragma unroll 4
+      for (int j = ty; j < 64; j += 4) {
+        const int dc = c0 + j, n = n0 + tx;
+        if (n < N && dc < pw) out[(size_t)n + (size_t)N * dc] = tile[tx][j];
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// 0: the launcher's choice; 1: every block stages all the clip's planes of its tile; 2: one plane per block (tools/clips_bench.py's A/B)
+int g_stage_clips_grid = 0;
+
 // one block per column pair (2j, 2j+1): swap columns idx[2j] and idx[2j+1] of the matrix in place
 __global__ void shuffle_columns_kernel(float* __restrict__ m, const float* __restrict__ idx, int height, int width) {
   const int c = 2 * blockIdx.x;
@@ -248,6 +351,49 @@ int stage_patches_u8(void* chunk, int dims, int num_cases, cudamat* case_index, 
                      jitter ? width_offset->data_device : nullptr, jitter ? height_offset->data_device : nullptr,
                      jitter ? flip->data_device : nullptr, num_images, num_cases, img_width, img_height, patch_width, patch_height,
                      num_colors);
+  return hipGetLastError() == hipSuccess ? 0 : CUDA_ERROR;
+}
+
+void convnet_hip_set_stage_clips_grid(int mode) { g_stage_clips_grid = mode == 1 || mode == 2 ? mode : 0; }
+
+int stage_clips_u8(void* frames, int frame_dims, int num_frames, cudamat* first_frame, int clip_frames, cudamat* mean, cudamat* sdev,
+                   cudamat* patches, cudamat* width_offset, cudamat* height_offset, cudamat* flip, int img_width, int img_height,
+                   int patch_width, int patch_height) {
+  if (!frames || !first_frame || !patches) return ERROR_NOT_ON_DEVICE;
+  const bool norm = mean || sdev, jitter = width_offset || height_offset || flip;
+  if (norm && !(mean && sdev)) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (jitter && !(width_offset && height_offset && flip)) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (!first_frame->on_device || !patches->on_device || (norm && (!mean->on_device || !sdev->on_device)) ||
+      (jitter && (!width_offset->on_device || !height_offset->on_device || !flip->on_device)))
+    return ERROR_NOT_ON_DEVICE;
+  if (patches->is_trans) return ERROR_TRANSPOSED;
+  if (frame_dims <= 0 || num_frames <= 0 || clip_frames <= 0 || img_width <= 0 || img_height <= 0 || patch_width <= 0 || patch_height <= 0)
+    return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (patch_width > img_width || patch_height > img_height) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (!jitter && (patch_width != img_width || patch_height != img_height)) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (frame_dims % ((long)img_width * img_height) != 0) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  const int num_colors = frame_dims / (img_width * img_height);
+  const int num_images = patches->size[0];
+  if ((long)patches->size[1] != (long)clip_frames * num_colors * patch_width * patch_height) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (numel(first_frame) != (size_t)num_images) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (norm && (mean->size[0] != frame_dims || mean->size[1] != 1 || sdev->size[0] != frame_dims || sdev->size[1] != 1))
+    return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (jitter && (numel(width_offset) != (size_t)num_images || numel(height_offset) != (size_t)num_images || numel(flip) != (size_t)num_images))
+    return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (num_frames > (1 << 24)) return ERROR_UNSUPPORTED;   // a column number must be exact as a float
+  if (num_images == 0) return 0;
+  const int frames_per_block = g_stage_clips_grid == 2 ? 1 : clip_frames;
+  const long grid_y = (long)patch_height * num_colors * divup(clip_frames, frames_per_block);
+  if (grid_y > 65535 || divup(num_images, 64) > 65535) return ERROR_UNSUPPORTED;
+  KernelTimer timer("stage_clips_u8_kernel", "input_staging", 0.0, (5.0 + (norm ? 8.0 / frames_per_block : 0.0)) * numel(patches));
+  const dim3 grid(divup(patch_width, 64), (unsigned)grid_y, divup(num_images, 64));
+  auto kernel = norm ? (jitter ? stage_clips_u8_kernel<true, true> : stage_clips_u8_kernel<true, false>)
+                     : (jitter ? stage_clips_u8_kernel<false, true> : stage_clips_u8_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream(), static_cast<const unsigned char*>(frames), first_frame->data_device,
+                     norm ? mean->data_device : nullptr, norm ? sdev->data_device : nullptr, patches->data_device,
+                     jitter ? width_offset->data_device : nullptr, jitter ? height_offset->data_device : nullptr,
+                     jitter ? flip->data_device : nullptr, num_images, num_frames, clip_frames, frames_per_block, img_width, img_height,
+                     patch_width, patch_height, num_colors);
   return hipGetLastError() == hipSuccess ? 0 : CUDA_ERROR;
 }
 

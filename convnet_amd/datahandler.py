@@ -1,7 +1,8 @@
 """Data handlers.  The contract is the reference's (src/datahandler.cc:145-198): ``GetBatch(data_layers)``
 leaves a batch in every input layer's ``state_`` (N, X*Y*C CHWN) and every output layer's ``data_``.
 ``DataHandler`` (below) is the reference's own, for HDF5 streams: built from a DatasetConfig, it reads
-chunks from disk and stages batches on the GPU; JPEG / video / text streams are refused.
+chunks from disk and stages batches on the GPU — rows of a dataset, or clips of consecutive frames of one (``is_sequence``); JPEG / video /
+text streams are refused.
 ``ChunkDataHandler`` stages from numpy arrays the caller holds; ``SyntheticDataHandler`` makes noise: inputs are N(0,1) (the real pipeline feeds mean/std-normalised
 pixels, :496-507), labels uniform ints stored as float (N,1); ``num_batches`` distinct batches are
 pre-generated on the device and cycled, so no host work sits inside a timed step."""
@@ -175,14 +176,103 @@ _REFUSED_TYPES = {
     "CROPS": "crops of raw images", "VIDEO_RAW": "video files decoded on the host"}
 
 
+class _SequenceReader:
+    """SequenceDataIterator (src/datahandler.cc:1100-1200) over a row reader of frames: row ``i`` is the clip of ``seq_length`` frames that
+    starts at frame ``row_mapping_[i]`` (its first frame alone with ``pick_first``).  The rest is the row reader's protocol."""
+
+    def __init__(self, base, seq_length, boundary_file, pick_first, layer_name):
+        import sys
+        self.base_, self.seq_length_, self.pick_first_ = base, seq_length, pick_first
+        self.frame_size_ = base.GetDims()
+        self.num_dims_ = self.frame_size_ * (1 if pick_first else seq_length)
+        frames = base.GetDataSetSize()
+        if not boundary_file:
+            print("No boundary file found. Assuming entire dataset is one sequence.", file=sys.stderr)
+            num_frames = [frames]
+        else:
+            try:
+                with open(boundary_file) as f:
+                    num_frames = [int(w) for w in f.read().split()]
+            except (OSError, ValueError) as e:
+                raise SystemExit(f"Data stream for layer {layer_name}: Could not open boundary file : {boundary_file} ({e})")
+            if sum(num_frames) != frames:
+                raise SystemExit(f"Data stream for layer {layer_name}: Error: Dataset has {frames} frames but boundary_file adds up to "
+                                 f"{sum(num_frames)}")
+        self.row_mapping_ = self.SetupRowMapping(num_frames, seq_length)
+        self.dataset_size_ = len(self.row_mapping_)
+        if self.dataset_size_ == 0:
+            raise SystemExit(f"Data stream for layer {layer_name}: no sequence holds seq_length {seq_length} frames.")
+        self.row_ = 0
+
+    @staticmethod
+    def SetupRowMapping(num_frames, seq_length):
+        """(:1158-1173): every frame a whole clip can start at, in dataset order."""
+        mapping, start = [], 0
+        for num_f in num_frames:
+            num_valid_start_pos = num_f - seq_length + 1
+            if num_valid_start_pos <= 0:
+                print(f"Warning: Number of frames {num_f} is smaller than sequence length {seq_length} for sequence starting at {start}. "
+                      "This sequence will be skipped.")
+            mapping.extend(range(start, start + max(num_valid_start_pos, 0)))
+            start += num_f
+        return np.asarray(mapping, np.int64)
+
+    def GetDataSetSize(self):
+        return self.dataset_size_
+
+    def SetMaxDataSetSize(self, max_dataset_size):
+        self.base_.SetMaxDataSetSize(max_dataset_size)      # the base's alone: the clip count stays (:1198-1200; NOTES.md)
+
+    def GetDims(self):
+        return self.num_dims_
+
+    def GetStoredType(self):
+        return self.base_.GetStoredType()
+
+    @property
+    def num_reads_(self):
+        return self.base_.num_reads_
+
+    def Seek(self, row):
+        self.row_ = row
+
+    def Tell(self):
+        return self.row_
+
+    def Get(self, out, row_start, row_end):
+        """Row by row, as DataIterator::Get(start, end) (:578-583): one read of the base per clip."""
+        if row_start < 0 or row_end <= row_start or row_end > self.dataset_size_:
+            raise IndexError(f"Asking for row {row_start} {row_end}")
+        rows = out.reshape(-1)[:(row_end - row_start) * self.num_dims_].reshape(row_end - row_start, self.num_dims_)
+        for i, row in enumerate(range(row_start, row_end)):
+            mapped = int(self.row_mapping_[row])
+            self.base_.Get(rows[i], mapped, mapped + (1 if self.pick_first_ else self.seq_length_))
+
+    def close(self):
+        self.base_.close()
+
+
+def _run_frames(row_mapping, seq_length, length):
+    """The most frames a run of ``length`` consecutive clip rows lays into a frame buffer, over every row it can start at.  A clip adds the
+    frames its predecessor did not hold: min(seq_length, gap to it) — the mapping is increasing — and a whole clip behind the wrap to row
+    0; prefix sums of that over the doubled list give every start's total."""
+    gaps = np.append(np.minimum(np.diff(row_mapping), seq_length), seq_length)
+    sums = np.concatenate([[0], np.cumsum(np.concatenate([gaps, gaps]))])
+    starts = np.arange(len(row_mapping))
+    return int(seq_length + (sums[starts + length - 1] - sums[starts]).max())
+
+
 class _Stream:
     """DataIterator + HDF5DataIterator<T> for one ``data_config`` (src/datahandler.cc:415-570, 604-721)."""
 
     def __init__(self, dsc):
         from . import hdf5io
         name = dsc.layer_name
-        if dsc.is_sequence:
-            raise SystemExit(f"Data stream for layer {name}: is_sequence (sequence data) is not supported.")
+        if dsc.is_sequence and dsc.seq_length < 1:
+            raise SystemExit(f"Data stream for layer {name}: is_sequence needs a seq_length of at least 1, not {dsc.seq_length}.")
+        if dsc.is_sequence and dsc.pca_noise_stddev > 0:
+            raise SystemExit(f"Data stream for layer {name}: pca_noise_stddev is not supported on a sequence stream: the colour noise "
+                             "has 3 columns, a clip 3 x seq_length planes.")
         if dsc.data_type != "HDF5":
             what = _REFUSED_TYPES.get(dsc.data_type)
             if what is None:
@@ -196,6 +286,15 @@ class _Stream:
         self.config_, self.layer_name_ = dsc, name
         self.file_ = hdf5io.File(dsc.file_pattern)
         self.reader_ = self.file_.RowReader(dsc.dataset_name)
+        self.frame_size_, self.frames_ = self.reader_.GetDims(), 1      # a row is frames_ frames of frame_size_ values
+        self.is_sequence_, self.frames_once_ = dsc.is_sequence, False
+        if dsc.is_sequence:
+            try:
+                self.reader_ = _SequenceReader(self.reader_, dsc.seq_length, dsc.boundary_file, dsc.pick_first, name)
+            except BaseException:
+                self.close()
+                raise
+            self.frames_ = 1 if dsc.pick_first else dsc.seq_length
         self.image_size_y_ = dsc.image_size_y if dsc.has_image_size_y() else dsc.image_size
         self.image_size_x_ = dsc.image_size_x if dsc.has_image_size_x() else dsc.image_size
         self.gpu_image_size_y_ = dsc.gpu_image_size_y if dsc.has_gpu_image_size_y() else self.image_size_y_
@@ -219,11 +318,12 @@ class _Stream:
 
     def StagedDims(self):
         """The width of the batch this stream leaves in its layer."""
-        return self.num_colors_ * self.gpu_image_size_y_ * self.gpu_image_size_x_ if self.Jitters() else self.GetDims()
+        return self.frames_ * self.num_colors_ * self.gpu_image_size_y_ * self.gpu_image_size_x_ if self.Jitters() else self.GetDims()
 
     def CheckGeometry(self):
-        if self.Jitters() and self.GetDims() != self.num_colors_ * self.image_size_y_ * self.image_size_x_:
-            raise SystemExit(f"Data stream for layer {self.layer_name_}: rows of {self.GetDims()} values are not {self.num_colors_} colours of "
+        if self.Jitters() and self.frame_size_ != self.num_colors_ * self.image_size_y_ * self.image_size_x_:
+            what = "frames" if self.is_sequence_ else "rows"
+            raise SystemExit(f"Data stream for layer {self.layer_name_}: {what} of {self.frame_size_} values are not {self.num_colors_} colours of "
                              f"{self.image_size_y_} x {self.image_size_x_} pixels.")
         if self.gpu_image_size_y_ > self.image_size_y_ or self.gpu_image_size_x_ > self.image_size_x_:
             raise SystemExit(f"Data stream for layer {self.layer_name_}: gpu_image_size exceeds image_size.")
@@ -231,7 +331,7 @@ class _Stream:
     # ---- DataIterator::LoadMeans (:445-474) ----
     def LoadMeans(self):
         from . import hdf5io
-        dims = self.GetDims()
+        dims = self.frame_size_                # a sequence stream's mean / std are its base stream's: per FRAME pixel (:1152-1156)
         with hdf5io.File(self.config_.mean_file) as f:
             if self.pixelwise_normalize_:
                 # mean_ = zeros(num_pixels, num_channels) + the row vector pixel_mean, reshaped to a column: every channel's value repeated
@@ -253,6 +353,14 @@ class _Stream:
 
     # ---- DataIterator::Preprocess (:496-507): the float chunk, once per load ----
     def Preprocess(self, m):
+        if self.frames_ > 1:                   # SequenceDataIterator::Preprocess (:1152-1156): the base stream's, frame by frame
+            m.Reshape(self.frame_size_, -1)
+            self._preprocess_frames(m)
+            m.Reshape(self.frame_size_ * self.frames_, -1)
+        else:
+            self._preprocess_frames(m)
+
+    def _preprocess_frames(self, m):
         if self.normalize_local_:
             dims = m.GetRows()
             m.Reshape(dims // self.num_colors_, -1)
@@ -299,7 +407,15 @@ class _Stream:
     # ---- DataIterator::AddNoise (:520-532), from either chunk form ----
     def AddNoise(self, handler, start, end, output):
         jit = self.Jitters()
-        if self.raw_:
+        if self.frames_once_:
+            name, fs = self.layer_name_, self.frame_size_
+            handler.first_frame_dev_[name].GetSlice(self.index_slice_, start, end)
+            used = handler.frames_used_[name]
+            offs = (self.width_offset_, self.height_offset_, self.flip_bit_) if jit else (None, None, None)
+            geom = ((self.image_size_y_, self.image_size_x_, self.gpu_image_size_y_, self.gpu_image_size_x_) if jit else (1, fs, 1, fs))
+            Matrix.StageClipsU8(handler.raw_data_[name][:used * fs], fs, used, self.index_slice_, self.frames_,
+                                self.mean_ if self.normalize_ else None, self.std_ if self.normalize_ else None, output, *offs, *geom)
+        elif self.raw_:
             handler.col_index_dev_.GetSlice(self.index_slice_, start, end)
             dims = self.GetDims()
             offs = (self.width_offset_, self.height_offset_, self.flip_bit_) if jit else (None, None, None)
@@ -337,6 +453,10 @@ class _DiskSide:
             self.random_indices_ = rng.permutation(dataset_size)
         self.host_ = None                    # [buffer][layer name] -> (chunk_size, dims) array
         self.error_ = None
+        # frames-once streams (sequence streams that keep their bytes): host_ holds (frames, frame_size) — every frame of a run once —
+        self.frames_once_ = set()            # their layer names
+        self.first_frame_ = None             # [buffer][layer name] -> (chunk_size,) float32: the buffer row of every clip's first frame
+        self.frames_used_ = None             # [buffer][layer name] -> how many rows of host_ the chunk filled
 
     def Preload(self, buf):
         try:
@@ -355,13 +475,19 @@ class _DiskSide:
             self.random_indices_ind_ += num_rand
         for name, reader in self.readers_.items():
             out = self.host_[buf][name]
+            once = name in self.frames_once_
+            load = self._lay_run if once else self._load_run
+            if once:
+                out = (out, self.first_frame_[buf][name], [0])
             if random_rows is None:
-                self._load_run(reader, out, 0, reader.Tell(), self.chunk_size_, seek=True)
+                load(reader, out, 0, reader.Tell(), self.chunk_size_, seek=True)
             else:
                 for i, row in enumerate(random_rows):
                     at = i * self.random_access_chunk_size_
                     # (the last run stops at the end of the chunk: the reference reads a whole run there, past its buffer)
-                    self._load_run(reader, out, at, row, min(self.random_access_chunk_size_, self.chunk_size_ - at))
+                    load(reader, out, at, row, min(self.random_access_chunk_size_, self.chunk_size_ - at))
+            if once:
+                self.frames_used_[buf][name] = out[2][0]
         return self.host_[buf]
 
     def _load_run(self, reader, out, at, row, count, seek=False):
@@ -370,6 +496,26 @@ class _DiskSide:
         while count > 0:
             n = min(count, size - row)
             reader.Get(out[at:at + n], row, row + n)
+            at, count, row = at + n, count - n, (row + n) % size
+        if seek:
+            reader.Seek(row)
+
+    def _lay_run(self, reader, out, at, row, count, seek=False):
+        """The same run of clip rows for a frames-once stream: the union of the clips' frame ranges goes behind what the buffer holds,
+        in dataset order and every frame once; clips ``at`` ... of the table get the buffer row of their first frame.  A piece — one
+        hyperslab read — ends where the next clip does not start one frame on: at a sequence boundary, at a skipped sequence, at the wrap
+        to row 0."""
+        frames, table, filled = out
+        mapping, T, size = reader.row_mapping_, reader.seq_length_, self.dataset_size_
+        while count > 0:
+            n = min(count, size - row)
+            m = mapping[row:row + n]
+            cuts = np.flatnonzero(np.diff(m) != 1) + 1
+            for a, b in zip([0, *cuts.tolist()], [*cuts.tolist(), n]):
+                lo, hi = int(m[a]), int(m[b - 1]) + T
+                reader.base_.Get(frames[filled[0]:filled[0] + hi - lo], lo, hi)
+                table[at + a:at + b] = filled[0] + (m[a:b] - lo)
+                filled[0] += hi - lo
             at, count, row = at + n, count - n, (row + n) % size
         if seek:
             reader.Seek(row)
@@ -387,6 +533,12 @@ class DataHandler:
     the memory); nothing touches it after the copy, ``randomize_gpu`` swaps entries of a column index instead, and a batch is ONE
     ``StagePatchesU8``: cast, mean / std, crop, flip and transpose together, bit for bit what the float form leaves.
     ``raw_chunks=False`` forces the float form everywhere.
+
+    A sequence stream (``is_sequence``, ``seq_length`` T) reads clips: its float form is the reference's, one materialised clip of T frames
+    per column.  Its bytes form (the same conditions, and not ``pick_first``) keeps every frame of a run of consecutive clip rows ONCE —
+    the union of the clips' frame ranges, in dataset order — beside a table of the buffer column of every clip's first frame;
+    ``randomize_gpu`` swaps entries of that table, and a batch is ONE ``StageClipsU8`` that gathers each clip's T consecutive columns.
+    The buffers are sized once, to the exact worst case over run starts (``FrameBufferSize``); only the used prefix is uploaded.
 
     The two host RNGs (random rows, column permutation) are numpy generators seeded from ``seed``; the device RNG calls are the
     library's, in the reference's order.  ``pipeline_loads``: one preload thread reads the next chunk into the idle one of two pinned
@@ -428,6 +580,8 @@ class DataHandler:
         self.perm_host_ = np.arange(self.chunk_size_, dtype=np.float32)     # SetupShuffler: shuffled in place, again and again
         self.col_index_ = np.arange(self.chunk_size_, dtype=np.float32)     # bytes form: where each column of the chunk sits now
         self.data_, self.raw_data_ = {}, {}  # layer name -> device chunk (Matrix (dims, chunk) / torch.uint8 tensor)
+        # frames-once streams: where every clip's first frame sits in raw_data_ (host copy, device copy) and how many frames that holds
+        self.first_frame_, self.first_frame_dev_, self.frames_used_ = {}, {}, {}
         self.input_layers_set_ = self.allocated_ = False
         self.copy_done_ = [None, None]       # per host buffer: the event behind the last copy that read it
         self.last_copied_, self.pending_ = -1, 0
@@ -436,20 +590,42 @@ class DataHandler:
     # ---- which streams keep their bytes ----
     def SetInputLayers(self, names):
         for name, st in self.streams_.items():
-            st.raw_ = (self.raw_chunks_ and name in names and st.reader_.GetStoredType() == np.uint8 and not st.normalize_local_)
+            st.raw_ = (self.raw_chunks_ and name in names and st.reader_.GetStoredType() == np.uint8 and not st.normalize_local_
+                       and not (st.is_sequence_ and st.config_.pick_first))
+            st.frames_once_ = st.raw_ and st.is_sequence_
+            if st.frames_once_ and self.FrameBufferSize(name) > 1 << 24:
+                raise SystemExit(f"Data stream for layer {name}: a byte chunk of more than 2^24 frames cannot be indexed; set chunk_size.")
             if st.raw_ and self.chunk_size_ > 1 << 24:
                 raise SystemExit(f"Data stream for layer {name}: a byte chunk of more than 2^24 cases cannot be indexed; set chunk_size.")
+        self.disk_.frames_once_ = {name for name, st in self.streams_.items() if st.frames_once_}
         self.input_layers_set_ = True
+
+    def FrameBufferSize(self, name):
+        """The frames a chunk of a frames-once stream can need at the most: the exact worst case over the rows its runs can start at —
+        one run of the whole chunk read sequentially, ``random_access_chunk_size`` rows each (the last one cut at the chunk's end) under
+        ``randomize_cpu``.  Runs follow each other in the buffer, so their worst cases add up."""
+        r = self.streams_[name].reader_
+        if not self.randomize_cpu_:
+            return _run_frames(r.row_mapping_, r.seq_length_, self.chunk_size_)
+        whole, last = divmod(self.chunk_size_, self.random_access_chunk_size_)
+        return (whole * _run_frames(r.row_mapping_, r.seq_length_, min(self.random_access_chunk_size_, self.chunk_size_)) if whole else 0) + \
+            (_run_frames(r.row_mapping_, r.seq_length_, last) if last else 0)
 
     def AllocateHostMemory(self, pinned=True):
         """One host buffer per stream, two with ``pipeline_loads``; ``pinned=False`` gives plain numpy arrays (no GPU needed)."""
         if not self.input_layers_set_:
             self.SetInputLayers(())
         host, self.host_tensors_ = [], []
+        sizes = {name: self.FrameBufferSize(name) for name, st in self.streams_.items() if st.frames_once_}    # once: here
+        self.disk_.first_frame_, self.disk_.frames_used_ = [], []
         for _ in range(2 if self.pipeline_loads_ else 1):
             arrays, tensors = {}, {}
+            self.disk_.first_frame_.append({name: np.zeros(self.chunk_size_, np.float32) for name in sizes})
+            self.disk_.frames_used_.append({name: 0 for name in sizes})
             for name, st in self.streams_.items():
                 shape, dtype = (self.chunk_size_, st.GetDims()), (np.uint8 if st.raw_ else np.float32)
+                if st.frames_once_:
+                    shape = (sizes[name], st.frame_size_)
                 if pinned:
                     import torch
                     tensors[name] = torch.empty(shape, dtype=torch.uint8 if st.raw_ else torch.float32, pin_memory=True)
@@ -464,7 +640,13 @@ class DataHandler:
         import torch
         self.AllocateHostMemory(pinned=True)
         for name, st in self.streams_.items():
-            if st.raw_:
+            if st.frames_once_:              # (the host buffer's size: the worst case, allocated once)
+                self.raw_data_[name] = torch.empty(self.host_[0][name].size, dtype=torch.uint8, device=Matrix()._dev())
+                self.first_frame_[name] = np.zeros(self.chunk_size_, np.float32)
+                self.first_frame_dev_[name] = Matrix()
+                self.first_frame_dev_[name].AllocateGPUMemory(1, self.chunk_size_)
+                self.frames_used_[name] = 0
+            elif st.raw_:
                 self.raw_data_[name] = torch.empty(self.chunk_size_ * st.GetDims(), dtype=torch.uint8, device=Matrix()._dev())
             else:
                 self.data_[name] = Matrix()
@@ -476,7 +658,7 @@ class DataHandler:
         if self.randomize_gpu_:
             self.rand_perm_indices_ = Matrix()
             self.rand_perm_indices_.AllocateGPUMemory(1, self.chunk_size_)
-        if any(st.raw_ for st in self.streams_.values()):
+        if any(st.raw_ and not st.frames_once_ for st in self.streams_.values()):
             self.col_index_dev_ = Matrix()
             self.col_index_dev_.AllocateGPUMemory(1, self.chunk_size_)
             self.col_index_dev_.FromNumpy(self.col_index_)
@@ -532,8 +714,12 @@ class DataHandler:
             # stays where it is: the same swaps go to the index of where each column sits
             pairs = self.perm_host_[:2 * (self.chunk_size_ // 2)].astype(np.int64)
             a, b = pairs[0::2], pairs[1::2]
-            self.col_index_[a], self.col_index_[b] = self.col_index_[b].copy(), self.col_index_[a].copy()
-            self.col_index_dev_.FromNumpy(self.col_index_)
+            if len(self.raw_data_) > len(self.first_frame_):
+                self.col_index_[a], self.col_index_[b] = self.col_index_[b].copy(), self.col_index_[a].copy()
+                self.col_index_dev_.FromNumpy(self.col_index_)
+            for name, table in self.first_frame_.items():        # a frames-once stream: the same swaps on its first-frame table
+                table[a], table[b] = table[b].copy(), table[a].copy()
+                self.first_frame_dev_[name].FromNumpy(table)
 
     # ---- DataHandler::GetBatch (:146-200) ----
     def GetBatch(self, data_layers):
@@ -577,14 +763,19 @@ class DataHandler:
             self.DiskAccess(0)
         for name, st in self.streams_.items():   # on the stream the step runs on
             src = self.host_tensors_[buf][name].view(-1)
-            if st.raw_:
+            if st.frames_once_:                  # the used prefix alone, and the table that goes with it
+                used = self.frames_used_[name] = self.disk_.frames_used_[buf][name]
+                self.raw_data_[name][:used * st.frame_size_].copy_(src[:used * st.frame_size_], non_blocking=True)
+                self.first_frame_[name][:] = self.disk_.first_frame_[buf][name]
+                self.first_frame_dev_[name].FromNumpy(self.first_frame_[name])
+            elif st.raw_:
                 self.raw_data_[name].copy_(src, non_blocking=True)
             else:
                 self.data_[name]._t[:src.numel()].copy_(src, non_blocking=True)
                 st.Preprocess(self.data_[name])
         self.copy_done_[buf].record(torch.cuda.current_stream())
         self.last_copied_ = buf
-        if any(st.raw_ for st in self.streams_.values()):
+        if len(self.raw_data_) > len(self.first_frame_):
             self.col_index_[:] = np.arange(self.chunk_size_, dtype=np.float32)
             self.col_index_dev_.FromNumpy(self.col_index_)
         if self.pipeline_loads_:

@@ -336,6 +336,21 @@ class Matrix:
                                   dest.GetMat(), opt(width_offset), opt(height_offset), opt(flip_bit), int(image_size_x), int(image_size_y),
                                   int(patch_size_x), int(patch_size_y)), "Error staging patches")
 
+    @staticmethod
+    def StageClipsU8(frames, frame_dims, num_frames, first_frame, clip_frames, mean, std, dest, width_offset, height_offset, flip_bit,
+                     image_size_y, image_size_x, patch_size_y, patch_size_x):
+        """One batch of clips out of a byte buffer that holds every frame once (include/convnet_hip.h: stage_clips_u8).  ``frames``: a
+        torch.uint8 device tensor of frame_dims * num_frames bytes, one frame per column; ``first_frame``: the column of every case's
+        first frame; ``mean`` / ``std``: (frame_dims, 1) or both None.  (y, x) sizes in, like ExtractPatches."""
+        if frames.dtype != torch.uint8 or not frames.is_cuda or frames.numel() != int(frame_dims) * int(num_frames):
+            raise MatrixError(f"Error: stage_clips_u8 : the frames must be {int(frame_dims) * int(num_frames)} uint8 values on the device")
+        if num_frames > 1 << 24:
+            raise MatrixError("Error: stage_clips_u8 : a buffer of more than 2^24 frames cannot be indexed by a float")
+        opt = lambda m: m.GetMat() if m is not None else None   # noqa: E731
+        _chk(lib.stage_clips_u8(ctypes.c_void_p(frames.data_ptr()), int(frame_dims), int(num_frames), first_frame.GetMat(), int(clip_frames),
+                                opt(mean), opt(std), dest.GetMat(), opt(width_offset), opt(height_offset), opt(flip_bit), int(image_size_x),
+                                int(image_size_y), int(patch_size_x), int(patch_size_y)), "Error staging clips")
+
     def Mult(self, val):
         if isinstance(val, Matrix):
             _chk(lib.mult_elementwise(self.GetMat(), val.GetMat(), self.GetMat(), 0.0), "mult")

@@ -195,6 +195,20 @@ int extract_patches(cudamat* images, cudamat* patches, cudamat* width_offset, cu
 int stage_patches_u8(void* chunk, int dims, int num_cases, cudamat* case_index, cudamat* mean, cudamat* std, cudamat* patches,
                      cudamat* width_offset, cudamat* height_offset, cudamat* flip, int img_width, int img_height, int patch_width,
                      int patch_height);
+/* Clips out of a byte buffer that holds every frame ONCE: `frames` is frame_dims x num_frames unsigned bytes on the device, one frame per
+ * column, [colour][row][col].  first_frame holds one float per batch case: the column of the clip's first frame (exact up to 2^24
+ * columns; more is ERROR_UNSUPPORTED).  patches is (cases, clip_frames * colours * ph * pw): plane t * colours + c of case n is colour c
+ * of frame column min(max((int)first_frame[n], 0) + t, num_frames - 1) — time outermost, the layout of a layer with image_size_t > 1.
+ * Per element the arithmetic is stage_patches_u8's with s the source pixel INSIDE the frame (mean / std are (frame_dims, 1), or both
+ * NULL): bit for bit what add_col_mult(-1), div_by_col_vec and extract_patches leave on the float cast of the materialised clips with
+ * mean / std tiled clip_frames times.  Offsets / flip: one value per case (the whole clip shares its crop), or all three NULL.  The
+ * frame column and the source row and column are clamped on the device; shape errors return stage_patches_u8's codes. */
+int stage_clips_u8(void* frames, int frame_dims, int num_frames, cudamat* first_frame, int clip_frames, cudamat* mean, cudamat* std,
+                   cudamat* patches, cudamat* width_offset, cudamat* height_offset, cudamat* flip, int img_width, int img_height,
+                   int patch_width, int patch_height);
+/* stage_clips_u8's grid, for A/B timing (tools/clips_bench.py); the results are the same.  0: the library's choice; 1: a block stages
+ * all clip_frames planes of its (colour, patch row, tile) with mean / std in registers; 2: one plane per block. */
+void convnet_hip_set_stage_clips_grid(int mode);
 /* in place: for every column pair (2j, 2j+1) swap columns idx[2j] and idx[2j+1] (cudamat.cu:2655, kShuffleColumns) */
 int shuffleColumns(cudamat* source, cudamat* rand_perm_indices);
 int add_col_vec(cudamat* mat, cudamat* vec, cudamat* target);                 /* cudamat.cuh:165 */
