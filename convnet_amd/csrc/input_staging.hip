@@ -289,6 +289,63 @@ int check_rowvec(const cudamat* mat, const cudamat* vec, const cudamat* target) 
   return 0;
 }
 
+// The arguments of a byte-staging entry (stage_patches_u8, stage_clips_u8) and what checking them works out.  A case is ``planes``
+// columns of ``dims`` bytes out of ``count`` (1: a chunk of cases; clip_frames: a buffer of frames), ``index`` names the (first) column
+// of every image, and a block stages ``planes_per_block`` planes of its 64 x 64 tile: the kernel's arguments between count and geometry.
+struct StageU8 {
+  void* data;
+  int dims, count;
+  cudamat *index, *mean, *sdev, *patches, *width_offset, *height_offset, *flip;
+  int img_width, img_height, patch_width, patch_height, planes, planes_per_block;
+  bool norm, jitter;
+  int num_colors, num_images;   // (0 images: nothing to launch)
+  long grid_y;
+};
+
+// Error code or 0, in the precedence tests/test_stage_patches_gpu.py and tests/test_stage_clips_gpu.py list.
+int check_stage_u8(StageU8& s) {
+  if (!s.data || !s.index || !s.patches) return ERROR_NOT_ON_DEVICE;
+  s.norm = s.mean || s.sdev;
+  s.jitter = s.width_offset || s.height_offset || s.flip;
+  if ((s.norm && !(s.mean && s.sdev)) || (s.jitter && !(s.width_offset && s.height_offset && s.flip))) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (!s.index->on_device || !s.patches->on_device || (s.norm && (!s.mean->on_device || !s.sdev->on_device)) ||
+      (s.jitter && (!s.width_offset->on_device || !s.height_offset->on_device || !s.flip->on_device)))
+    return ERROR_NOT_ON_DEVICE;
+  if (s.patches->is_trans) return ERROR_TRANSPOSED;
+  if (s.dims <= 0 || s.count <= 0 || s.planes <= 0 || s.img_width <= 0 || s.img_height <= 0 || s.patch_width <= 0 || s.patch_height <= 0)
+    return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (s.patch_width > s.img_width || s.patch_height > s.img_height) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (!s.jitter && (s.patch_width != s.img_width || s.patch_height != s.img_height)) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (s.dims % ((long)s.img_width * s.img_height) != 0) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  s.num_colors = s.dims / (s.img_width * s.img_height);
+  const size_t num_images = s.num_images = s.patches->size[0];
+  if ((long)s.patches->size[1] != (long)s.planes * s.num_colors * s.patch_width * s.patch_height || numel(s.index) != num_images)
+    return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (s.norm && (s.mean->size[0] != s.dims || s.mean->size[1] != 1 || s.sdev->size[0] != s.dims || s.sdev->size[1] != 1))
+    return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (s.jitter && (numel(s.width_offset) != num_images || numel(s.height_offset) != num_images || numel(s.flip) != num_images))
+    return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (s.count > (1 << 24)) return ERROR_UNSUPPORTED;   // a column number must be exact as a float
+  if (num_images == 0) return 0;
+  s.grid_y = (long)s.patch_height * s.num_colors * divup(s.planes, s.planes_per_block);
+  return s.grid_y > 65535 || divup(s.num_images, 64) > 65535 ? ERROR_UNSUPPORTED : 0;
+}
+
+// the instantiation of a byte-staging kernel template for (norm, jitter)
+#define STAGE_U8_KERNEL(kernel, s) \
+  ((s).norm ? ((s).jitter ? kernel<true, true> : kernel<true, false>) : ((s).jitter ? kernel<false, true> : kernel<false, false>))
+
+template <typename Kernel, typename... Planes>
+int launch_stage_u8(const StageU8& s, Kernel kernel, Planes... planes) {
+  const dim3 grid(divup(s.patch_width, 64), (unsigned)s.grid_y, divup(s.num_images, 64));
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream(), static_cast<const unsigned char*>(s.data), s.index->data_device,
+                     s.norm ? s.mean->data_device : nullptr, s.norm ? s.sdev->data_device : nullptr, s.patches->data_device,
+                     s.jitter ? s.width_offset->data_device : nullptr, s.jitter ? s.height_offset->data_device : nullptr,
+                     s.jitter ? s.flip->data_device : nullptr, s.num_images, s.count, planes..., s.img_width, s.img_height, s.patch_width,
+                     s.patch_height, s.num_colors);
+  return hipGetLastError() == hipSuccess ? 0 : CUDA_ERROR;
+}
+
 }  // namespace
 }  // namespace chip
 
@@ -319,39 +376,11 @@ int extract_patches(cudamat* images, cudamat* patches, cudamat* width_offset, cu
 int stage_patches_u8(void* chunk, int dims, int num_cases, cudamat* case_index, cudamat* mean, cudamat* sdev, cudamat* patches,
                      cudamat* width_offset, cudamat* height_offset, cudamat* flip, int img_width, int img_height, int patch_width,
                      int patch_height) {
-  if (!chunk || !case_index || !patches) return ERROR_NOT_ON_DEVICE;
-  const bool norm = mean || sdev, jitter = width_offset || height_offset || flip;
-  if (norm && !(mean && sdev)) return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if (jitter && !(width_offset && height_offset && flip)) return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if (!case_index->on_device || !patches->on_device || (norm && (!mean->on_device || !sdev->on_device)) ||
-      (jitter && (!width_offset->on_device || !height_offset->on_device || !flip->on_device)))
-    return ERROR_NOT_ON_DEVICE;
-  if (patches->is_trans) return ERROR_TRANSPOSED;
-  if (dims <= 0 || num_cases <= 0 || img_width <= 0 || img_height <= 0 || patch_width <= 0 || patch_height <= 0)
-    return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if (patch_width > img_width || patch_height > img_height) return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if (!jitter && (patch_width != img_width || patch_height != img_height)) return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if (dims % ((long)img_width * img_height) != 0) return ERROR_INCOMPATIBLE_DIMENSIONS;
-  const int num_colors = dims / (img_width * img_height);
-  const int num_images = patches->size[0];
-  if ((long)patches->size[1] != (long)num_colors * patch_width * patch_height) return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if (numel(case_index) != (size_t)num_images) return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if (norm && (mean->size[0] != dims || mean->size[1] != 1 || sdev->size[0] != dims || sdev->size[1] != 1)) return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if (jitter && (numel(width_offset) != (size_t)num_images || numel(height_offset) != (size_t)num_images || numel(flip) != (size_t)num_images))
-    return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if (num_cases > (1 << 24)) return ERROR_UNSUPPORTED;   // a column number must be exact as a float
-  if (num_images == 0) return 0;
-  if ((long)patch_height * num_colors > 65535 || divup(num_images, 64) > 65535) return ERROR_UNSUPPORTED;
+  StageU8 s{chunk, dims, num_cases, case_index, mean, sdev, patches, width_offset, height_offset, flip, img_width, img_height, patch_width,
+            patch_height, 1, 1};
+  if (const int e = check_stage_u8(s); e || s.num_images == 0) return e;
   KernelTimer timer("stage_patches_u8_kernel", "input_staging", 0.0, 5.0 * numel(patches));
-  const dim3 grid(divup(patch_width, 64), patch_height * num_colors, divup(num_images, 64));
-  auto kernel = norm ? (jitter ? stage_patches_u8_kernel<true, true> : stage_patches_u8_kernel<true, false>)
-                     : (jitter ? stage_patches_u8_kernel<false, true> : stage_patches_u8_kernel<false, false>);
-  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream(), static_cast<const unsigned char*>(chunk), case_index->data_device,
-                     norm ? mean->data_device : nullptr, norm ? sdev->data_device : nullptr, patches->data_device,
-                     jitter ? width_offset->data_device : nullptr, jitter ? height_offset->data_device : nullptr,
-                     jitter ? flip->data_device : nullptr, num_images, num_cases, img_width, img_height, patch_width, patch_height,
-                     num_colors);
-  return hipGetLastError() == hipSuccess ? 0 : CUDA_ERROR;
+  return launch_stage_u8(s, STAGE_U8_KERNEL(stage_patches_u8_kernel, s));
 }
 
 void convnet_hip_set_stage_clips_grid(int mode) { g_stage_clips_grid = mode == 1 || mode == 2 ? mode : 0; }
@@ -359,42 +388,12 @@ void convnet_hip_set_stage_clips_grid(int mode) { g_stage_clips_grid = mode == 1
 int stage_clips_u8(void* frames, int frame_dims, int num_frames, cudamat* first_frame, int clip_frames, cudamat* mean, cudamat* sdev,
                    cudamat* patches, cudamat* width_offset, cudamat* height_offset, cudamat* flip, int img_width, int img_height,
                    int patch_width, int patch_height) {
-  if (!frames || !first_frame || !patches) return ERROR_NOT_ON_DEVICE;
-  const bool norm = mean || sdev, jitter = width_offset || height_offset || flip;
-  if (norm && !(mean && sdev)) return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if (jitter && !(width_offset && height_offset && flip)) return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if (!first_frame->on_device || !patches->on_device || (norm && (!mean->on_device || !sdev->on_device)) ||
-      (jitter && (!width_offset->on_device || !height_offset->on_device || !flip->on_device)))
-    return ERROR_NOT_ON_DEVICE;
-  if (patches->is_trans) return ERROR_TRANSPOSED;
-  if (frame_dims <= 0 || num_frames <= 0 || clip_frames <= 0 || img_width <= 0 || img_height <= 0 || patch_width <= 0 || patch_height <= 0)
-    return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if (patch_width > img_width || patch_height > img_height) return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if (!jitter && (patch_width != img_width || patch_height != img_height)) return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if (frame_dims % ((long)img_width * img_height) != 0) return ERROR_INCOMPATIBLE_DIMENSIONS;
-  const int num_colors = frame_dims / (img_width * img_height);
-  const int num_images = patches->size[0];
-  if ((long)patches->size[1] != (long)clip_frames * num_colors * patch_width * patch_height) return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if (numel(first_frame) != (size_t)num_images) return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if (norm && (mean->size[0] != frame_dims || mean->size[1] != 1 || sdev->size[0] != frame_dims || sdev->size[1] != 1))
-    return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if (jitter && (numel(width_offset) != (size_t)num_images || numel(height_offset) != (size_t)num_images || numel(flip) != (size_t)num_images))
-    return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if (num_frames > (1 << 24)) return ERROR_UNSUPPORTED;   // a column number must be exact as a float
-  if (num_images == 0) return 0;
   const int frames_per_block = g_stage_clips_grid == 2 ? 1 : clip_frames;
-  const long grid_y = (long)patch_height * num_colors * divup(clip_frames, frames_per_block);
-  if (grid_y > 65535 || divup(num_images, 64) > 65535) return ERROR_UNSUPPORTED;
-  KernelTimer timer("stage_clips_u8_kernel", "input_staging", 0.0, (5.0 + (norm ? 8.0 / frames_per_block : 0.0)) * numel(patches));
-  const dim3 grid(divup(patch_width, 64), (unsigned)grid_y, divup(num_images, 64));
-  auto kernel = norm ? (jitter ? stage_clips_u8_kernel<true, true> : stage_clips_u8_kernel<true, false>)
-                     : (jitter ? stage_clips_u8_kernel<false, true> : stage_clips_u8_kernel<false, false>);
-  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream(), static_cast<const unsigned char*>(frames), first_frame->data_device,
-                     norm ? mean->data_device : nullptr, norm ? sdev->data_device : nullptr, patches->data_device,
-                     jitter ? width_offset->data_device : nullptr, jitter ? height_offset->data_device : nullptr,
-                     jitter ? flip->data_device : nullptr, num_images, num_frames, clip_frames, frames_per_block, img_width, img_height,
-                     patch_width, patch_height, num_colors);
-  return hipGetLastError() == hipSuccess ? 0 : CUDA_ERROR;
+  StageU8 s{frames, frame_dims, num_frames, first_frame, mean, sdev, patches, width_offset, height_offset, flip, img_width, img_height,
+            patch_width, patch_height, clip_frames, frames_per_block};
+  if (const int e = check_stage_u8(s); e || s.num_images == 0) return e;
+  KernelTimer timer("stage_clips_u8_kernel", "input_staging", 0.0, (5.0 + (s.norm ? 8.0 / frames_per_block : 0.0)) * numel(patches));
+  return launch_stage_u8(s, STAGE_U8_KERNEL(stage_clips_u8_kernel, s), clip_frames, frames_per_block);
 }
 
 int shuffleColumns(cudamat* source, cudamat* rand_perm_indices) {

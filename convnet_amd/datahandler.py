@@ -7,6 +7,7 @@ text streams are refused.
 pixels, :496-507), labels uniform ints stored as float (N,1); ``num_batches`` distinct batches are
 pre-generated on the device and cycled, so no host work sits inside a timed step."""
 import numpy as np
+import torch
 
 from .matrix import Matrix
 
@@ -52,6 +53,59 @@ class SyntheticDataHandler:
             (l.GetState() if l.IsInput() else l.GetData()).Set(b[l.GetName()])
 
 
+class _Jitter:
+    """The crop / flip of one stream: its geometry and the per-case offsets and flip bits on the device — DataIterator::SampleNoise
+    (src/datahandler.cc:534-570) and what every staging call takes of it."""
+
+    def __init__(self, image_size_y, image_size_x, gpu_image_size_y, gpu_image_size_x, translate, flip):
+        self.image_size_y_, self.image_size_x_ = image_size_y, image_size_x
+        self.gpu_image_size_y_, self.gpu_image_size_x_ = gpu_image_size_y, gpu_image_size_x
+        self.translate_, self.flip_ = translate, flip
+        self.width_offset_, self.height_offset_, self.flip_bit_ = Matrix(), Matrix(), Matrix()
+
+    def Jitters(self):
+        return self.image_size_y_ != self.gpu_image_size_y_ or self.image_size_x_ != self.gpu_image_size_x_ or self.flip_
+
+    def Sample(self, batch_size, multiplicity_id):
+        if not self.Jitters():
+            return
+        max_offset_y = self.image_size_y_ - self.gpu_image_size_y_
+        max_offset_x = self.image_size_x_ - self.gpu_image_size_x_
+        if self.width_offset_.GetCols() != batch_size:
+            for m in (self.width_offset_, self.height_offset_, self.flip_bit_):
+                m.AllocateGPUMemory(1, batch_size)
+        if self.translate_:
+            self.height_offset_.FillWithRand()
+            self.width_offset_.FillWithRand()
+            self.height_offset_.Mult(max_offset_y + 1)         # rounded down by the kernel's int()
+            self.width_offset_.Mult(max_offset_x + 1)
+        else:                                                  # centre / corner patches by multiplicity id
+            w, h = [(max_offset_x // 2, max_offset_y // 2), (0, 0), (max_offset_x, 0), (max_offset_x, max_offset_y),
+                    (0, max_offset_y)][multiplicity_id % 5]
+            self.height_offset_.Set(h)
+            self.width_offset_.Set(w)
+        if self.flip_:
+            self.flip_bit_.FillWithRand()                      # flip if > 0.5
+        else:
+            self.flip_bit_.Set(multiplicity_id // 5)
+
+    def StagingArgs(self, dims):
+        """The (offsets, flip bits, geometry) arguments of ExtractPatches / StagePatchesU8 / StageClipsU8 for rows (frames) of ``dims``
+        values.  No jitter: a transpose of whole rows, whatever image_size says (the reference's CopyTranspose)."""
+        if self.Jitters():
+            return (self.width_offset_, self.height_offset_, self.flip_bit_, self.image_size_y_, self.image_size_x_, self.gpu_image_size_y_,
+                    self.gpu_image_size_x_)
+        return (None, None, None, 1, dims, 1, dims)
+
+    def StageColumns(self, chunk, slice_, start, end, output):
+        """DataIterator::AddNoise (:520-531) from a float chunk: columns ``start:end`` of ``chunk``, through the view ``slice_``."""
+        chunk.GetSlice(slice_, start, end)
+        if self.Jitters():
+            Matrix.ExtractPatches(slice_, output, *self.StagingArgs(chunk.GetRows()))
+        else:
+            slice_.CopyTranspose(output)
+
+
 class ChunkDataHandler:
     """GPU-resident dataset chunk + per-batch staging on the GPU: DataHandler::GetBatch (src/datahandler.cc:146-198) and
     DataIterator::SampleNoise / AddNoise / Preprocess (:496-570) for one image stream and one label stream.
@@ -71,8 +125,8 @@ class ChunkDataHandler:
         assert dims == colors * image_size * image_size and labels.shape[0] == self.chunk_size_
         assert batch_size <= self.chunk_size_
         self.batch_size_ = batch_size
-        self.image_size_, self.gpu_image_size_ = image_size, crop_size or image_size
-        self.colors_, self.translate_, self.flip_, self.randomize_ = colors, translate, flip, randomize
+        self.jitter_ = _Jitter(image_size, image_size, crop_size or image_size, crop_size or image_size, translate, flip)
+        self.colors_, self.randomize_ = colors, randomize
         self.rng_ = np.random.default_rng(seed)
         # Sequential (non-shuffled) use — validation, feature extraction — reads the dataset round-robin, so the batch that
         # straddles the end continues with the first cases (the reference's chunk loader wraps the same way): keep a copy
@@ -94,8 +148,8 @@ class ChunkDataHandler:
         self.perm_.AllocateGPUMemory(1, self.chunk_size_)
         self.perm_host_ = np.arange(self.chunk_size_, dtype=np.float32)
         self.start_ = 0
-        self.width_offset_, self.height_offset_, self.flip_bit_ = Matrix(), Matrix(), Matrix()
-        for m in (self.width_offset_, self.height_offset_, self.flip_bit_):
+        self.width_offset_, self.height_offset_, self.flip_bit_ = self.jitter_.width_offset_, self.jitter_.height_offset_, self.jitter_.flip_bit_
+        for m in (self.width_offset_, self.height_offset_, self.flip_bit_):     # (here, jitter or not)
             m.AllocateGPUMemory(1, batch_size)
         self.slice_, self.label_slice_ = Matrix(), Matrix()
         self.multiplicity_counter_ = 0
@@ -119,33 +173,10 @@ class ChunkDataHandler:
     def Sync(self):
         pass
 
-    def _jitter(self):
-        return self.image_size_ != self.gpu_image_size_ or self.flip_
-
     def ShuffleIndices(self):
         # DataHandler::ShuffleIndices (:139-144): random_shuffle of the SAME index array every time, then to the device
         self.rng_.shuffle(self.perm_host_)
         self.perm_.FromNumpy(self.perm_host_)
-
-    def SampleNoise(self):
-        # DataIterator::SampleNoise (:533-570)
-        if not self._jitter():
-            return
-        max_off = self.image_size_ - self.gpu_image_size_
-        if self.translate_:
-            self.height_offset_.FillWithRand()
-            self.width_offset_.FillWithRand()
-            self.height_offset_.Mult(max_off + 1)          # rounded down by the kernel's int()
-            self.width_offset_.Mult(max_off + 1)
-        else:                                              # centre / corner patches by multiplicity id
-            mid = self.multiplicity_counter_ % 5
-            w, h = [(max_off // 2, max_off // 2), (0, 0), (max_off, 0), (max_off, max_off), (0, max_off)][mid]
-            self.height_offset_.Set(h)
-            self.width_offset_.Set(w)
-        if self.flip_:
-            self.flip_bit_.FillWithRand()                  # flip if > 0.5
-        else:
-            self.flip_bit_.Set(self.multiplicity_counter_ // 5)
 
     def GetBatch(self, data_layers):
         end = self.start_ + self.batch_size_
@@ -154,16 +185,10 @@ class ChunkDataHandler:
             self.data_.ShuffleColumns(self.perm_)
             self.labels_.ShuffleColumns(self.perm_)
             self.start_, end = 0, self.batch_size_
-        self.SampleNoise()
+        self.jitter_.Sample(self.batch_size_, self.multiplicity_counter_)
         for l in data_layers:
             if l.IsInput():
-                self.data_.GetSlice(self.slice_, self.start_, end)
-                dest = l.GetState()
-                if self._jitter():                         # DataIterator::AddNoise (:520-531)
-                    Matrix.ExtractPatches(self.slice_, dest, self.width_offset_, self.height_offset_, self.flip_bit_, self.image_size_,
-                                          self.image_size_, self.gpu_image_size_, self.gpu_image_size_)
-                else:
-                    self.slice_.CopyTranspose(dest)
+                self.jitter_.StageColumns(self.data_, self.slice_, self.start_, end, l.GetState())
             else:
                 self.labels_.GetSlice(self.label_slice_, self.start_, end)
                 self.label_slice_.CopyTranspose(l.GetData())
@@ -287,7 +312,8 @@ class _Stream:
         self.file_ = hdf5io.File(dsc.file_pattern)
         self.reader_ = self.file_.RowReader(dsc.dataset_name)
         self.frame_size_, self.frames_ = self.reader_.GetDims(), 1      # a row is frames_ frames of frame_size_ values
-        self.is_sequence_, self.frames_once_ = dsc.is_sequence, False
+        self.is_sequence_ = dsc.is_sequence
+        self.form_ = None            # how the chunk is kept: DataHandler.SetInputLayers decides
         if dsc.is_sequence:
             try:
                 self.reader_ = _SequenceReader(self.reader_, dsc.seq_length, dsc.boundary_file, dsc.pick_first, name)
@@ -295,38 +321,42 @@ class _Stream:
                 self.close()
                 raise
             self.frames_ = 1 if dsc.pick_first else dsc.seq_length
-        self.image_size_y_ = dsc.image_size_y if dsc.has_image_size_y() else dsc.image_size
-        self.image_size_x_ = dsc.image_size_x if dsc.has_image_size_x() else dsc.image_size
-        self.gpu_image_size_y_ = dsc.gpu_image_size_y if dsc.has_gpu_image_size_y() else self.image_size_y_
-        self.gpu_image_size_x_ = dsc.gpu_image_size_x if dsc.has_gpu_image_size_x() else self.image_size_x_
-        self.num_colors_, self.translate_, self.flip_ = dsc.num_colors, dsc.can_translate, dsc.can_flip
+        size_y = dsc.image_size_y if dsc.has_image_size_y() else dsc.image_size
+        size_x = dsc.image_size_x if dsc.has_image_size_x() else dsc.image_size
+        self.jitter_ = j = _Jitter(size_y, size_x, dsc.gpu_image_size_y if dsc.has_gpu_image_size_y() else size_y,
+                                   dsc.gpu_image_size_x if dsc.has_gpu_image_size_x() else size_x, dsc.can_translate, dsc.can_flip)
+        self.width_offset_, self.height_offset_, self.flip_bit_ = j.width_offset_, j.height_offset_, j.flip_bit_
+        self.num_colors_ = dsc.num_colors
         self.normalize_ = dsc.normalize or dsc.pixelwise_normalize
         self.pixelwise_normalize_, self.normalize_local_ = dsc.pixelwise_normalize, dsc.normalize_local
         self.pca_noise_stddev_ = dsc.pca_noise_stddev
         self.add_pca_noise_ = dsc.pca_noise_stddev > 0
-        self.raw_ = False            # the chunk form: bytes (True) or float (DataHandler.SetInputLayers decides)
         self.mean_ = self.std_ = None
-        self.width_offset_, self.height_offset_, self.flip_bit_ = Matrix(), Matrix(), Matrix()
         self.pca_noise1_, self.pca_noise2_ = Matrix(), Matrix()
-        self.slice_, self.index_slice_ = Matrix(), Matrix()
+
+    raw_ = property(lambda self: self.form_ is not None and self.form_.raw_)
+    frames_once_ = property(lambda self: self.form_ is not None and self.form_.frames_once_)
 
     def GetDims(self):
         return self.reader_.GetDims()
 
-    def Jitters(self):
-        return self.image_size_y_ != self.gpu_image_size_y_ or self.image_size_x_ != self.gpu_image_size_x_ or self.flip_
-
     def StagedDims(self):
         """The width of the batch this stream leaves in its layer."""
-        return self.frames_ * self.num_colors_ * self.gpu_image_size_y_ * self.gpu_image_size_x_ if self.Jitters() else self.GetDims()
+        j = self.jitter_
+        return self.frames_ * self.num_colors_ * j.gpu_image_size_y_ * j.gpu_image_size_x_ if j.Jitters() else self.GetDims()
 
     def CheckGeometry(self):
-        if self.Jitters() and self.frame_size_ != self.num_colors_ * self.image_size_y_ * self.image_size_x_:
+        j = self.jitter_
+        if j.Jitters() and self.frame_size_ != self.num_colors_ * j.image_size_y_ * j.image_size_x_:
             what = "frames" if self.is_sequence_ else "rows"
             raise SystemExit(f"Data stream for layer {self.layer_name_}: {what} of {self.frame_size_} values are not {self.num_colors_} colours of "
-                             f"{self.image_size_y_} x {self.image_size_x_} pixels.")
-        if self.gpu_image_size_y_ > self.image_size_y_ or self.gpu_image_size_x_ > self.image_size_x_:
+                             f"{j.image_size_y_} x {j.image_size_x_} pixels.")
+        if j.gpu_image_size_y_ > j.image_size_y_ or j.gpu_image_size_x_ > j.image_size_x_:
             raise SystemExit(f"Data stream for layer {self.layer_name_}: gpu_image_size exceeds image_size.")
+
+    def Normalizers(self):
+        """(mean, std) for a staging call that normalises on the way, or no pair."""
+        return (self.mean_, self.std_) if self.normalize_ else (None, None)
 
     # ---- DataIterator::LoadMeans (:445-474) ----
     def LoadMeans(self):
@@ -370,30 +400,6 @@ class _Stream:
             m.AddColVec(self.mean_, -1)
             m.DivideByColVec(self.std_)
 
-    # ---- DataIterator::SampleNoise (:534-570) ----
-    def SampleNoise(self, batch_size, multiplicity_id):
-        if not self.Jitters():
-            return
-        max_offset_y = self.image_size_y_ - self.gpu_image_size_y_
-        max_offset_x = self.image_size_x_ - self.gpu_image_size_x_
-        if self.width_offset_.GetCols() != batch_size:
-            for m in (self.width_offset_, self.height_offset_, self.flip_bit_):
-                m.AllocateGPUMemory(1, batch_size)
-        if self.translate_:
-            self.height_offset_.FillWithRand()
-            self.width_offset_.FillWithRand()
-            self.height_offset_.Mult(max_offset_y + 1)
-            self.width_offset_.Mult(max_offset_x + 1)
-        else:
-            w, h = [(max_offset_x // 2, max_offset_y // 2), (0, 0), (max_offset_x, 0), (max_offset_x, max_offset_y),
-                    (0, max_offset_y)][multiplicity_id % 5]
-            self.height_offset_.Set(h)
-            self.width_offset_.Set(w)
-        if self.flip_:
-            self.flip_bit_.FillWithRand()
-        else:
-            self.flip_bit_.Set(multiplicity_id // 5)
-
     # ---- DataIterator::AddPCANoise (:509-518) ----
     def AddPCANoise(self, m):
         if self.pca_noise1_.GetRows() != m.GetRows():
@@ -404,32 +410,9 @@ class _Stream:
         Matrix.Dot(self.pca_noise1_, self.eig_vectors_, self.pca_noise2_, 0, 1)
         m.AddToEachPixel(self.pca_noise2_, self.pca_noise_stddev_)
 
-    # ---- DataIterator::AddNoise (:520-532), from either chunk form ----
-    def AddNoise(self, handler, start, end, output):
-        jit = self.Jitters()
-        if self.frames_once_:
-            name, fs = self.layer_name_, self.frame_size_
-            handler.first_frame_dev_[name].GetSlice(self.index_slice_, start, end)
-            used = handler.frames_used_[name]
-            offs = (self.width_offset_, self.height_offset_, self.flip_bit_) if jit else (None, None, None)
-            geom = ((self.image_size_y_, self.image_size_x_, self.gpu_image_size_y_, self.gpu_image_size_x_) if jit else (1, fs, 1, fs))
-            Matrix.StageClipsU8(handler.raw_data_[name][:used * fs], fs, used, self.index_slice_, self.frames_,
-                                self.mean_ if self.normalize_ else None, self.std_ if self.normalize_ else None, output, *offs, *geom)
-        elif self.raw_:
-            handler.col_index_dev_.GetSlice(self.index_slice_, start, end)
-            dims = self.GetDims()
-            offs = (self.width_offset_, self.height_offset_, self.flip_bit_) if jit else (None, None, None)
-            # no jitter: a transpose of whole rows, whatever image_size says (the reference's CopyTranspose)
-            geom = ((self.image_size_y_, self.image_size_x_, self.gpu_image_size_y_, self.gpu_image_size_x_) if jit else (1, dims, 1, dims))
-            Matrix.StagePatchesU8(handler.raw_data_[self.layer_name_], dims, handler.chunk_size_, self.index_slice_,
-                                  self.mean_ if self.normalize_ else None, self.std_ if self.normalize_ else None, output, *offs, *geom)
-        else:
-            handler.data_[self.layer_name_].GetSlice(self.slice_, start, end)
-            if jit:
-                Matrix.ExtractPatches(self.slice_, output, self.width_offset_, self.height_offset_, self.flip_bit_, self.image_size_y_,
-                                      self.image_size_x_, self.gpu_image_size_y_, self.gpu_image_size_x_)
-            else:
-                self.slice_.CopyTranspose(output)
+    # ---- DataIterator::AddNoise (:520-532) ----
+    def AddNoise(self, start, end, output):
+        self.form_.Stage(self, start, end, output)
         if self.add_pca_noise_:
             self.AddPCANoise(output)
 
@@ -438,25 +421,200 @@ class _Stream:
         self.file_.close()
 
 
-class _DiskSide:
-    """DataHandler::DiskAccess / LoadChunk (src/datahandler.cc:239-314): everything the preload thread touches — the row readers, the
-    host buffers and the random-row list.  libhdf5 and numpy only: no GPU call, no ``Matrix``, and no way back to the handler, so a
-    handler that is dropped while a preload runs is collected (and joins the thread) at once."""
+# ---- the chunk forms ----------------------------------------------------------------------------------------------------------------------
+# A form has two halves.  The DISK half (_RowsDisk / _FramesDisk) is all the preload thread sees of it: the row reader, the shape of a host
+# buffer and how a run of rows gets into one — libhdf5 and numpy only.  The DEVICE half (_FloatForm / _BytesForm / _FramesOnceForm, which
+# holds its disk half as ``disk_``) owns the chunk on the GPU: storage, upload, what randomize_gpu does to it, staging a batch.
 
-    def __init__(self, readers, chunk_size, dataset_size, randomize_cpu, random_access_chunk_size, rng):
-        self.readers_ = readers              # layer name -> RowReader, in data_config order
+class _RowsDisk:
+    """Rows as they are in the dataset, one per buffer row: cast to float by the reader (float form) or kept as bytes (bytes form)."""
+
+    def __init__(self, reader, chunk_size, dataset_size, dtype):
+        self.reader_, self.chunk_size_, self.dataset_size_, self.dtype_ = reader, chunk_size, dataset_size, dtype
+
+    def HostBuffers(self, count):
+        """(shape, dtype) of a host buffer of this stream; ``count`` of them are about to be made."""
+        return (self.chunk_size_, self.reader_.GetDims()), self.dtype_
+
+    def LoadRun(self, out, buf, at, row, count, seek=False):
+        """``count`` consecutive rows from ``row`` into host buffer ``out`` (number ``buf``) from chunk position ``at`` on, wrapping at the
+        end of the dataset (GetNext's wrap, :717-721; LoadChunk's, :305-311)."""
+        size = self.dataset_size_
+        while count > 0:
+            n = min(count, size - row)
+            self.LoadPiece(out, buf, at, row, n)
+            at, count, row = at + n, count - n, (row + n) % size
+        if seek:
+            self.reader_.Seek(row)
+
+    def LoadPiece(self, out, buf, at, row, n):
+        self.reader_.Get(out[at:at + n], row, row + n)
+
+
+class _FramesDisk(_RowsDisk):
+    """Clip rows of a sequence stream with every frame held once: a buffer is (frames, frame_size); beside each there is the table of the
+    buffer row of every clip's first frame (float32, as it goes to the device) and the number of buffer rows the chunk filled."""
+
+    def __init__(self, reader, chunk_size, dataset_size, buffer_frames):
+        super().__init__(reader, chunk_size, dataset_size, np.uint8)
+        self.buffer_frames_ = buffer_frames  # DataHandler.FrameBufferSize: the worst case, sized once
+        self.first_frame_ = self.frames_used_ = None         # [buffer]
+
+    def HostBuffers(self, count):
+        self.first_frame_ = [np.zeros(self.chunk_size_, np.float32) for _ in range(count)]
+        self.frames_used_ = [0] * count
+        return (self.buffer_frames_, self.reader_.frame_size_), self.dtype_
+
+    def LoadPiece(self, frames, buf, at, row, n):
+        """The union of the clips' frame ranges goes behind what the buffer holds (a run at chunk position 0 begins it), in dataset order
+        and every frame once; clips ``at`` ... of the table get the buffer row of their first frame.  One hyperslab read ends where the
+        next clip does not start one frame on: at a sequence boundary, at a skipped sequence, at the wrap to row 0."""
+        table, filled = self.first_frame_[buf], self.frames_used_[buf] if at else 0
+        m, T = self.reader_.row_mapping_[row:row + n], self.reader_.seq_length_
+        cuts = np.flatnonzero(np.diff(m) != 1) + 1
+        for a, b in zip([0, *cuts.tolist()], [*cuts.tolist(), n]):
+            lo, hi = int(m[a]), int(m[b - 1]) + T
+            self.reader_.base_.Get(frames[filled:filled + hi - lo], lo, hi)
+            table[at + a:at + b] = filled + (m[a:b] - lo)
+            filled += hi - lo
+        self.frames_used_[buf] = filled
+
+
+class _Index:
+    """``chunk_size`` column numbers beside a byte chunk, as floats, on the host and on the device: a batch gathers the columns that
+    entries ``start:end`` name.  The chunk stays where the copy left it; randomize_gpu swaps entries here."""
+
+    def __init__(self, chunk_size):
+        self.host_ = np.arange(chunk_size, dtype=np.float32)
+        self.dev_ = Matrix()
+
+    def Allocate(self):
+        self.dev_.AllocateGPUMemory(1, len(self.host_))
+
+    def Set(self, values):
+        self.host_[:] = values
+        self.dev_.FromNumpy(self.host_)
+
+    def Reset(self):
+        self.Set(np.arange(len(self.host_), dtype=np.float32))
+
+    def Swap(self, a, b):
+        self.host_[a], self.host_[b] = self.host_[b].copy(), self.host_[a].copy()
+        self.dev_.FromNumpy(self.host_)
+
+
+class _Form:
+    """What randomize_gpu does to a chunk, given the shuffled permutation: shuffleColumns swaps columns idx[2j] and idx[2j + 1] for every
+    pair (``a[j]``, ``b[j]`` on the host; a permutation's pairs are disjoint).  A float chunk has its columns swapped on the device; a
+    byte chunk stays where it is, and the same swaps go to the index of where each column sits."""
+
+    def ShuffleColumns(self, rand_perm_indices):
+        pass
+
+    def SwapEntries(self, a, b):
+        pass
+
+
+class _FloatForm(_Form):
+    """The reference's form: rows are cast to float on the host, the chunk is a (dims, cases) ``Matrix``, ``Preprocess`` normalises all of
+    it at load, randomize_gpu swaps its columns, and a batch is ``ExtractPatches`` / ``CopyTranspose`` of a slice."""
+    raw_ = frames_once_ = False
+
+    def __init__(self, st, chunk_size, dataset_size):
+        self.chunk_size_ = chunk_size
+        self.disk_ = _RowsDisk(st.reader_, chunk_size, dataset_size, np.float32)
+        self.data_, self.slice_ = Matrix(), Matrix()
+
+    def AllocateMemory(self, st):
+        self.data_.AllocateGPUMemory(st.GetDims(), self.chunk_size_, "databuffer")
+
+    def Upload(self, st, src, buf):
+        self.data_._t[:src.numel()].copy_(src, non_blocking=True)
+        st.Preprocess(self.data_)
+
+    def ShuffleColumns(self, rand_perm_indices):
+        self.data_.ShuffleColumns(rand_perm_indices)
+
+    def Stage(self, st, start, end, output):
+        st.jitter_.StageColumns(self.data_, self.slice_, start, end, output)
+
+
+class _BytesForm(_Form):
+    """The chunk stays on the GPU exactly as read — a ``torch.uint8`` tensor, a quarter of the transfer and of the memory — and nothing
+    touches it after the copy.  Which column a case sits in is the handler's one column index, shared by all its streams of this form (the
+    handler resets and swaps it); a batch is ONE ``StagePatchesU8``: cast, mean / std, crop, flip and transpose together."""
+    raw_, frames_once_ = True, False
+
+    def __init__(self, st, chunk_size, dataset_size, col_index):
+        self.chunk_size_, self.col_index_ = chunk_size, col_index
+        self.disk_ = _RowsDisk(st.reader_, chunk_size, dataset_size, np.uint8)
+        self.data_, self.index_slice_ = None, Matrix()
+
+    def AllocateMemory(self, st):
+        self.data_ = torch.empty(self.chunk_size_ * st.GetDims(), dtype=torch.uint8, device=Matrix()._dev())
+
+    def Upload(self, st, src, buf):
+        self.data_.copy_(src, non_blocking=True)
+
+    def Stage(self, st, start, end, output):
+        self.col_index_.dev_.GetSlice(self.index_slice_, start, end)
+        dims = st.GetDims()
+        Matrix.StagePatchesU8(self.data_, dims, self.chunk_size_, self.index_slice_, *st.Normalizers(), output, *st.jitter_.StagingArgs(dims))
+
+
+class _FramesOnceForm(_Form):
+    """A sequence stream's byte form: every frame of a run of consecutive clip rows is held ONCE — the union of the clips' frame ranges, in
+    dataset order — beside this stream's own table of the buffer column of every clip's first frame.  Only the used prefix of a host buffer
+    is uploaded; randomize_gpu swaps entries of the table; a batch is ONE ``StageClipsU8`` that gathers each clip's consecutive columns."""
+    raw_ = frames_once_ = True
+
+    def __init__(self, st, chunk_size, dataset_size, buffer_frames):
+        self.disk_ = _FramesDisk(st.reader_, chunk_size, dataset_size, buffer_frames)
+        self.data_, self.frames_used_ = None, 0
+        self.first_frame_, self.index_slice_ = _Index(chunk_size), Matrix()
+
+    def AllocateMemory(self, st):            # (the host buffer's size: the worst case, allocated once)
+        self.data_ = torch.empty(self.disk_.buffer_frames_ * st.frame_size_, dtype=torch.uint8, device=Matrix()._dev())
+        self.first_frame_.Allocate()
+
+    def Upload(self, st, src, buf):          # the used prefix alone, and the table that goes with it
+        used = self.frames_used_ = self.disk_.frames_used_[buf]
+        self.data_[:used * st.frame_size_].copy_(src[:used * st.frame_size_], non_blocking=True)
+        self.first_frame_.Set(self.disk_.first_frame_[buf])
+
+    def SwapEntries(self, a, b):
+        self.first_frame_.Swap(a, b)
+
+    def Stage(self, st, start, end, output):
+        self.first_frame_.dev_.GetSlice(self.index_slice_, start, end)
+        fs, used = st.frame_size_, self.frames_used_
+        Matrix.StageClipsU8(self.data_[:used * fs], fs, used, self.index_slice_, st.frames_, *st.Normalizers(), output,
+                            *st.jitter_.StagingArgs(fs))
+
+
+class _DiskSide:
+    """DataHandler::DiskAccess / LoadChunk (src/datahandler.cc:239-314): everything the preload thread touches — the disk halves of the
+    streams' forms (their row readers), the host buffers and the random-row list.  libhdf5 and numpy only: no GPU call, no ``Matrix``, and
+    no way back to the handler, so a handler that is dropped while a preload runs is collected (and joins the thread) at once."""
+
+    def __init__(self, chunk_size, dataset_size, randomize_cpu, random_access_chunk_size, rng):
+        self.halves_ = None                  # layer name -> disk half of the stream's form, in data_config order (SetInputLayers)
         self.chunk_size_, self.dataset_size_ = chunk_size, dataset_size
         self.randomize_cpu_, self.random_access_chunk_size_ = randomize_cpu, random_access_chunk_size
         self.rng_ = rng
         self.random_indices_ind_ = 0
         if randomize_cpu:
             self.random_indices_ = rng.permutation(dataset_size)
-        self.host_ = None                    # [buffer][layer name] -> (chunk_size, dims) array
+        self.host_ = None                    # [buffer][layer name] -> array, shaped as the disk half says
         self.error_ = None
-        # frames-once streams (sequence streams that keep their bytes): host_ holds (frames, frame_size) — every frame of a run once —
-        self.frames_once_ = set()            # their layer names
-        self.first_frame_ = None             # [buffer][layer name] -> (chunk_size,) float32: the buffer row of every clip's first frame
-        self.frames_used_ = None             # [buffer][layer name] -> how many rows of host_ the chunk filled
+
+    def _beside(self, what):
+        return [{name: getattr(half, what)[buf] for name, half in self.halves_.items() if getattr(half, what, None) is not None}
+                for buf in range(len(self.host_ or ()))]
+
+    # [buffer][layer name] -> what a disk half keeps beside that host buffer (read-only views, as ``DataHandler.host_`` is)
+    first_frame_ = property(lambda self: self._beside("first_frame_"))
+    frames_used_ = property(lambda self: self._beside("frames_used_"))
 
     def Preload(self, buf):
         try:
@@ -473,52 +631,16 @@ class _DiskSide:
                 self.random_indices_ind_ = 0
             random_rows = self.random_indices_[self.random_indices_ind_:self.random_indices_ind_ + num_rand].tolist()
             self.random_indices_ind_ += num_rand
-        for name, reader in self.readers_.items():
+        for name, half in self.halves_.items():
             out = self.host_[buf][name]
-            once = name in self.frames_once_
-            load = self._lay_run if once else self._load_run
-            if once:
-                out = (out, self.first_frame_[buf][name], [0])
             if random_rows is None:
-                load(reader, out, 0, reader.Tell(), self.chunk_size_, seek=True)
+                half.LoadRun(out, buf, 0, half.reader_.Tell(), self.chunk_size_, seek=True)
             else:
                 for i, row in enumerate(random_rows):
                     at = i * self.random_access_chunk_size_
                     # (the last run stops at the end of the chunk: the reference reads a whole run there, past its buffer)
-                    load(reader, out, at, row, min(self.random_access_chunk_size_, self.chunk_size_ - at))
-            if once:
-                self.frames_used_[buf][name] = out[2][0]
+                    half.LoadRun(out, buf, at, row, min(self.random_access_chunk_size_, self.chunk_size_ - at))
         return self.host_[buf]
-
-    def _load_run(self, reader, out, at, row, count, seek=False):
-        """``count`` consecutive rows from ``row``, wrapping at the end of the dataset (GetNext's wrap, :717-721; LoadChunk's, :305-311)."""
-        size = self.dataset_size_
-        while count > 0:
-            n = min(count, size - row)
-            reader.Get(out[at:at + n], row, row + n)
-            at, count, row = at + n, count - n, (row + n) % size
-        if seek:
-            reader.Seek(row)
-
-    def _lay_run(self, reader, out, at, row, count, seek=False):
-        """The same run of clip rows for a frames-once stream: the union of the clips' frame ranges goes behind what the buffer holds,
-        in dataset order and every frame once; clips ``at`` ... of the table get the buffer row of their first frame.  A piece — one
-        hyperslab read — ends where the next clip does not start one frame on: at a sequence boundary, at a skipped sequence, at the wrap
-        to row 0."""
-        frames, table, filled = out
-        mapping, T, size = reader.row_mapping_, reader.seq_length_, self.dataset_size_
-        while count > 0:
-            n = min(count, size - row)
-            m = mapping[row:row + n]
-            cuts = np.flatnonzero(np.diff(m) != 1) + 1
-            for a, b in zip([0, *cuts.tolist()], [*cuts.tolist(), n]):
-                lo, hi = int(m[a]), int(m[b - 1]) + T
-                reader.base_.Get(frames[filled[0]:filled[0] + hi - lo], lo, hi)
-                table[at + a:at + b] = filled[0] + (m[a:b] - lo)
-                filled[0] += hi - lo
-            at, count, row = at + n, count - n, (row + n) % size
-        if seek:
-            reader.Seek(row)
 
 
 class DataHandler:
@@ -526,19 +648,12 @@ class DataHandler:
     from disk (sequentially, or ``randomize_cpu`` in runs of ``random_access_chunk_size`` rows), copied to the GPU, and every
     ``GetBatch`` stages one batch from the resident chunk into the data layers.
 
-    Two chunk forms per stream.  **float** is the reference's: rows are cast to float on the host, the chunk is a (dims, cases)
-    ``Matrix``, ``Preprocess`` normalises all of it at load, ``randomize_gpu`` swaps its columns, and a batch is ``ExtractPatches`` /
-    ``CopyTranspose`` of a slice.  **bytes** — taken when the dataset is stored as unsigned 8-bit, its layer is an input layer and
-    ``normalize_local`` is off — keeps the chunk on the GPU exactly as read (a ``torch.uint8`` tensor, a quarter of the transfer and of
-    the memory); nothing touches it after the copy, ``randomize_gpu`` swaps entries of a column index instead, and a batch is ONE
-    ``StagePatchesU8``: cast, mean / std, crop, flip and transpose together, bit for bit what the float form leaves.
-    ``raw_chunks=False`` forces the float form everywhere.
-
-    A sequence stream (``is_sequence``, ``seq_length`` T) reads clips: its float form is the reference's, one materialised clip of T frames
-    per column.  Its bytes form (the same conditions, and not ``pick_first``) keeps every frame of a run of consecutive clip rows ONCE —
-    the union of the clips' frame ranges, in dataset order — beside a table of the buffer column of every clip's first frame;
-    ``randomize_gpu`` swaps entries of that table, and a batch is ONE ``StageClipsU8`` that gathers each clip's T consecutive columns.
-    The buffers are sized once, to the exact worst case over run starts (``FrameBufferSize``); only the used prefix is uploaded.
+    Every stream keeps its chunk in one of three forms, a class each (above); ``SetInputLayers`` picks.  **float** (``_FloatForm``) is the
+    reference's.  **bytes** (``_BytesForm``) is taken when the dataset is stored as unsigned 8-bit, its layer is an input layer and
+    ``normalize_local`` is off; a batch out of it is bit for bit what the float form leaves.  **frames-once** (``_FramesOnceForm``) is the
+    bytes form of a sequence stream (``is_sequence``, not ``pick_first``), whose float form is one materialised clip of ``seq_length``
+    frames per column; its buffers are sized once, to the exact worst case over run starts (``FrameBufferSize``).  ``raw_chunks=False``
+    forces the float form everywhere.
 
     The two host RNGs (random rows, column permutation) are numpy generators seeded from ``seed``; the device RNG calls are the
     library's, in the reference's order.  ``pipeline_loads``: one preload thread reads the next chunk into the idle one of two pinned
@@ -557,11 +672,9 @@ class DataHandler:
         self.pipeline_loads_, self.randomize_cpu_, self.randomize_gpu_ = config.pipeline_loads, config.randomize_cpu, config.randomize_gpu
         self.multiplicity_ = config.multiplicity
         self.row_rng_, self.perm_rng_ = (np.random.default_rng(s) for s in np.random.SeedSequence(seed).spawn(2))
-        self.layer_names_, self.streams_ = [], {}
+        self.streams_ = {}                   # layer name -> stream, in data_config order
         for dsc in config.data_config:
-            st = _Stream(dsc)
-            self.layer_names_.append(dsc.layer_name)
-            self.streams_[dsc.layer_name] = st
+            st = self.streams_[dsc.layer_name] = _Stream(dsc)
             st.reader_.SetMaxDataSetSize(config.max_dataset_size)
             size = st.reader_.GetDataSetSize()
             if self.dataset_size_ == -1:
@@ -575,29 +688,33 @@ class DataHandler:
             self.chunk_size_, self.fits_on_gpu_ = self.dataset_size_, True
         if self.batch_size_ > self.chunk_size_:
             raise SystemExit(f"batch_size {self.batch_size_} exceeds the chunk of {self.chunk_size_} cases.")
-        self.disk_ = _DiskSide({n: self.streams_[n].reader_ for n in self.layer_names_}, self.chunk_size_, self.dataset_size_,
-                               self.randomize_cpu_, self.random_access_chunk_size_, self.row_rng_)
+        self.disk_ = _DiskSide(self.chunk_size_, self.dataset_size_, self.randomize_cpu_, self.random_access_chunk_size_, self.row_rng_)
         self.perm_host_ = np.arange(self.chunk_size_, dtype=np.float32)     # SetupShuffler: shuffled in place, again and again
-        self.col_index_ = np.arange(self.chunk_size_, dtype=np.float32)     # bytes form: where each column of the chunk sits now
-        self.data_, self.raw_data_ = {}, {}  # layer name -> device chunk (Matrix (dims, chunk) / torch.uint8 tensor)
-        # frames-once streams: where every clip's first frame sits in raw_data_ (host copy, device copy) and how many frames that holds
-        self.first_frame_, self.first_frame_dev_, self.frames_used_ = {}, {}, {}
+        self.col_index_ = None               # where each column of a byte chunk sits now: ONE index for all the plain byte streams
         self.input_layers_set_ = self.allocated_ = False
         self.copy_done_ = [None, None]       # per host buffer: the event behind the last copy that read it
         self.last_copied_, self.pending_ = -1, 0
         self.Seek(0)
 
-    # ---- which streams keep their bytes ----
+    # ---- which form every stream keeps its chunk in: the one place that decides ----
     def SetInputLayers(self, names):
+        self.col_index_ = None
         for name, st in self.streams_.items():
-            st.raw_ = (self.raw_chunks_ and name in names and st.reader_.GetStoredType() == np.uint8 and not st.normalize_local_
-                       and not (st.is_sequence_ and st.config_.pick_first))
-            st.frames_once_ = st.raw_ and st.is_sequence_
-            if st.frames_once_ and self.FrameBufferSize(name) > 1 << 24:
+            raw = (self.raw_chunks_ and name in names and st.reader_.GetStoredType() == np.uint8 and not st.normalize_local_
+                   and not (st.is_sequence_ and st.config_.pick_first))
+            frames = self.FrameBufferSize(name) if raw and st.is_sequence_ else 0
+            if frames > 1 << 24:
                 raise SystemExit(f"Data stream for layer {name}: a byte chunk of more than 2^24 frames cannot be indexed; set chunk_size.")
-            if st.raw_ and self.chunk_size_ > 1 << 24:
+            if raw and self.chunk_size_ > 1 << 24:
                 raise SystemExit(f"Data stream for layer {name}: a byte chunk of more than 2^24 cases cannot be indexed; set chunk_size.")
-        self.disk_.frames_once_ = {name for name, st in self.streams_.items() if st.frames_once_}
+            if frames:
+                st.form_ = _FramesOnceForm(st, self.chunk_size_, self.dataset_size_, frames)
+            elif raw:
+                self.col_index_ = self.col_index_ or _Index(self.chunk_size_)
+                st.form_ = _BytesForm(st, self.chunk_size_, self.dataset_size_, self.col_index_)
+            else:
+                st.form_ = _FloatForm(st, self.chunk_size_, self.dataset_size_)
+        self.disk_.halves_ = {name: st.form_.disk_ for name, st in self.streams_.items()}
         self.input_layers_set_ = True
 
     def FrameBufferSize(self, name):
@@ -615,20 +732,14 @@ class DataHandler:
         """One host buffer per stream, two with ``pipeline_loads``; ``pinned=False`` gives plain numpy arrays (no GPU needed)."""
         if not self.input_layers_set_:
             self.SetInputLayers(())
+        count = 2 if self.pipeline_loads_ else 1
+        buffers = {name: half.HostBuffers(count) for name, half in self.disk_.halves_.items()}
         host, self.host_tensors_ = [], []
-        sizes = {name: self.FrameBufferSize(name) for name, st in self.streams_.items() if st.frames_once_}    # once: here
-        self.disk_.first_frame_, self.disk_.frames_used_ = [], []
-        for _ in range(2 if self.pipeline_loads_ else 1):
+        for _ in range(count):
             arrays, tensors = {}, {}
-            self.disk_.first_frame_.append({name: np.zeros(self.chunk_size_, np.float32) for name in sizes})
-            self.disk_.frames_used_.append({name: 0 for name in sizes})
-            for name, st in self.streams_.items():
-                shape, dtype = (self.chunk_size_, st.GetDims()), (np.uint8 if st.raw_ else np.float32)
-                if st.frames_once_:
-                    shape = (sizes[name], st.frame_size_)
+            for name, (shape, dtype) in buffers.items():
                 if pinned:
-                    import torch
-                    tensors[name] = torch.empty(shape, dtype=torch.uint8 if st.raw_ else torch.float32, pin_memory=True)
+                    tensors[name] = torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), pin_memory=True)
                     arrays[name] = tensors[name].numpy()
                 else:
                     arrays[name] = np.zeros(shape, dtype)
@@ -637,20 +748,9 @@ class DataHandler:
         self.disk_.host_ = host
 
     def AllocateMemory(self):
-        import torch
         self.AllocateHostMemory(pinned=True)
         for name, st in self.streams_.items():
-            if st.frames_once_:              # (the host buffer's size: the worst case, allocated once)
-                self.raw_data_[name] = torch.empty(self.host_[0][name].size, dtype=torch.uint8, device=Matrix()._dev())
-                self.first_frame_[name] = np.zeros(self.chunk_size_, np.float32)
-                self.first_frame_dev_[name] = Matrix()
-                self.first_frame_dev_[name].AllocateGPUMemory(1, self.chunk_size_)
-                self.frames_used_[name] = 0
-            elif st.raw_:
-                self.raw_data_[name] = torch.empty(self.chunk_size_ * st.GetDims(), dtype=torch.uint8, device=Matrix()._dev())
-            else:
-                self.data_[name] = Matrix()
-                self.data_[name].AllocateGPUMemory(st.GetDims(), self.chunk_size_, "databuffer")
+            st.form_.AllocateMemory(st)
             if st.normalize_:
                 st.LoadMeans()
             elif st.add_pca_noise_:
@@ -658,10 +758,9 @@ class DataHandler:
         if self.randomize_gpu_:
             self.rand_perm_indices_ = Matrix()
             self.rand_perm_indices_.AllocateGPUMemory(1, self.chunk_size_)
-        if any(st.raw_ and not st.frames_once_ for st in self.streams_.values()):
-            self.col_index_dev_ = Matrix()
-            self.col_index_dev_.AllocateGPUMemory(1, self.chunk_size_)
-            self.col_index_dev_.FromNumpy(self.col_index_)
+        if self.col_index_ is not None:
+            self.col_index_.Allocate()
+            self.col_index_.Reset()
         self.copy_done_ = [torch.cuda.Event() for _ in self.host_]
         self.allocated_ = True
 
@@ -707,19 +806,14 @@ class DataHandler:
     def _shuffle_columns(self, data_layers):
         self.ShuffleIndices()
         for l in data_layers:
-            if l.GetName() in self.data_:
-                self.data_[l.GetName()].ShuffleColumns(self.rand_perm_indices_)
-        if self.raw_data_:
-            # shuffleColumns swaps columns idx[2j] and idx[2j+1] for every pair; a permutation's pairs are disjoint.  The byte chunk
-            # stays where it is: the same swaps go to the index of where each column sits
-            pairs = self.perm_host_[:2 * (self.chunk_size_ // 2)].astype(np.int64)
-            a, b = pairs[0::2], pairs[1::2]
-            if len(self.raw_data_) > len(self.first_frame_):
-                self.col_index_[a], self.col_index_[b] = self.col_index_[b].copy(), self.col_index_[a].copy()
-                self.col_index_dev_.FromNumpy(self.col_index_)
-            for name, table in self.first_frame_.items():        # a frames-once stream: the same swaps on its first-frame table
-                table[a], table[b] = table[b].copy(), table[a].copy()
-                self.first_frame_dev_[name].FromNumpy(table)
+            if l.GetName() in self.streams_:
+                self.streams_[l.GetName()].form_.ShuffleColumns(self.rand_perm_indices_)
+        pairs = self.perm_host_[:2 * (self.chunk_size_ // 2)].astype(np.int64)     # the pairs shuffleColumns swaps (_Form)
+        a, b = pairs[0::2], pairs[1::2]
+        if self.col_index_ is not None:
+            self.col_index_.Swap(a, b)
+        for st in self.streams_.values():
+            st.form_.SwapEntries(a, b)
 
     # ---- DataHandler::GetBatch (:146-200) ----
     def GetBatch(self, data_layers):
@@ -743,9 +837,9 @@ class DataHandler:
             self.start_, end = 0, self.batch_size_
         streams = [(l, self.streams_[l.GetName()]) for l in data_layers if l.GetName() in self.streams_]
         for l, st in streams:            # all the noise first: a layer may need another's (:170-181)
-            st.SampleNoise(self.batch_size_, self.multiplicity_counter_)
+            st.jitter_.Sample(self.batch_size_, self.multiplicity_counter_)
         for l, st in streams:
-            st.AddNoise(self, self.start_, end, l.GetState() if l.IsInput() else l.GetData())
+            st.AddNoise(self.start_, end, l.GetState() if l.IsInput() else l.GetData())
         self.multiplicity_counter_ += 1
         if self.multiplicity_counter_ == self.multiplicity_:
             self.multiplicity_counter_ = 0
@@ -753,7 +847,6 @@ class DataHandler:
 
     # ---- DataHandler::PipelinedDiskAccess / StartPreload / WaitForPreload (:202-237) ----
     def PipelinedDiskAccess(self):
-        import torch
         if self.pipeline_loads_:
             self.WaitForPreload()
             buf = self.pending_
@@ -762,22 +855,11 @@ class DataHandler:
             self.copy_done_[0].synchronize()     # the last copy out of this buffer
             self.DiskAccess(0)
         for name, st in self.streams_.items():   # on the stream the step runs on
-            src = self.host_tensors_[buf][name].view(-1)
-            if st.frames_once_:                  # the used prefix alone, and the table that goes with it
-                used = self.frames_used_[name] = self.disk_.frames_used_[buf][name]
-                self.raw_data_[name][:used * st.frame_size_].copy_(src[:used * st.frame_size_], non_blocking=True)
-                self.first_frame_[name][:] = self.disk_.first_frame_[buf][name]
-                self.first_frame_dev_[name].FromNumpy(self.first_frame_[name])
-            elif st.raw_:
-                self.raw_data_[name].copy_(src, non_blocking=True)
-            else:
-                self.data_[name]._t[:src.numel()].copy_(src, non_blocking=True)
-                st.Preprocess(self.data_[name])
+            st.form_.Upload(st, self.host_tensors_[buf][name].view(-1), buf)
         self.copy_done_[buf].record(torch.cuda.current_stream())
         self.last_copied_ = buf
-        if len(self.raw_data_) > len(self.first_frame_):
-            self.col_index_[:] = np.arange(self.chunk_size_, dtype=np.float32)
-            self.col_index_dev_.FromNumpy(self.col_index_)
+        if self.col_index_ is not None:          # the byte chunks are as read again
+            self.col_index_.Reset()
         if self.pipeline_loads_:
             self.StartPreload()
 
@@ -811,3 +893,8 @@ class DataHandler:
     @property
     def host_(self):
         return self.disk_.host_
+
+    @property
+    def raw_data_(self):
+        """layer name -> the chunk on the device, of the streams whose chunk stays a byte tensor (a read-only view)."""
+        return {name: st.form_.data_ for name, st in self.streams_.items() if isinstance(st.form_.data_, torch.Tensor)}

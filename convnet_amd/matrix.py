@@ -36,6 +36,21 @@ def _conv_call(fn, mats, conv_desc, *scalars, unshaped=None):
        *(ctypes.byref(m.shape_) for i, m in enumerate(mats) if i != unshaped), conv_desc, *scalars)
 
 
+def _opt(m):
+    """An optional matrix argument: NULL for None."""
+    return m.GetMat() if m is not None else None
+
+
+def _byte_columns(entry, what, holder, unit, t, dims, count):
+    """The guard of the byte-staging entries: ``t`` must be ``dims * count`` uint8 values on the device, ``count`` columns that a float
+    can number.  Returns its address."""
+    if t.dtype != torch.uint8 or not t.is_cuda or t.numel() != int(dims) * int(count):
+        raise MatrixError(f"Error: {entry} : the {what} must be {int(dims) * int(count)} uint8 values on the device")
+    if count > 1 << 24:
+        raise MatrixError(f"Error: {entry} : a {holder} of more than 2^24 {unit} cannot be indexed by a float")
+    return ctypes.c_void_p(t.data_ptr())
+
+
 class Matrix:
     # reference statics: temp_/ones_ pools, rnd_ state (src/matrix.cc:10-16)
     _temp = None
@@ -327,13 +342,9 @@ class Matrix:
         """One batch out of a byte chunk (include/convnet_hip.h: stage_patches_u8).  ``chunk``: a torch.uint8 device tensor of
         dims * num_cases bytes, one case per column; ``mean`` / ``std``: (dims, 1) or both None; the offsets and the flip bits: all three
         None for no jitter.  (y, x) sizes in, like ExtractPatches."""
-        if chunk.dtype != torch.uint8 or not chunk.is_cuda or chunk.numel() != int(dims) * int(num_cases):
-            raise MatrixError(f"Error: stage_patches_u8 : the chunk must be {int(dims) * int(num_cases)} uint8 values on the device")
-        if num_cases > 1 << 24:
-            raise MatrixError("Error: stage_patches_u8 : a chunk of more than 2^24 cases cannot be indexed by a float")
-        opt = lambda m: m.GetMat() if m is not None else None   # noqa: E731
-        _chk(lib.stage_patches_u8(ctypes.c_void_p(chunk.data_ptr()), int(dims), int(num_cases), case_index.GetMat(), opt(mean), opt(std),
-                                  dest.GetMat(), opt(width_offset), opt(height_offset), opt(flip_bit), int(image_size_x), int(image_size_y),
+        ptr = _byte_columns("stage_patches_u8", "chunk", "chunk", "cases", chunk, dims, num_cases)
+        _chk(lib.stage_patches_u8(ptr, int(dims), int(num_cases), case_index.GetMat(), _opt(mean), _opt(std), dest.GetMat(),
+                                  _opt(width_offset), _opt(height_offset), _opt(flip_bit), int(image_size_x), int(image_size_y),
                                   int(patch_size_x), int(patch_size_y)), "Error staging patches")
 
     @staticmethod
@@ -342,13 +353,9 @@ class Matrix:
         """One batch of clips out of a byte buffer that holds every frame once (include/convnet_hip.h: stage_clips_u8).  ``frames``: a
         torch.uint8 device tensor of frame_dims * num_frames bytes, one frame per column; ``first_frame``: the column of every case's
         first frame; ``mean`` / ``std``: (frame_dims, 1) or both None.  (y, x) sizes in, like ExtractPatches."""
-        if frames.dtype != torch.uint8 or not frames.is_cuda or frames.numel() != int(frame_dims) * int(num_frames):
-            raise MatrixError(f"Error: stage_clips_u8 : the frames must be {int(frame_dims) * int(num_frames)} uint8 values on the device")
-        if num_frames > 1 << 24:
-            raise MatrixError("Error: stage_clips_u8 : a buffer of more than 2^24 frames cannot be indexed by a float")
-        opt = lambda m: m.GetMat() if m is not None else None   # noqa: E731
-        _chk(lib.stage_clips_u8(ctypes.c_void_p(frames.data_ptr()), int(frame_dims), int(num_frames), first_frame.GetMat(), int(clip_frames),
-                                opt(mean), opt(std), dest.GetMat(), opt(width_offset), opt(height_offset), opt(flip_bit), int(image_size_x),
+        ptr = _byte_columns("stage_clips_u8", "frames", "buffer", "frames", frames, frame_dims, num_frames)
+        _chk(lib.stage_clips_u8(ptr, int(frame_dims), int(num_frames), first_frame.GetMat(), int(clip_frames), _opt(mean), _opt(std),
+                                dest.GetMat(), _opt(width_offset), _opt(height_offset), _opt(flip_bit), int(image_size_x),
                                 int(image_size_y), int(patch_size_x), int(patch_size_y)), "Error staging clips")
 
     def Mult(self, val):
