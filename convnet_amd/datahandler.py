@@ -771,6 +771,9 @@ class DataHandler:
     def GetDataSetSize(self):
         return self.dataset_size_
 
+    def GetMultiplicity(self):
+        return self.multiplicity_
+
     def GetDims(self, layer_name):
         if layer_name not in self.streams_:
             raise SystemExit(f"Layer name {layer_name} not found.")

@@ -221,6 +221,8 @@ class EdgeWithWeight(Edge):
         self.initialization_ = c.initialization
         self.init_wt_ = c.init_wt
         self.init_bias_ = c.init_bias
+        self.pretrained_model_ = c.pretrained_model
+        self.pretrained_edge_name_ = c.pretrained_edge_name      # empty: the edge's own "<source>:<dest>" (src/edge_with_weight.cc:17-19)
         self.has_no_bias_ = c.has_no_bias
         self.num_grads_received_ = 0
         self.num_shares_ = 1
@@ -357,10 +359,27 @@ class EdgeWithWeight(Edge):
             self.weights_.Mult(init_wt)
         elif init == "CONSTANT":
             self.weights_.Set(self.init_wt_)
+        elif init == "PRETRAINED":
+            self._load_pretrained()
         else:
             raise SystemExit(f"Unknown / out-of-scope weight initialization type {init}.")
-        if not self.has_no_bias_:
+        if init != "PRETRAINED" and not self.has_no_bias_:       # a loaded bias stays (:140-142)
             self.bias_.Set(self.init_bias_)
+
+    def _load_pretrained(self):
+        """``initialization: PRETRAINED`` (src/edge_with_weight.cc:132-135): weight and bias come from ``pretrained_model``, stored there
+        under ``pretrained_edge_name`` or this edge's own "<source>:<dest>" (the name ``SaveParameters`` stores it under)."""
+        from . import hdf5io
+        edge_name = self.pretrained_edge_name_ or self._checkpoint_prefix()
+        try:
+            file = hdf5io.File(self.pretrained_model_)
+        except OSError as e:
+            raise SystemExit(f"Edge {self.GetName()}: initialization PRETRAINED: {e}")
+        with file:
+            for what in ("weight",) if self.has_no_bias_ else ("weight", "bias"):
+                if not file.Has(f"{edge_name}:{what}"):
+                    raise SystemExit(f"Edge {self.GetName()}: initialization PRETRAINED: no dataset {edge_name}:{what} in {self.pretrained_model_}")
+            self.LoadParameters(file, edge_name)
 
     def GetRMSWeight(self):
         temp = Matrix()

@@ -9,7 +9,9 @@ versa: names are ``<source>:<dest>:weight``, ``…:bias``, ``…:weight_gradient
 (convnet.cc:672-673,744-749)."""
 import ctypes
 import ctypes.util
+import functools
 import os
+import threading
 
 import numpy as np
 
@@ -90,9 +92,24 @@ _ROW_TYPES = {np.dtype(np.int8): "INT8", np.dtype(np.int32): "INT32", np.dtype(n
               np.dtype(np.uint32): "UINT32", np.dtype(np.uint64): "UINT64", np.dtype(np.float32): "FLOAT", np.dtype(np.float64): "DOUBLE"}
 
 
+# libhdf5 may be built without thread safety, so no two threads may be inside it at once.  Every method below that enters the library
+# holds this one lock for its whole duration — the main thread (checkpoints, means), the data handler's preload thread (RowReader.Get)
+# and the data writer's thread (RowWriter.WriteRows) all come through here.  Re-entrant: a method may call another.
+LOCK = threading.RLock()
+
+
+def _serialized(method):
+    @functools.wraps(method)
+    def locked(*args, **kw):
+        with LOCK:
+            return method(*args, **kw)
+    return locked
+
+
 class File:
     """``with File(path, "w") as f`` — H5Fcreate(H5F_ACC_TRUNC) / H5Fopen(H5F_ACC_RDONLY) (convnet.cc:668,741)."""
 
+    @_serialized
     def __init__(self, path, mode="r"):
         L = _lib()
         self.path = path
@@ -107,12 +124,14 @@ class File:
     def __exit__(self, *exc):
         self.close()
 
+    @_serialized
     def close(self):
         if self.id >= 0:
             _lib().H5Fclose(self.id)
             self.id = -1
 
     # ---- util.cc:128-138 ----
+    @_serialized
     def WriteHDF5CPU(self, mat, rows, cols, name):
         """``mat``: the floats in memory order; stored as a (rows, cols) row-major dataset."""
         L = _lib()
@@ -131,10 +150,12 @@ class File:
         if rc < 0:
             raise OSError(f"H5Dwrite failed for {name}")
 
+    @_serialized
     def Has(self, name):
         return _lib().H5Lexists(self.id, name.encode(), H5P_DEFAULT) > 0
 
     # ---- util.cc:163-175: (rows, cols) of the column-major matrix = (dims[1] or 1, dims[0]) ----
+    @_serialized
     def ReadHDF5Shape(self, name):
         L = _lib()
         ds = L.H5Dopen2(self.id, name.encode(), H5P_DEFAULT)
@@ -151,6 +172,7 @@ class File:
         return rows, cols
 
     # ---- util.cc:188-206 ----
+    @_serialized
     def ReadHDF5CPU(self, size, name):
         L = _lib()
         rows, cols = self.ReadHDF5Shape(name)
@@ -165,6 +187,7 @@ class File:
         return out
 
     # ---- util.cc:177-186 / :188-196 ----
+    @_serialized
     def WriteHDF5IntAttr(self, name, val):
         L = _lib()
         aid = L.H5Screate(H5S_SCALAR)
@@ -177,6 +200,7 @@ class File:
         if rc < 0:
             raise OSError(f"cannot write attribute {name}")
 
+    @_serialized
     def ReadHDF5IntAttr(self, name, default):
         """Missing attribute: the reference prints a note and leaves the caller's value untouched."""
         L = _lib()
@@ -189,6 +213,7 @@ class File:
         return v.value
 
     # ---- datasets of rows: what a DataHandler stream reads (src/datahandler.cc:604-721) ----
+    @_serialized
     def WriteDataset(self, name, array):
         """A 1-D or 2-D numpy array of one of the eight row types, stored in its own type."""
         L = _lib()
@@ -208,12 +233,66 @@ class File:
     def RowReader(self, name):
         return RowReader(self, name)
 
+    def CreateRows(self, name, num_rows, num_dims):
+        """A (num_rows, num_dims) float dataset created empty, to be filled by ``RowWriter.WriteRows`` (DataWriter::SetNumDims,
+        src/datawriter.cc:29-45)."""
+        return RowWriter(self, name, num_rows, num_dims)
+
+
+class RowWriter:
+    """The write side of a dataset of rows: DataWriter::SetNumDims creates it, DataWriter::WriteHDF5 (src/datawriter.cc:48-94) fills it
+    by hyperslabs of consecutive rows."""
+
+    @_serialized
+    def __init__(self, file, name, num_rows, num_dims):
+        L = _lib()
+        self.file_, self.name_, self.num_rows_, self.num_dims_ = file, name, int(num_rows), int(num_dims)
+        dims = (ctypes.c_uint64 * 2)(self.num_rows_, self.num_dims_)
+        space = L.H5Screate_simple(2, dims, None)
+        self.dataset_ = L.H5Dcreate2(file.id, name.encode(), _T["float"], space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT) if space >= 0 else -1
+        if space >= 0:
+            L.H5Sclose(space)
+        if self.dataset_ < 0:
+            raise OSError(f"Could not create dataset {name} of {num_rows} x {num_dims} in {file.path}")
+
+    @_serialized
+    def WriteRows(self, data, row_start):
+        """``data``: a C-contiguous float32 array of whole rows, written to rows ``row_start`` ... of the dataset."""
+        L = _lib()
+        if not isinstance(data, np.ndarray) or data.dtype != np.float32 or not data.flags.c_contiguous or data.size % self.num_dims_:
+            raise ValueError(f"dataset {self.name_}: WriteRows needs a contiguous float32 array of whole rows of {self.num_dims_}")
+        num_rows = data.size // self.num_dims_
+        if self.dataset_ < 0:
+            raise OSError(f"dataset {self.name_} of {self.file_.path} is closed")
+        if row_start < 0 or num_rows <= 0 or row_start + num_rows > self.num_rows_:
+            raise IndexError(f"dataset {self.name_}: rows {row_start}:{row_start + num_rows} are not inside its {self.num_rows_} rows")
+        start = (ctypes.c_uint64 * 2)(row_start, 0)
+        count = (ctypes.c_uint64 * 2)(num_rows, self.num_dims_)
+        fspace = L.H5Dget_space(self.dataset_)
+        mspace = L.H5Screate_simple(2, count, None)
+        rc = L.H5Sselect_hyperslab(fspace, H5S_SELECT_SET, start, None, count, None) if fspace >= 0 and mspace >= 0 else -1
+        if rc >= 0:
+            rc = L.H5Dwrite(self.dataset_, _T["float"], mspace, fspace, H5P_DEFAULT, data.ctypes.data_as(ctypes.c_void_p))
+        if mspace >= 0:
+            L.H5Sclose(mspace)
+        if fspace >= 0:
+            L.H5Sclose(fspace)
+        if rc < 0:
+            raise OSError(f"Could not write rows {row_start}:{row_start + num_rows} of {self.name_} to {self.file_.path}")
+
+    @_serialized
+    def close(self):
+        if self.dataset_ >= 0:
+            _lib().H5Dclose(self.dataset_)
+            self.dataset_ = -1
+
 
 class RowReader:
     """HDF5DataIterator<T> (src/datahandler.cc:604-721): the rows of one dataset, read as hyperslabs through a 1 GiB chunk cache.
     ``Get`` fills a caller-owned buffer: a float32 one takes the reference's ``static_cast<float>`` of every element, whatever the
     stored type; a uint8 one takes the bytes as they are and is accepted for an unsigned 8-bit dataset only."""
 
+    @_serialized
     def __init__(self, file, name):
         L = _lib()
         self.file_, self.name_ = file, name
@@ -243,6 +322,7 @@ class RowReader:
         self.row_ = 0
         self.num_reads_ = 0     # H5Dread calls so far
 
+    @_serialized
     def close(self):
         if self.dataset_ >= 0:
             _lib().H5Dclose(self.dataset_)
@@ -272,6 +352,7 @@ class RowReader:
     def Tell(self):
         return self.row_
 
+    @_serialized
     def Get(self, out, row_start, row_end):
         L = _lib()
         num_rows = row_end - row_start

@@ -348,6 +348,13 @@ class Matrix:
                                   int(patch_size_x), int(patch_size_y)), "Error staging patches")
 
     @staticmethod
+    def FeatureRows(state, sum_, pass_, passes, cases, carry, consumed, group, rows):
+        """A layer state as rows of a feature file, averaged over ``passes`` calls and over groups of ``group`` consecutive cases
+        (include/convnet_hip.h: feature_rows).  ``sum_``: None when passes == 1; ``carry``: None when group == 1."""
+        _chk(lib.feature_rows(state.GetMat(), _opt(sum_), int(pass_), int(passes), int(cases), _opt(carry), int(consumed), int(group),
+                              rows.GetMat()), "Error writing feature rows")
+
+    @staticmethod
     def StageClipsU8(frames, frame_dims, num_frames, first_frame, clip_frames, mean, std, dest, width_offset, height_offset, flip_bit,
                      image_size_y, image_size_x, patch_size_y, patch_size_x):
         """One batch of clips out of a byte buffer that holds every frame once (include/convnet_hip.h: stage_clips_u8).  ``frames``: a

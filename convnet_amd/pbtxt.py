@@ -129,6 +129,14 @@ class DatasetConfig(Msg):  # proto:371-382
     }
 
 
+class FeatureStreamConfig(Msg):  # proto:384-388
+    FIELDS = {"layer": "", "average_batches": 1, "average_online": 1}
+
+
+class FeatureExtractorConfig(Msg):  # proto:389-393
+    FIELDS = {"output_file": "", "feature": (list, FeatureStreamConfig), "input": DatasetConfig}
+
+
 class Model(Msg):  # proto:239-272
     FIELDS = {
         "name": "", "layer": (list, Layer), "edge": (list, Edge), "seed": 0, "max_iter": -1, "display_after": -1,

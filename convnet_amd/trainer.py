@@ -189,10 +189,14 @@ class TrainLoopMixin:
         return history
 
     # ---- feature extraction: src/convnet.cc:606-657 + src/datawriter.cc (one (cases, dims) float dataset per layer) -----
-    def ExtractFeatures(self, dataset, layer_names, output_file):
-        """Fprop(false) over the whole dataset (the last, partial batch contributes its first ``left_overs`` cases) and
+    def ExtractFeatures(self, dataset, layer_names=None, output_file=None, *, pipelined=True, on_allocated=None):
+        """Two forms.  ``ExtractFeatures(config)`` — a ``pbtxt.FeatureExtractorConfig`` or the path of one — is the reference's
+        (src/convnet.cc:600-657): ``ExtractFeaturesFromConfig`` below.  ``ExtractFeatures(dataset, layer_names, output_file)``:
+        Fprop(false) over the whole dataset (the last, partial batch contributes its first ``left_overs`` cases) and
         write each named layer's state, one case per row, to ``output_file``.  The net must have been allocated for this
         dataset's batch size (``AllocateMemory(True)`` is enough)."""
+        if layer_names is None and output_file is None:
+            return self.ExtractFeaturesFromConfig(dataset, pipelined=pipelined, on_allocated=on_allocated)
         from . import hdf5io
         layers = [self.GetLayerByName(n) for n in layer_names]
         dataset_size, batch_size = dataset.GetDataSetSize(), dataset.GetBatchSize()
@@ -214,3 +218,44 @@ class TrainLoopMixin:
             for name, parts in rows.items():
                 a = np.concatenate(parts, axis=0)
                 f.WriteHDF5CPU(a, a.shape[0], a.shape[1], name)
+
+    def ExtractFeaturesFromConfig(self, config, pipelined=True, on_allocated=None):
+        """ConvNet::ExtractFeatures(FeatureExtractorConfig) (src/convnet.cc:606-657): the handler of ``config.input``, the net allocated
+        for its batch size (``AllocateMemory(True)``: weights as the model's ``initialization`` says — PRETRAINED loads them; then
+        ``on_allocated()``, where a caller loads a checkpoint), and ``num_batches x multiplicity`` rounds of GetBatch / Fprop(false) /
+        ``DataWriter.Write``: the views of a batch follow each other, and the last, partial batch passes ``left_overs`` as numcases.
+        Returns {layer name: rows written}."""
+        from . import pbtxt
+        from .datawriter import DataWriter
+        if isinstance(config, str):
+            config = pbtxt.read(config, pbtxt.FeatureExtractorConfig)
+        by_name = {l.GetName(): l for l in self.layers_}
+        dataset = self._build_data_handler(config.input)
+        try:
+            dataset_size, batch_size, multiplicity = dataset.GetDataSetSize(), dataset.GetBatchSize(), dataset.GetMultiplicity()
+            num_batches, left_overs = divmod(dataset_size, batch_size)
+            self.SetBatchsize(batch_size)
+            self.AllocateMemory(True)
+            if on_allocated is not None:
+                on_allocated()
+            self.log(f"Extracting features for dataset of size {dataset_size} # batches {num_batches} # left overs {left_overs}")
+            if left_overs > 0:
+                num_batches += 1
+            self.log(f"Writing to {config.output_file}")
+            writer = DataWriter(config, self.layers_, dataset_size, multiplicity, batch_size, pipelined=pipelined)
+            try:
+                layers = [by_name[f.layer] for f in config.feature]
+                for k in range(num_batches):
+                    numcases = left_overs if (left_overs > 0 and k == num_batches - 1) else batch_size
+                    for _ in range(multiplicity):
+                        for l in self.layers_:
+                            l.ResetAddOrOverwrite()
+                        self.GetBatch(dataset)
+                        self.Fprop(False)
+                        writer.Write(layers, numcases)
+            finally:
+                writer.close()
+            dataset.Sync()
+            return {name: writer.GetRows(name) for name in writer.streams_}
+        finally:
+            dataset.close()

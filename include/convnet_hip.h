@@ -209,6 +209,22 @@ int stage_clips_u8(void* frames, int frame_dims, int num_frames, cudamat* first_
 /* stage_clips_u8's grid, for A/B timing (tools/clips_bench.py); the results are the same.  0: the library's choice; 1: a block stages
  * all clip_frames planes of its (colour, patch row, tile) with mean / std in registers; 2: one plane per block. */
 void convnet_hip_set_stage_clips_grid(int mode);
+/* ---- feature extraction: src/datawriter.cc (DataWriter::Write / WriteHDF5SeqBuf; csrc/feature_rows.hip) -------------------------
+ * A layer state becomes rows of a feature file's dataset, averaged on the way.  state is (N, D), case fastest; sum has its shape (NULL
+ * is fine when passes == 1); rows is (D, R): R rows of D contiguous floats; carry is (D, 1) (NULL is fine when group == 1).
+ *   pass < passes - 1: sum = state (pass == 0; as 0 + state) or sum + state.  Nothing else is touched.
+ *   last pass        : v = state (passes == 1) or (sum + state) / passes — bit for bit add_elementwise into a zeroed buffer `passes`
+ *                      times, then divide_by_scalar (buf.Add(m) ...; buf.Divide(average_batches)).  sum is not written.
+ *     group == 1     : rows[:, n] = v[n, :] for n < cases: an exact transpose; later columns of rows and carry are untouched.
+ *     group  > 1     : the `cases` columns of v are consumed in order into groups of `group` consecutive cases; the open group already
+ *                      holds `consumed` (< group) cases in carry.  Every completed group writes the next column of rows (from 0): the
+ *                      carry, then fma(member, 1 / group, .) member by member in case order — (consumed + cases) / group columns.  On
+ *                      return carry holds the partial of the still-open group, or zeros.  No atomics: the same bits from call to call.
+ * ERROR_GENERIC for a NULL or out-of-range argument, ERROR_TRANSPOSED for a transposed operand, ERROR_INCOMPATIBLE_DIMENSIONS when sum
+ * differs from state, rows has not D rows or fewer columns than are written, carry is not (D, 1) or cases > N.  get_slice views are
+ * fine: 16-byte loads along N need N % 4 == 0 and 16-byte bases of state and sum, 16-byte stores along D need D % 4 == 0 and a 16-byte
+ * base of rows; otherwise that side runs scalar.  One launch per call, no workspace. */
+int feature_rows(cudamat* state, cudamat* sum, int pass, int passes, int cases, cudamat* carry, int consumed, int group, cudamat* rows);
 /* in place: for every column pair (2j, 2j+1) swap columns idx[2j] and idx[2j+1] (cudamat.cu:2655, kShuffleColumns) */
 int shuffleColumns(cudamat* source, cudamat* rand_perm_indices);
 int add_col_vec(cudamat* mat, cudamat* vec, cudamat* target);                 /* cudamat.cuh:165 */
