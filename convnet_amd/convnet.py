@@ -44,6 +44,13 @@ class LayerPlan(NamedTuple):
     logistic_deriv: bool               # LogisticDerivScaled instead of ApplyDerivativeofDropout + ApplyDerivativeOfActivation
 
 
+def _zero_storage(m):
+    """Zeroes the device storage a matrix owns; one that owns none (a stand-in that only records allocations) has nothing to zero."""
+    t = getattr(m, "_t", None)
+    if t is not None:
+        t.zero_()
+
+
 class ConvNet(TrainLoopMixin):
     def __init__(self, model, fused=False, process_id=0, num_processes=1, verbose=False, exchange=None, overlap_update=None,
                  overlap_wgrad=None):
@@ -334,14 +341,19 @@ class ConvNet(TrainLoopMixin):
             usage[e] = mem
             total += ((mem + 127) // 128) * 128   # 128-float aligned slices (src/convnet.cc:279)
         self.parameters_.AllocateGPUMemory(1, total, "parameters")
+        # The padding between the 128-float slices is written by nobody: what the allocator left there (NaN bit patterns, after byte or
+        # integer tensors) would stay in the flat buffers for good.  Their storage is handed out zeroed (the owner's job: no library call).
+        _zero_storage(self.parameters_)
         if not fprop_only:
             self.grad_parameters_.AllocateGPUMemory(1, total, "grad parameters")
             self.grad_parameters_.Set(0.0)
             self.history_.AllocateGPUMemory(1, total, "optimizer history")   # flat, same layout
+            _zero_storage(self.history_)
             second = any(o is not None and o.NeedsSecondHistory() for e in self.edges_ if isinstance(e, EdgeWithWeight)
                          for o in (e.weight_optimizer_, e.bias_optimizer_))
             if second:
                 self.second_history_.AllocateGPUMemory(1, total, "optimizer second-moment history")
+                _zero_storage(self.second_history_)
         offset = 0
         for e in self.edges_:
             mem = usage[e]

@@ -849,7 +849,8 @@ class DataHandler:
             self.start_ = end
 
     # ---- DataHandler::PipelinedDiskAccess / StartPreload / WaitForPreload (:202-237) ----
-    def PipelinedDiskAccess(self):
+    def PipelinedDiskAccess(self, preload_next=True):
+        """``preload_next=False``: the chunk that is uploaded now is the last one a single pass needs (compute_mean)."""
         if self.pipeline_loads_:
             self.WaitForPreload()
             buf = self.pending_
@@ -863,7 +864,7 @@ class DataHandler:
         self.last_copied_ = buf
         if self.col_index_ is not None:          # the byte chunks are as read again
             self.col_index_.Reset()
-        if self.pipeline_loads_:
+        if self.pipeline_loads_ and preload_next:
             self.StartPreload()
 
     def StartPreload(self):

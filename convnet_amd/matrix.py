@@ -348,6 +348,18 @@ class Matrix:
                                   int(patch_size_x), int(patch_size_y)), "Error staging patches")
 
     @staticmethod
+    def ChunkMomentsU8(chunk, dims, num_cases, first_case, cases, num_colors, acc):
+        """The integer moments of columns ``first_case`` ... of a byte chunk, ADDED into ``acc`` (include/convnet_hip.h: chunk_moments_u8).
+        ``chunk``: a torch.uint8 device tensor of dims * num_cases bytes, one case per column; ``acc``: a torch.int64 device tensor of
+        2 * dims + num_colors ** 2 sums (read as unsigned)."""
+        if chunk.dtype != torch.uint8 or not chunk.is_cuda or chunk.numel() != int(dims) * int(num_cases):
+            raise MatrixError(f"Error: chunk_moments_u8 : the chunk must be {int(dims) * int(num_cases)} uint8 values on the device")
+        if acc.dtype != torch.int64 or not acc.is_cuda or not acc.is_contiguous() or acc.numel() != 2 * int(dims) + int(num_colors) ** 2:
+            raise MatrixError(f"Error: chunk_moments_u8 : acc must be {2 * int(dims) + int(num_colors) ** 2} int64 values on the device")
+        _chk(lib.chunk_moments_u8(ctypes.c_void_p(chunk.data_ptr()), int(dims), int(num_cases), int(first_case), int(cases), int(num_colors),
+                                  ctypes.c_void_p(acc.data_ptr())), "Error computing chunk moments")
+
+    @staticmethod
     def FeatureRows(state, sum_, pass_, passes, cases, carry, consumed, group, rows):
         """A layer state as rows of a feature file, averaged over ``passes`` calls and over groups of ``group`` consecutive cases
         (include/convnet_hip.h: feature_rows).  ``sum_``: None when passes == 1; ``carry``: None when group == 1."""

@@ -195,6 +195,18 @@ int extract_patches(cudamat* images, cudamat* patches, cudamat* width_offset, cu
 int stage_patches_u8(void* chunk, int dims, int num_cases, cudamat* case_index, cudamat* mean, cudamat* std, cudamat* patches,
                      cudamat* width_offset, cudamat* height_offset, cudamat* flip, int img_width, int img_height, int patch_width,
                      int patch_height);
+/* Dataset statistics from the same byte chunk (apps/compute_mean.cc:70-80; csrc/dataset_moments.hip): the raw integer moments of
+ * columns first_case ... first_case + cases - 1, ADDED into acc, which is 2 * dims + num_colors^2 unsigned 64-bit integers on the
+ * device (8-byte aligned) and is never cleared here:
+ *   acc[d]                    += sum over the cases of x[d]
+ *   acc[dims + d]             += sum over the cases of x[d]^2
+ *   acc[2 * dims + c * C + c'] += sum over the cases and the pixels p of x[c, p] * x[c', p]      (C = num_colors, the full symmetric block)
+ * One read of the range, no workspace.  Every sum is an integer, so the result does not depend on how the cases are split over blocks:
+ * bit for bit numpy's int64 sums, from call to call.  The range's start need not be aligned.  num_colors 1 ... 4 are served.
+ * ERROR_GENERIC for a NULL chunk or acc (or an acc that is not 8-byte aligned); ERROR_INCOMPATIBLE_DIMENSIONS for dims or num_colors
+ * < 1, dims % num_colors != 0, cases < 0 or a range outside [0, num_cases); then ERROR_UNSUPPORTED for num_colors > 4.  cases == 0
+ * succeeds and touches nothing. */
+int chunk_moments_u8(void* chunk, int dims, int num_cases, int first_case, int cases, int num_colors, void* acc);
 /* Clips out of a byte buffer that holds every frame ONCE: `frames` is frame_dims x num_frames unsigned bytes on the device, one frame per
  * column, [colour][row][col].  first_frame holds one float per batch case: the column of the clip's first frame (exact up to 2^24
  * columns; more is ERROR_UNSUPPORTED).  patches is (cases, clip_frames * colours * ph * pw): plane t * colours + c of case n is colour c
