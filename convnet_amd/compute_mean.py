@@ -167,6 +167,9 @@ def ComputeMean(data_config, layer_name, num_colors, *, raw_chunks=True):
     dh = DataHandler(cfg, raw_chunks=bool(raw_chunks) and C <= 4)
     try:
         st = dh.streams_[layer_name]
+        if st.is_images_:
+            raise SystemExit(f"Data stream for layer {layer_name}: compute_mean does not take an IMAGE_RAW stream: the statistics pass "
+                             "reads stored rows, and a list of image files stores none.")
         dims, size, chunk, batch = st.GetDims(), dh.GetDataSetSize(), dh.chunk_size_, dh.GetBatchSize()
         if dims % C:
             raise SystemExit(f"Data stream for layer {layer_name}: rows of {dims} values are not {C} colours of whole images.")

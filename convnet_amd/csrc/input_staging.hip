@@ -214,6 +214,119 @@ __global__ void __launch_bounds__(256) stage_clips_u8_kernel(const unsigned char
   }
 }
 
+// The same staging out of DECODED IMAGE FILES kept at their original sizes (interleaved RGB rows, images back to back in one byte
+// buffer), with the 8-bit bilinear resize of the crop's pixels on the way: the resized image is never stored.  Every image has one row
+// of the image table {byte offset, w, h, new_w, new_h, first tap} (64-bit) and new_w column taps followed by new_h row taps
+// {source index, coefficient 0, coefficient 1} (32-bit), built on the host; every case names its image, where the crop starts in the
+// resized image and whether the crop is mirrored.  The tile, the LDS transpose and the wave stores are stage_patches_u8_kernel's, for the
+// three colours of a patch pixel at once: one thread resamples one pixel in all three colours, because its four source pixels are 12
+// interleaved bytes of two source rows (so the colours share their cache lines), and the tile is three planes of 64 x 65 floats.  A block
+// owns one patch row, so what a case contributes to every pixel of it — the image's base and width, the two source rows and the row
+// coefficients, where its column taps start, the first crop column and the walking direction — is worked out once by the first wave and
+// kept in LDS; the pixel loop loads one column tap (12 B, consecutive lanes consecutive taps unless mirrored) and 12 bytes.
+// Integer arithmetic only up to the cast (include/convnet_hip.h has the formula).  Everything read from a table is clamped: the image
+// number, the tap numbers, the source row and column, the byte address.
+struct ImageCase {
+  size_t row0, row1;      // byte offsets of the two source rows in the buffer
+  int width;              // source width, >= 1
+  int b0, b1;             // the row coefficients
+  int new_w;              // resized width, >= 1
+  long col_taps;          // number of the image's first column tap
+  int left, mirror;       // where the crop starts in the resized row, and whether it walks backwards
+  int col_first, col_step, crop_row;   // the jitter: crop column of patch column 0, direction, crop row
+};
+
+__device__ inline int resample_row(const unsigned char* __restrict__ bytes, size_t last, size_t at0, size_t at1, int a0, int a1) {
+  const int p0 = bytes[at0 < last ? at0 : last], p1 = bytes[at1 < last ? at1 : last];
+  return (((2048 * ((p0 * a0 + p1 * a1) >> 4)) >> 16) + 2) >> 2;
+}
+
+template <bool NORM, bool JITTER>
+__global__ void __launch_bounds__(256) stage_images_u8_kernel(const unsigned char* __restrict__ bytes, size_t num_bytes,
+                                                              const long long* __restrict__ image_table, int num_images,
+                                                              const int* __restrict__ taps, long num_taps,
+                                                              const int* __restrict__ case_table, const float* __restrict__ mean,
+                                                              const float* __restrict__ sdev, float* __restrict__ patches,
+                                                              const float* __restrict__ wo, const float* __restrict__ ho,
+                                                              const float* __restrict__ flip, int N, int W, int H, int pw, int ph) {
+  __shared__ float tile[3][64][65];
+  __shared__ ImageCase cases[64];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;   // 64 x 4
+  const int c0 = blockIdx.x * 64;
+  const int row = blockIdx.y;
+  const int n0 = blockIdx.z * 64;
+  const size_t last = num_bytes - 1;
+  if (ty == 0 && n0 + tx < N) {
+    const int n = n0 + tx;
+    int sr = row, first = 0, step = 1;
+    if (JITTER) {
+      sr += min(max((int)ho[n], -H - ph), H + ph);
+      first = min(max((int)wo[n], -W - pw), W + pw);
+      if (flip[n] > 0.5f) {
+        first = W - first - 1;
+        step = -1;
+      }
+    }
+    sr = min(max(sr, 0), H - 1);
+    const int* c = case_table + 4 * (size_t)n;
+    const long long* im = image_table + 6 * (size_t)min(max(c[0], 0), num_images - 1);
+    const auto dim = [](long long v) { return (int)min(max(v, 1LL), 1LL << 30); };
+    const int w = dim(im[1]), h = dim(im[2]), new_w = dim(im[3]), new_h = dim(im[4]);
+    const long first_tap = (long)min(max(im[5], 0LL), (long long)num_taps - 1);
+    const int rr = min(max(min(max(c[2], -(1 << 30)), 1 << 30) + sr, 0), new_h - 1);   // the row of the resized image
+    const int* t = taps + 3 * min(first_tap + new_w + rr, num_taps - 1);
+    const int sy = min(max(t[0], 0), h - 1);
+    const size_t base = (size_t)min(max(im[0], 0LL), (long long)last);
+    ImageCase& k = cases[tx];
+    k.row0 = base + (size_t)sy * w * 3;
+    k.row1 = base + (size_t)min(sy + 1, h - 1) * w * 3;
+    k.width = w;
+    k.b0 = t[1];
+    k.b1 = t[2];
+    k.new_w = new_w;
+    k.col_taps = first_tap;
+    k.left = min(max(c[1], -(1 << 30)), 1 << 30);
+    k.mirror = c[3] != 0;
+    k.col_first = first;
+    k.col_step = step;
+    k.crop_row = sr;
+  }
+  __syncthreads();
+#pragma unroll 2
+  for (int j = ty; j < 64; j += 4) {
+    const int n = n0 + j, dc = c0 + tx;
+    if (n < N && dc < pw) {
+      const ImageCase& k = cases[j];
+      const int sc = min(max(k.col_first + k.col_step * dc, 0), W - 1);                  // the column of the crop
+      const int rc = min(max(k.left + (k.mirror ? W - 1 - sc : sc), 0), k.new_w - 1);      // the column of the resized image
+      const int* t = taps + 3 * min(k.col_taps + rc, num_taps - 1);
+      const int sx = min(max(t[0], 0), k.width - 1), a0 = t[1], a1 = t[2];
+      const size_t x0 = (size_t)sx * 3, x1 = (size_t)min(sx + 1, k.width - 1) * 3;
+      const int src = sc + W * k.crop_row;
+#pragma unroll
+      for (int color = 0; color < 3; ++color) {
+        const int h0 = resample_row(bytes, last, k.row0 + x0 + color, k.row0 + x1 + color, a0, a1);
+        const int h1 = resample_row(bytes, last, k.row1 + x0 + color, k.row1 + x1 + color, a0, a1);
+        float v = (float)((((k.b0 * ((2048 * h0) >> 4)) >> 16) + ((k.b1 * ((2048 * h1) >> 4)) >> 16) + 2) >> 2);
+        if (NORM) {
+          const int s = src + W * H * color;
+          v = (v - mean[s]) / sdev[s];
+        }
+        tile[color][j][tx] = v;
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int color = 0; color < 3; ++color) {
+#pragma unroll 4
+    for (int j = ty; j < 64; j += 4) {
+      const int dc = c0 + j, n = n0 + tx;
+      if (n < N && dc < pw) patches[(size_t)n + (size_t)N * (dc + (size_t)pw * (row + (size_t)ph * color))] = tile[color][tx][j];
+    }
+  }
+}
+
 // 0: the launcher's choice; 1: every block stages all the clip's planes of its tile; 2: one plane per block (tools/clips_bench.py's A/B)
 int g_stage_clips_grid = 0;
 
@@ -302,13 +415,14 @@ struct StageU8 {
   long grid_y;
 };
 
-// Error code or 0, in the precedence tests/test_stage_patches_gpu.py and tests/test_stage_clips_gpu.py list.
-int check_stage_u8(StageU8& s) {
-  if (!s.data || !s.index || !s.patches) return ERROR_NOT_ON_DEVICE;
+// Error code or 0, in the precedence tests/test_stage_patches_gpu.py and tests/test_stage_clips_gpu.py list.  ``indexed`` false: the
+// entry has no per-case column index (stage_images_u8, whose tables are plain device pointers), and s.index is not looked at.
+int check_stage_u8(StageU8& s, bool indexed = true) {
+  if (!s.data || (indexed && !s.index) || !s.patches) return ERROR_NOT_ON_DEVICE;
   s.norm = s.mean || s.sdev;
   s.jitter = s.width_offset || s.height_offset || s.flip;
   if ((s.norm && !(s.mean && s.sdev)) || (s.jitter && !(s.width_offset && s.height_offset && s.flip))) return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if (!s.index->on_device || !s.patches->on_device || (s.norm && (!s.mean->on_device || !s.sdev->on_device)) ||
+  if ((indexed && !s.index->on_device) || !s.patches->on_device || (s.norm && (!s.mean->on_device || !s.sdev->on_device)) ||
       (s.jitter && (!s.width_offset->on_device || !s.height_offset->on_device || !s.flip->on_device)))
     return ERROR_NOT_ON_DEVICE;
   if (s.patches->is_trans) return ERROR_TRANSPOSED;
@@ -319,7 +433,7 @@ int check_stage_u8(StageU8& s) {
   if (s.dims % ((long)s.img_width * s.img_height) != 0) return ERROR_INCOMPATIBLE_DIMENSIONS;
   s.num_colors = s.dims / (s.img_width * s.img_height);
   const size_t num_images = s.num_images = s.patches->size[0];
-  if ((long)s.patches->size[1] != (long)s.planes * s.num_colors * s.patch_width * s.patch_height || numel(s.index) != num_images)
+  if ((long)s.patches->size[1] != (long)s.planes * s.num_colors * s.patch_width * s.patch_height || (indexed && numel(s.index) != num_images))
     return ERROR_INCOMPATIBLE_DIMENSIONS;
   if (s.norm && (s.mean->size[0] != s.dims || s.mean->size[1] != 1 || s.sdev->size[0] != s.dims || s.sdev->size[1] != 1))
     return ERROR_INCOMPATIBLE_DIMENSIONS;
@@ -394,6 +508,27 @@ int stage_clips_u8(void* frames, int frame_dims, int num_frames, cudamat* first_
   if (const int e = check_stage_u8(s); e || s.num_images == 0) return e;
   KernelTimer timer("stage_clips_u8_kernel", "input_staging", 0.0, (5.0 + (s.norm ? 8.0 / frames_per_block : 0.0)) * numel(patches));
   return launch_stage_u8(s, STAGE_U8_KERNEL(stage_clips_u8_kernel, s), clip_frames, frames_per_block);
+}
+
+int stage_images_u8(void* bytes, size_t num_bytes, void* image_table, int num_images, void* taps, int num_taps, void* case_table,
+                    cudamat* mean, cudamat* sdev, cudamat* patches, cudamat* width_offset, cudamat* height_offset, cudamat* flip,
+                    int img_width, int img_height, int patch_width, int patch_height) {
+  if (!bytes || !image_table || !taps || !case_table || !patches) return ERROR_GENERIC;
+  // the rest is stage_patches_u8's checker on a crop of three colours
+  if (img_width <= 0 || img_height <= 0 || (long)img_width * img_height > (1 << 28) || num_bytes == 0 || num_taps <= 0)
+    return ERROR_INCOMPATIBLE_DIMENSIONS;
+  StageU8 s{bytes, 3 * img_width * img_height, num_images, nullptr, mean, sdev, patches, width_offset, height_offset, flip, img_width,
+            img_height, patch_width, patch_height, 1, 1};
+  if (const int e = check_stage_u8(s, false); e || s.num_images == 0) return e;
+  if (s.patch_height > 65535) return ERROR_UNSUPPORTED;
+  KernelTimer timer("stage_images_u8_kernel", "input_staging", 0.0, 16.0 * numel(patches));
+  const dim3 grid(divup(s.patch_width, 64), s.patch_height, divup(s.num_images, 64));
+  hipLaunchKernelGGL(STAGE_U8_KERNEL(stage_images_u8_kernel, s), grid, dim3(256), 0, stream(), static_cast<const unsigned char*>(bytes),
+                     num_bytes, static_cast<const long long*>(image_table), num_images, static_cast<const int*>(taps), (long)num_taps,
+                     static_cast<const int*>(case_table), s.norm ? mean->data_device : nullptr, s.norm ? sdev->data_device : nullptr,
+                     patches->data_device, s.jitter ? width_offset->data_device : nullptr, s.jitter ? height_offset->data_device : nullptr,
+                     s.jitter ? flip->data_device : nullptr, s.num_images, img_width, img_height, patch_width, patch_height);
+  return hipGetLastError() == hipSuccess ? 0 : CUDA_ERROR;
 }
 
 int shuffleColumns(cudamat* source, cudamat* rand_perm_indices) {

@@ -1,8 +1,8 @@
 """Data handlers.  The contract is the reference's (src/datahandler.cc:145-198): ``GetBatch(data_layers)``
 leaves a batch in every input layer's ``state_`` (N, X*Y*C CHWN) and every output layer's ``data_``.
-``DataHandler`` (below) is the reference's own, for HDF5 streams: built from a DatasetConfig, it reads
-chunks from disk and stages batches on the GPU — rows of a dataset, or clips of consecutive frames of one (``is_sequence``); JPEG / video /
-text streams are refused.
+``DataHandler`` (below) is the reference's own, for HDF5 streams and lists of image files: built from a DatasetConfig, it reads
+chunks from disk and stages batches on the GPU — rows of a dataset, clips of consecutive frames of one (``is_sequence``), or crops of
+image files resized on the way (``data_type: IMAGE_RAW``, image_iterators.py); video / text / sliding-window streams are refused.
 ``ChunkDataHandler`` stages from numpy arrays the caller holds; ``SyntheticDataHandler`` makes noise: inputs are N(0,1) (the real pipeline feeds mean/std-normalised
 pixels, :496-507), labels uniform ints stored as float (N,1); ``num_batches`` distinct batches are
 pre-generated on the device and cycled, so no host work sits inside a timed step."""
@@ -196,9 +196,48 @@ class ChunkDataHandler:
 
 
 _REFUSED_TYPES = {
-    "DUMMY": "random numbers in place of data", "IMAGE_RAW": "JPEG files decoded and resized on the host",
+    "DUMMY": "random numbers in place of data",
     "SLIDING_WINDOW": "sliding windows over raw images", "TXT": "text files of numbers", "BOUNDING_BOX": "bounding-box files",
     "CROPS": "crops of raw images", "VIDEO_RAW": "video files decoded on the host"}
+
+
+def _raw_image_size(dsc):
+    """(y, x) of the size every image of an IMAGE_RAW stream is resized to cover (src/datahandler.cc:725-726)."""
+    return (dsc.raw_image_size_y if dsc.has_raw_image_size_y() else dsc.raw_image_size,
+            dsc.raw_image_size_x if dsc.has_raw_image_size_x() else dsc.raw_image_size)
+
+
+def _check_image_stream(dsc):
+    """What an IMAGE_RAW stream cannot be here, each with a message of its own naming the layer and the field."""
+    head = f"Data stream for layer {dsc.layer_name}: "
+    raw_y, raw_x = _raw_image_size(dsc)
+    if raw_y <= 0 or raw_x <= 0:
+        raise SystemExit(head + "data_type IMAGE_RAW without a raw_image_size (the size every image is resized to cover) is not supported; "
+                         "set raw_image_size, or raw_image_size_y and raw_image_size_x.")
+    if dsc.is_sequence:
+        raise SystemExit(head + "is_sequence is not supported on an IMAGE_RAW stream: clips are read from HDF5 frame datasets.")
+    if dsc.jitter_raw_image:
+        raise SystemExit(head + "jitter_raw_image is not supported: the random crop, scale and rotation of the decoded image need "
+                         "warpAffine and the stream of std::default_random_engine.")
+    if dsc.random_rotate_max_angle != 0:
+        raise SystemExit(head + f"random_rotate_max_angle {dsc.random_rotate_max_angle:g} is not supported: rotating the decoded image needs "
+                         "warpAffine.")
+    if dsc.min_scale != 0:
+        raise SystemExit(head + f"min_scale {dsc.min_scale:g} is not supported: it scales the random crop of jitter_raw_image, which is not built.")
+    if dsc.bbox_file:
+        raise SystemExit(head + f"bbox_file ({dsc.bbox_file}) is not supported: crops around bounding boxes are not built.")
+    if dsc.num_colors != 3:
+        raise SystemExit(head + f"num_colors {dsc.num_colors} is not supported on an IMAGE_RAW stream: a decoded image has 3 colour planes "
+                         "(the reference writes three into a buffer of num_colors).")
+    size_y = dsc.image_size_y if dsc.has_image_size_y() else dsc.image_size
+    size_x = dsc.image_size_x if dsc.has_image_size_x() else dsc.image_size
+    if size_y <= 0 or size_x <= 0:
+        raise SystemExit(head + "an IMAGE_RAW stream needs an image_size (the crop taken from every resized image).")
+    if size_y > raw_y or size_x > raw_x:
+        raise SystemExit(head + f"image_size {size_y} x {size_x} exceeds raw_image_size {raw_y} x {raw_x}: the crop must fit the resized image.")
+    if dsc.avg10_full_image and dsc.parallel_disk_access:
+        raise SystemExit(head + "avg10_full_image together with parallel_disk_access is not supported: the reference indexes its file list "
+                         "with a row of the ten times larger dataset there.")
 
 
 class _SequenceReader:
@@ -293,24 +332,36 @@ class _Stream:
     def __init__(self, dsc):
         from . import hdf5io
         name = dsc.layer_name
+        self.is_images_ = dsc.data_type == "IMAGE_RAW"
+        if self.is_images_:
+            _check_image_stream(dsc)
         if dsc.is_sequence and dsc.seq_length < 1:
             raise SystemExit(f"Data stream for layer {name}: is_sequence needs a seq_length of at least 1, not {dsc.seq_length}.")
         if dsc.is_sequence and dsc.pca_noise_stddev > 0:
             raise SystemExit(f"Data stream for layer {name}: pca_noise_stddev is not supported on a sequence stream: the colour noise "
                              "has 3 columns, a clip 3 x seq_length planes.")
-        if dsc.data_type != "HDF5":
+        if not self.is_images_ and dsc.data_type != "HDF5":
             what = _REFUSED_TYPES.get(dsc.data_type)
             if what is None:
                 raise SystemExit(f"Data stream for layer {name}: Unknown data type {dsc.data_type}")
-            raise SystemExit(f"Data stream for layer {name}: data_type {dsc.data_type} ({what}) is not supported; only HDF5 streams are.")
+            raise SystemExit(f"Data stream for layer {name}: data_type {dsc.data_type} ({what}) is not supported; only HDF5 and IMAGE_RAW streams are.")
         if dsc.noise_layer_name:
             raise SystemExit(f"Data stream for layer {name}: noise_layer_name ({dsc.noise_layer_name}) is not supported: "
                              "no stream takes its jitter from another.")
         if dsc.gpu_id != 0:
             raise SystemExit(f"Data stream for layer {name}: gpu_id {dsc.gpu_id} is not supported: one process drives one GPU, gpu_id 0.")
         self.config_, self.layer_name_ = dsc, name
-        self.file_ = hdf5io.File(dsc.file_pattern)
-        self.reader_ = self.file_.RowReader(dsc.dataset_name)
+        size_y = dsc.image_size_y if dsc.has_image_size_y() else dsc.image_size
+        size_x = dsc.image_size_x if dsc.has_image_size_x() else dsc.image_size
+        if self.is_images_:          # ImageDataIterator (:723-754): a list of image files, resized to cover the raw size and cropped
+            from . import image_iterators
+            self.file_ = None
+            self.raw_size_y_, self.raw_size_x_ = _raw_image_size(dsc)
+            self.reader_ = image_iterators.ImageReader(image_iterators.ReadFileList(dsc.file_pattern), size_y, size_x, self.raw_size_y_,
+                                                       self.raw_size_x_, dsc.avg10_full_image, dsc.parallel_disk_access, name)
+        else:
+            self.file_ = hdf5io.File(dsc.file_pattern)
+            self.reader_ = self.file_.RowReader(dsc.dataset_name)
         self.frame_size_, self.frames_ = self.reader_.GetDims(), 1      # a row is frames_ frames of frame_size_ values
         self.is_sequence_ = dsc.is_sequence
         self.form_ = None            # how the chunk is kept: DataHandler.SetInputLayers decides
@@ -321,8 +372,6 @@ class _Stream:
                 self.close()
                 raise
             self.frames_ = 1 if dsc.pick_first else dsc.seq_length
-        size_y = dsc.image_size_y if dsc.has_image_size_y() else dsc.image_size
-        size_x = dsc.image_size_x if dsc.has_image_size_x() else dsc.image_size
         self.jitter_ = j = _Jitter(size_y, size_x, dsc.gpu_image_size_y if dsc.has_gpu_image_size_y() else size_y,
                                    dsc.gpu_image_size_x if dsc.has_gpu_image_size_x() else size_x, dsc.can_translate, dsc.can_flip)
         self.width_offset_, self.height_offset_, self.flip_bit_ = j.width_offset_, j.height_offset_, j.flip_bit_
@@ -418,12 +467,14 @@ class _Stream:
 
     def close(self):
         self.reader_.close()
-        self.file_.close()
+        if self.file_ is not None:
+            self.file_.close()
 
 
 # ---- the chunk forms ----------------------------------------------------------------------------------------------------------------------
-# A form has two halves.  The DISK half (_RowsDisk / _FramesDisk) is all the preload thread sees of it: the row reader, the shape of a host
-# buffer and how a run of rows gets into one — libhdf5 and numpy only.  The DEVICE half (_FloatForm / _BytesForm / _FramesOnceForm, which
+# A form has two halves.  The DISK half (_RowsDisk / _FramesDisk / _ImagesDisk) is all the preload thread sees of it: the row reader, the
+# shape of a host buffer and how a run of rows gets into one — libhdf5, the image decoders and numpy only.  The DEVICE half (_FloatForm /
+# _BytesForm / _FramesOnceForm / _ImagesOnceForm, which
 # holds its disk half as ``disk_``) owns the chunk on the GPU: storage, upload, what randomize_gpu does to it, staging a batch.
 
 class _RowsDisk:
@@ -478,6 +529,72 @@ class _FramesDisk(_RowsDisk):
             table[at + a:at + b] = filled + (m[a:b] - lo)
             filled += hi - lo
         self.frames_used_[buf] = filled
+
+
+class _ImagesDisk(_RowsDisk):
+    """Rows of an IMAGE_RAW stream with every file of the chunk decoded ONCE: a buffer is plain bytes — the images at their original
+    sizes as interleaved R, G, B rows, back to back.  Beside each buffer (numpy, [buffer]): ``image_table_`` {byte offset, w, h, new_w,
+    new_h, first tap} per image, ``taps_`` {source index, coefficient 0, coefficient 1} per column and row of every resized image, built
+    here in the preload thread, ``case_table_`` {image, left, top, mirrored} per case, and how much of each the chunk filled.  The ten
+    positions of a file share its pixels and its taps.  Buffers start at chunk_size * raw_y * raw_x * 3 * 2 bytes (twice a chunk of images
+    that are exactly the raw size); a chunk that needs more gets new ones of twice its need, through ``grow_`` (the handler's, which
+    knows whether host buffers are pinned)."""
+
+    def __init__(self, reader, chunk_size, dataset_size):
+        super().__init__(reader, chunk_size, dataset_size, np.uint8)
+        self.start_bytes_ = chunk_size * reader.raw_y_ * reader.raw_x_ * 3 * 2
+        self.image_table_ = self.taps_ = self.case_table_ = self.bytes_used_ = self.images_used_ = self.taps_used_ = None
+        self.image_of_file_ = None           # [buffer]: file -> image number, of the chunk in the buffer
+        self.bytes_ = None                   # [buffer]: the host array as it is now (DataHandler.AllocateHostMemory)
+        self.grow_ = None                    # (buffer number, bytes) -> the new host array, in place of the old one everywhere
+
+    def HostBuffers(self, count):
+        r = self.reader_
+        self.image_table_ = [np.zeros((self.chunk_size_, 6), np.int64) for _ in range(count)]
+        self.taps_ = [np.zeros((self.chunk_size_ * (r.raw_y_ + r.raw_x_) * 2, 3), np.int32) for _ in range(count)]
+        self.case_table_ = [np.zeros((self.chunk_size_, 4), np.int32) for _ in range(count)]
+        self.bytes_used_, self.images_used_, self.taps_used_ = [0] * count, [0] * count, [0] * count
+        self.image_of_file_ = [{} for _ in range(count)]
+        return (self.start_bytes_,), self.dtype_
+
+    def LoadPiece(self, out, buf, at, row, n):
+        """The files of rows ``row:row + n`` that the buffer does not hold yet go behind what it holds (a run at chunk position 0 begins
+        it); cases ``at`` ... of the case table get their image and the crop of their position in the RESIZED image."""
+        from . import image_iterators as ii
+        r = self.reader_
+        if at == 0:
+            self.bytes_used_[buf] = self.images_used_[buf] = self.taps_used_[buf] = 0
+            self.image_of_file_[buf] = {}
+        known = self.image_of_file_[buf]
+        files = [f for f in r.FilesOf(row, row + n) if f not in known]
+        images = r.Decode(files)
+        sizes = [(im.shape[1], im.shape[0], *ii.ResizedSize(im.shape[1], im.shape[0], r.raw_y_, r.raw_x_)) for im in images]
+        used, taps_used = self.bytes_used_[buf], self.taps_used_[buf]
+        need = used + sum(im.size for im in images)
+        out = self.bytes_[buf]               # (not the caller's: an earlier piece of this chunk may have replaced it)
+        if need > out.size:
+            grown = self.grow_(buf, 2 * need)
+            grown[:used] = out[:used]
+            out = grown
+        taps_need = taps_used + sum(new_w + new_h for _, _, new_w, new_h in sizes)
+        if taps_need > len(self.taps_[buf]):
+            grown = np.zeros((2 * taps_need, 3), np.int32)
+            grown[:taps_used] = self.taps_[buf][:taps_used]
+            self.taps_[buf] = grown
+        for f, im, (w, h, new_w, new_h) in zip(files, images, sizes):
+            k = known[f] = self.images_used_[buf]
+            out[used:used + im.size] = im.reshape(-1)
+            cols, rows = ii.ImageTaps(w, h, new_w, new_h)
+            self.taps_[buf][taps_used:taps_used + new_w] = cols
+            self.taps_[buf][taps_used + new_w:taps_used + new_w + new_h] = rows
+            self.image_table_[buf][k] = (used, w, h, new_w, new_h, taps_used)
+            used, taps_used, self.images_used_[buf] = used + im.size, taps_used + new_w + new_h, k + 1
+        self.bytes_used_[buf], self.taps_used_[buf] = used, taps_used
+        for i in range(n):
+            f, position = r.FileAndPosition(row + i)
+            _, _, _, new_w, new_h, _ = self.image_table_[buf][known[f]]
+            left, top, mirrored = ii.Coordinates(int(new_w), int(new_h), position, r.size_y_, r.size_x_)
+            self.case_table_[buf][at + i] = (known[f], left, top, mirrored)
 
 
 class _Index:
@@ -592,6 +709,43 @@ class _FramesOnceForm(_Form):
                             *st.jitter_.StagingArgs(fs))
 
 
+class _ImagesOnceForm(_Form):
+    """An IMAGE_RAW stream's byte form: the decoded files of a chunk at their original sizes, each once, and the three tables of
+    ``_ImagesDisk`` beside them on the device.  Only the used prefixes are uploaded; the device buffer starts at the host buffer's size and
+    is reallocated at twice the need when a chunk needs more; randomize_gpu swaps rows of the case table; a batch is ONE ``StageImagesU8``
+    that resamples, crops, mirrors, normalises and transposes the pixels of the patch — the resized image is never made."""
+    raw_, frames_once_ = True, False
+
+    def __init__(self, st, chunk_size, dataset_size):
+        self.disk_ = _ImagesDisk(st.reader_, chunk_size, dataset_size)
+        self.data_ = self.image_table_ = self.taps_ = self.case_table_ = self.case_host_ = None
+        self.bytes_used_ = 0
+
+    def AllocateMemory(self, st):
+        self.data_ = torch.empty(self.disk_.start_bytes_, dtype=torch.uint8, device=Matrix()._dev())
+
+    def Upload(self, st, src, buf):
+        d, dev = self.disk_, self.data_.device
+        used = self.bytes_used_ = d.bytes_used_[buf]
+        if used > self.data_.numel():
+            self.data_ = torch.empty(2 * used, dtype=torch.uint8, device=dev)
+        self.data_[:used].copy_(src[:used], non_blocking=True)
+        self.image_table_ = torch.from_numpy(d.image_table_[buf][:d.images_used_[buf]]).to(dev)
+        self.taps_ = torch.from_numpy(d.taps_[buf][:d.taps_used_[buf]]).to(dev)
+        self.case_host_ = d.case_table_[buf].copy()
+        self.case_table_ = torch.from_numpy(self.case_host_).to(dev)
+
+    def SwapEntries(self, a, b):
+        self.case_host_[a], self.case_host_[b] = self.case_host_[b].copy(), self.case_host_[a].copy()
+        self.case_table_ = torch.from_numpy(self.case_host_).to(self.data_.device)
+
+    def Stage(self, st, start, end, output):
+        j = st.jitter_
+        offsets = (j.width_offset_, j.height_offset_, j.flip_bit_) if j.Jitters() else (None, None, None)
+        Matrix.StageImagesU8(self.data_[:self.bytes_used_], self.image_table_, self.taps_, self.case_table_[start:end], *st.Normalizers(),
+                             output, *offsets, j.image_size_y_, j.image_size_x_, j.gpu_image_size_y_, j.gpu_image_size_x_)
+
+
 class _DiskSide:
     """DataHandler::DiskAccess / LoadChunk (src/datahandler.cc:239-314): everything the preload thread touches — the disk halves of the
     streams' forms (their row readers), the host buffers and the random-row list.  libhdf5 and numpy only: no GPU call, no ``Matrix``, and
@@ -643,6 +797,20 @@ class _DiskSide:
         return self.host_[buf]
 
 
+def _grower(host, tensors, half, name, pinned):
+    """What replaces a host buffer of an images-once stream by a larger one (``_ImagesDisk.grow_``): in the handler's lists and in the
+    disk half's.  It holds no handler.  With pinned buffers this is the one GPU runtime call the preload thread can make."""
+    def grow(buf, size):
+        if pinned:
+            tensors[buf][name] = torch.empty((size,), dtype=torch.uint8, pin_memory=True)
+            host[buf][name] = tensors[buf][name].numpy()
+        else:
+            host[buf][name] = np.zeros((size,), np.uint8)
+        half.bytes_[buf] = host[buf][name]
+        return host[buf][name]
+    return grow
+
+
 class DataHandler:
     """DataHandler for HDF5 streams, built from a ``pbtxt.DatasetConfig`` (src/datahandler.cc:8-336): chunks of the dataset are read
     from disk (sequentially, or ``randomize_cpu`` in runs of ``random_access_chunk_size`` rows), copied to the GPU, and every
@@ -652,7 +820,9 @@ class DataHandler:
     reference's.  **bytes** (``_BytesForm``) is taken when the dataset is stored as unsigned 8-bit, its layer is an input layer and
     ``normalize_local`` is off; a batch out of it is bit for bit what the float form leaves.  **frames-once** (``_FramesOnceForm``) is the
     bytes form of a sequence stream (``is_sequence``, not ``pick_first``), whose float form is one materialised clip of ``seq_length``
-    frames per column; its buffers are sized once, to the exact worst case over run starts (``FrameBufferSize``).  ``raw_chunks=False``
+    frames per column; its buffers are sized once, to the exact worst case over run starts (``FrameBufferSize``).  **images-once**
+    (``_ImagesOnceForm``) is the bytes form of an IMAGE_RAW stream, whose float form is resized and cropped on the host: the decoded files
+    of a chunk at their original sizes, each once, and tables; its buffers grow when a chunk needs more.  ``raw_chunks=False``
     forces the float form everywhere.
 
     The two host RNGs (random rows, column permutation) are numpy generators seeded from ``seed``; the device RNG calls are the
@@ -675,6 +845,9 @@ class DataHandler:
         self.streams_ = {}                   # layer name -> stream, in data_config order
         for dsc in config.data_config:
             st = self.streams_[dsc.layer_name] = _Stream(dsc)
+            if st.is_images_ and dsc.avg10_full_image and config.randomize_cpu:
+                raise SystemExit(f"Data stream for layer {dsc.layer_name}: avg10_full_image together with randomize_cpu is not supported: "
+                                 "the reference indexes its file list with a row of the ten times larger dataset there.")
             st.reader_.SetMaxDataSetSize(config.max_dataset_size)
             size = st.reader_.GetDataSetSize()
             if self.dataset_size_ == -1:
@@ -709,6 +882,8 @@ class DataHandler:
                 raise SystemExit(f"Data stream for layer {name}: a byte chunk of more than 2^24 cases cannot be indexed; set chunk_size.")
             if frames:
                 st.form_ = _FramesOnceForm(st, self.chunk_size_, self.dataset_size_, frames)
+            elif raw and st.is_images_:
+                st.form_ = _ImagesOnceForm(st, self.chunk_size_, self.dataset_size_)
             elif raw:
                 self.col_index_ = self.col_index_ or _Index(self.chunk_size_)
                 st.form_ = _BytesForm(st, self.chunk_size_, self.dataset_size_, self.col_index_)
@@ -746,6 +921,10 @@ class DataHandler:
             host.append(arrays)
             self.host_tensors_.append(tensors)
         self.disk_.host_ = host
+        for name, half in self.disk_.halves_.items():
+            if isinstance(half, _ImagesDisk):
+                half.bytes_ = [arrays[name] for arrays in host]
+                half.grow_ = _grower(host, self.host_tensors_, half, name, pinned)
 
     def AllocateMemory(self):
         self.AllocateHostMemory(pinned=True)

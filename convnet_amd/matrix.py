@@ -377,6 +377,26 @@ class Matrix:
                                 dest.GetMat(), _opt(width_offset), _opt(height_offset), _opt(flip_bit), int(image_size_x),
                                 int(image_size_y), int(patch_size_x), int(patch_size_y)), "Error staging clips")
 
+    @staticmethod
+    def StageImagesU8(bytes_, image_table, taps, case_table, mean, std, dest, width_offset, height_offset, flip_bit, image_size_y,
+                      image_size_x, patch_size_y, patch_size_x):
+        """One batch out of decoded images kept at their original sizes, resized on the way (include/convnet_hip.h: stage_images_u8).
+        Device tensors, all contiguous: ``bytes_`` torch.uint8; ``image_table`` torch.int64 (images, 6); ``taps`` torch.int32 (taps, 3);
+        ``case_table`` torch.int32 (cases of ``dest``, 4).  ``mean`` / ``std``: (3 * image_size_y * image_size_x, 1) or both None.
+        (y, x) sizes in, like ExtractPatches."""
+        for t, dtype, width, what in ((bytes_, torch.uint8, None, "bytes"), (image_table, torch.int64, 6, "image table"),
+                                      (taps, torch.int32, 3, "tap table"), (case_table, torch.int32, 4, "case table")):
+            if t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or (width and (t.dim() != 2 or t.shape[1] != width)):
+                raise MatrixError(f"Error: stage_images_u8 : the {what} must be a contiguous {dtype} tensor on the device"
+                                  + (f" with rows of {width}" if width else ""))
+        if case_table.shape[0] != dest.GetRows():
+            raise MatrixError(f"Error: stage_images_u8 : the case table has {case_table.shape[0]} rows for {dest.GetRows()} cases")
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
+        _chk(lib.stage_images_u8(ptr(bytes_), bytes_.numel(), ptr(image_table), image_table.shape[0], ptr(taps), taps.shape[0],
+                                 ptr(case_table), _opt(mean), _opt(std), dest.GetMat(), _opt(width_offset), _opt(height_offset),
+                                 _opt(flip_bit), int(image_size_x), int(image_size_y), int(patch_size_x), int(patch_size_y)),
+             "Error staging images")
+
     def Mult(self, val):
         if isinstance(val, Matrix):
             _chk(lib.mult_elementwise(self.GetMat(), val.GetMat(), self.GetMat(), 0.0), "mult")

@@ -221,6 +221,36 @@ int stage_clips_u8(void* frames, int frame_dims, int num_frames, cudamat* first_
 /* stage_clips_u8's grid, for A/B timing (tools/clips_bench.py); the results are the same.  0: the library's choice; 1: a block stages
  * all clip_frames planes of its (colour, patch row, tile) with mean / std in registers; 2: one plane per block. */
 void convnet_hip_set_stage_clips_grid(int mode);
+/* The same staging out of decoded image files kept at their ORIGINAL sizes, resized on the way (src/image_iterators.cc:22-30,143-187:
+ * Resize, GetCoordinates, crop, mirror; the resized image is never stored).  All buffers are plain device pointers:
+ *   bytes        num_bytes unsigned bytes: the images back to back, each h rows of w interleaved R, G, B pixels.
+ *   image_table  num_images rows of 6 signed 64-bit values {byte offset, w, h, new_w, new_h, first_tap} (8-byte aligned).
+ *   taps         num_taps rows of 3 signed 32-bit values {source index, coefficient 0, coefficient 1}: image i owns rows first_tap ...
+ *                first_tap + new_w - 1 (one per column of the resized image) and the next new_h (one per row of it).
+ *   case_table   one row of 4 signed 32-bit values per case of patches: {image, left, top, mirrored (0 / 1)}.
+ * patches is (cases, 3 * ph * pw), planar R, G, B in the layer's layout.  For case n the crop of img_height x img_width pixels is:
+ * crop column c is resized column left + (mirrored ? img_width - 1 - c : c), crop row r is resized row top + r.  On that crop the
+ * semantics are exactly stage_patches_u8's: v = (float)byte, then (v - mean[s]) / std[s] with s the pixel of the CROP (mean / std are
+ * (3 * img_height * img_width, 1), or both NULL); width_offset / height_offset / flip pick the patch inside the crop as in
+ * extract_patches, or all three NULL (the patch is then the whole crop).  Bit for bit what add_col_mult(-1), div_by_col_vec and
+ * extract_patches leave on the float cast of the crops.
+ * One byte of the resized image, integers only (arithmetic shifts): with the column's taps (sx, a0, a1), the row's (sy, b0, b1) and
+ * p(y, x) the source byte of that colour, x + 1 and y + 1 clamped to the last index,
+ *   h(y)   = ((((2048 * ((p(y, sx) * a0 + p(y, sx + 1) * a1) >> 4)) >> 16) + 2) >> 2            the width pass, rounded to a byte
+ *   result = ((((b0 * ((2048 * h(sy)) >> 4)) >> 16) + ((b1 * ((2048 * h(sy + 1)) >> 4)) >> 16) + 2) >> 2
+ * — two 8-bit bilinear resizes, first the width at the old height, then the height.  A pass that keeps its size has taps (i, 2048, 0)
+ * and is the identity.  The taps are the caller's (convnet_amd/image_iterators.py: Taps builds them in the exact float sequence).
+ * Every index read from a table is clamped on the device: the image into [0, num_images), tap rows into [0, num_taps), source
+ * indices into [0, w - 1] / [0, h - 1], the byte address below num_bytes, w / h / new_w / new_h to at least 1: a wrong table gives
+ * wrong pixels, never a read outside bytes / image_table / taps.
+ * ERROR_GENERIC for a NULL bytes / image_table / taps / case_table / patches; ERROR_INCOMPATIBLE_DIMENSIONS for num_bytes == 0,
+ * num_taps or num_images < 1 and for every shape mismatch stage_patches_u8 reports (patches not (cases, 3 * ph * pw), mean / std not
+ * (3 * H * W, 1) or only one of them, offsets not one per case or not all three, a patch larger than the crop, no jitter but patch !=
+ * crop); ERROR_UNSUPPORTED for more than 2^24 images.  Nothing is launched on an error.  One launch per call, no atomics, no
+ * workspace. */
+int stage_images_u8(void* bytes, size_t num_bytes, void* image_table, int num_images, void* taps, int num_taps, void* case_table,
+                    cudamat* mean, cudamat* std, cudamat* patches, cudamat* width_offset, cudamat* height_offset, cudamat* flip,
+                    int img_width, int img_height, int patch_width, int patch_height);
 /* ---- feature extraction: src/datawriter.cc (DataWriter::Write / WriteHDF5SeqBuf; csrc/feature_rows.hip) -------------------------
  * A layer state becomes rows of a feature file's dataset, averaged on the way.  state is (N, D), case fastest; sum has its shape (NULL
  * is fine when passes == 1); rows is (D, R): R rows of D contiguous floats; carry is (D, 1) (NULL is fine when group == 1).
