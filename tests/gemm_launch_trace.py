@@ -15,7 +15,8 @@ tail-split shape of test_hip_parity.py plain, accumulating and with bias + ReLU;
 gradient with bias) and fc6-8 (NT / NN / TN) at 128 and 256 images and conv1's weight gradient at 64, in the library's default modes — the
 sizes the launch plans were tuned at; one row for the three-blocks-per-CU gg_kernel build; one strided input gradient with N % 4 != 0.
 
-Also the home of the row runners tests/test_split_arithmetic_gpu.py shares (both_paths, run_case, the per-entry callers) and of
+Also the home of the row runners tests/test_split_arithmetic_gpu.py and tests/test_gemm_exact_gpu.py share (both_paths, run_case,
+one_path, the per-entry callers, which take an operand factory: Whole here, Guarded in tests/gemm_exact.py) and of
 alex_geoms (tests/test_full_geometry_gpu.py).  Plain helper, no pytest:
 
     python tests/gemm_launch_trace.py ROW      one row's record, for a diff against another checkout
@@ -92,66 +93,163 @@ def conv_geom(case):
     return Geom(N=N, C=C, H=H, W=W, F=F, Ky=Ky, Kx=Kx, sy=sy, sx=sx, pady=pad, padx=pad)
 
 
-def _act(a, N, W, H, C):
-    from hip_adapter import _mat
-    return _mat(a, N, W * H * C, (N, W, H, C))
+class Whole:
+    """The operand factory of the plain rows: every operand a device matrix of its own.  A factory's mat() turns a numpy array into the
+    (rows, cols) matrix the library is handed — role "act" (activations, derivatives), "param" (banks, bank gradients) or "vec" (biases,
+    bias gradients, masks), target: the call writes it — and read() brings a target back.  tests/gemm_exact.py has the factory that places
+    every operand between guard floats of one flat allocation."""
+
+    def mat(self, a, rows, cols, shape4=None, role="act", target=False):
+        from hip_adapter import _mat
+        return _mat(a, rows, cols, shape4)
+
+    def read(self, m):
+        return m.ToNumpy()
 
 
-def call_conv_fprop(case, g, x, w, t0=None, bias=None):
+WHOLE = Whole()
+
+
+def one_path(case, fn, path):
+    """fn() on one matrix path (1 = split, 0 = fp32) with the patch / wgrad-tile modes of the row: (result, the timer names that ran)"""
+    from convnet_amd import _lib
+    pm, wt = _lib.lib.convnet_hip_get_patch_mode(), _lib.lib.convnet_hip_get_wgrad_tile()
+    names = set()
+    try:
+        if case.patch_mode >= 0:
+            _lib.lib.convnet_hip_set_patch_mode(case.patch_mode)
+        if case.wgrad_tile >= 0:
+            _lib.lib.convnet_hip_set_wgrad_tile(case.wgrad_tile)
+        _lib.lib.convnet_hip_set_matrix_path(path)
+        _lib.profile_report()
+        _lib.profile_enable(True)
+        try:
+            out = fn()
+        finally:
+            names.update(r["kernel"] for r in _lib.profile_report())
+            _lib.profile_enable(False)
+    finally:
+        _lib.lib.convnet_hip_set_matrix_path(1)
+        _lib.lib.convnet_hip_set_patch_mode(pm)
+        _lib.lib.convnet_hip_set_wgrad_tile(wt)
+    return out, names
+
+
+def _act(ops, a, N, W, H, C, target=False):
+    return ops.mat(a, N, W * H * C, (N, W, H, C), "act", target)
+
+
+def _bank(ops, g, w, target=False):
+    return ops.mat(w, g.F, g.K, (g.F, g.Kx, g.Ky, g.C), "param", target)
+
+
+def call_conv_fprop(case, g, x, w, t0=None, bias=None, ops=WHOLE):
     """convUp / convUpBiasAct of the row: the targets (F, My, Mx, N)"""
     from convnet_amd.matrix import Matrix
-    from hip_adapter import _desc, _mat
-    X, Wm = _act(x, g.N, g.W, g.H, g.C), _mat(w, g.F, g.K, (g.F, g.Kx, g.Ky, g.C))
-    T = _act(t0 if t0 is not None else np.zeros(g.out_shape(), np.float32), g.N, g.Mx, g.My, g.F)
+    from hip_adapter import _desc
+    X, Wm = _act(ops, x, g.N, g.W, g.H, g.C), _bank(ops, g, w)
+    T = _act(ops, t0 if t0 is not None else np.zeros(g.out_shape(), np.float32), g.N, g.Mx, g.My, g.F, True)
     if bias is not None:
-        Matrix.ConvUpBiasAct(X, Wm, _mat(bias, 1, g.F), T, _desc(g), case.st, bool(case.relu))
+        Matrix.ConvUpBiasAct(X, Wm, ops.mat(bias, 1, g.F, None, "vec"), T, _desc(g), case.st, bool(case.relu))
     else:
         Matrix.ConvUp(X, Wm, T, _desc(g), case.st)
-    return T.ToNumpy().reshape(g.out_shape())
+    return ops.read(T).reshape(g.out_shape())
 
 
-def call_conv_dgrad(case, g, dy, w, t0=None, mask=None):
+def call_conv_dgrad(case, g, dy, w, t0=None, mask=None, ops=WHOLE):
     """convDown / convDownMask of the row: the targets (C, H, W, N)"""
     from convnet_amd.matrix import Matrix
-    from hip_adapter import _desc, _mat
-    D, Wm = _act(dy, g.N, g.Mx, g.My, g.F), _mat(w, g.F, g.K, (g.F, g.Kx, g.Ky, g.C))
-    T = _act(t0 if t0 is not None else np.zeros(g.in_shape(), np.float32), g.N, g.W, g.H, g.C)
+    from hip_adapter import _desc
+    D, Wm = _act(ops, dy, g.N, g.Mx, g.My, g.F), _bank(ops, g, w)
+    T = _act(ops, t0 if t0 is not None else np.zeros(g.in_shape(), np.float32), g.N, g.W, g.H, g.C, True)
     if mask is not None:
-        Matrix.ConvDownMask(D, Wm, _act(mask, g.N, g.W, g.H, g.C), T, _desc(g), case.st, case.post_scale)
+        S = ops.mat(mask, g.N, g.W * g.H * g.C, (g.N, g.W, g.H, g.C), "vec")
+        Matrix.ConvDownMask(D, Wm, S, T, _desc(g), case.st, case.post_scale)
     else:
         Matrix.ConvDown(D, Wm, T, _desc(g), case.st)
-    return T.ToNumpy().reshape(g.in_shape())
+    return ops.read(T).reshape(g.in_shape())
 
 
-def call_conv_wgrad(case, g, x, dy, t0, b0):
+def call_conv_wgrad(case, g, x, dy, t0, b0, ops=WHOLE):
     """convOutpBias (dW, db) or convOutp (dW, None) of the row"""
-    from hip_adapter import HipImpl, conv_outp_bias
+    from convnet_amd.matrix import Matrix
+    from hip_adapter import _desc
+    X, D = _act(ops, x, g.N, g.W, g.H, g.C), _act(ops, dy, g.N, g.Mx, g.My, g.F)
+    T = _bank(ops, g, t0, True)
     if case.entry == "convOutpBias":
-        return conv_outp_bias(g, x, dy, t0, b0, case.st, case.so)
-    return HipImpl().conv_outp(g, x, dy, t0, case.st, case.so), None
+        B = ops.mat(b0.reshape(1, g.F), 1, g.F, None, "vec", True)
+        Matrix.ConvOutpBias(X, D, T, B, _desc(g), case.st, case.so)
+        return ops.read(T).reshape(g.filt_shape()), ops.read(B).reshape(g.F)
+    Matrix.ConvOutp(X, D, T, _desc(g), 0, 0, case.st, case.so)
+    return ops.read(T).reshape(g.filt_shape()), None
 
 
-def dot_mask(Am, Bm, mask, T, case, out_shape, ta, tb):
+def dot_mask(Am, Bm, mask, T, case, out_shape, ta, tb, ops=WHOLE):
     from convnet_amd._lib import lib
-    from hip_adapter import _mat
     am = Am.GetMatTranspose() if ta else Am.GetMat()
     bm = Bm.GetMatTranspose() if tb else Bm.GetMat()
-    rc = lib.dotMask(am, bm, _mat(mask, out_shape[1], out_shape[0]).GetMat(), T.GetMat(), float(case.st), float(case.so), float(case.post_scale))
+    S = ops.mat(mask, out_shape[1], out_shape[0], None, "vec")
+    rc = lib.dotMask(am, bm, S.GetMat(), T.GetMat(), float(case.st), float(case.so), float(case.post_scale))
     assert rc == 0, rc
 
 
-def call_dot(case, A, B, t0, out_shape, ta, tb, bias=None, mask=None):
-    """dot / dotBiasAct / dotMask of the row on numpy (cols, rows) operands: the target in out_shape"""
+def call_dot(case, A, B, t0, out_shape, ta, tb, bias=None, mask=None, ops=WHOLE):
+    """dot / dotBiasAct / dotMask of the row on numpy (cols, rows) operands: the target in out_shape.  The weights are B on the NT and
+    NN rows and the target on the TN rows (role "param"); everything else is an activation or a derivative."""
     from convnet_amd.matrix import Matrix
-    from hip_adapter import _mat
-    Am, Bm, T = _mat(A, A.shape[1], A.shape[0]), _mat(B, B.shape[1], B.shape[0]), _mat(t0, out_shape[1], out_shape[0])
+    tn = case.trans == "TN"
+    Am, Bm = ops.mat(A, A.shape[1], A.shape[0]), ops.mat(B, B.shape[1], B.shape[0], None, "act" if tn else "param")
+    T = ops.mat(t0, out_shape[1], out_shape[0], None, "param" if tn else "act", True)
     if case.entry == "dotBiasAct":
-        Matrix.DotBiasAct(Am, Bm, _mat(bias, 1, out_shape[0]), T, case.st, case.so, ta, tb, bool(case.relu))
+        Matrix.DotBiasAct(Am, Bm, ops.mat(bias, 1, out_shape[0], None, "vec"), T, case.st, case.so, ta, tb, bool(case.relu))
     elif case.entry == "dotMask":
-        dot_mask(Am, Bm, mask, T, case, out_shape, ta, tb)
+        dot_mask(Am, Bm, mask, T, case, out_shape, ta, tb, ops)
     else:
         Matrix.Dot(Am, Bm, T, case.st, case.so, ta, tb)
-    return T.ToNumpy().reshape(out_shape)
+    return ops.read(T).reshape(out_shape)
+
+
+def _local_mats(ops, g, x=None, y=None, w=None, target=None):
+    """the LOCAL geometry's (activations, outputs, bank) that are given, as matrices; `target` names the one the call writes"""
+    out = []
+    if x is not None:
+        out.append(ops.mat(x, g.N, g.W * g.H * g.C, (g.N, g.W, g.H, g.C), "act", target == "x"))
+    if y is not None:
+        out.append(ops.mat(y, g.N, g.Mx * g.My * g.F, (g.N, g.Mx, g.My, g.F), "act", target == "y"))
+    if w is not None:
+        out.append(ops.mat(w, g.F, g.K * g.M, (g.F, g.Kx, g.Ky, g.C * g.M), "param", target == "w"))
+    return out
+
+
+def call_local_up(case, g, x, w, t0=None, bias=None, ops=WHOLE):
+    """localUp / localUpBiasAct of the row (bias (F, My, Mx)): the targets (F, My, Mx, N)"""
+    from convnet_amd._lib import lib
+    from convnet_amd.matrix import _conv_call
+    from hip_adapter import _desc
+    X, T, Wm = _local_mats(ops, g, x, t0 if t0 is not None else np.zeros(g.out_shape(), np.float32), w, "y")
+    if bias is not None:
+        _conv_call(lib.localUpBiasAct, (X, Wm, ops.mat(bias, 1, g.F * g.M, None, "vec"), T), _desc(g), float(case.st), int(case.relu), unshaped=2)
+    else:
+        _conv_call(getattr(lib, case.entry), (X, Wm, T), _desc(g), float(case.st))
+    return ops.read(T).reshape(g.out_shape())
+
+
+def call_local_down(case, g, dy, w, t0=None, ops=WHOLE):
+    from convnet_amd._lib import lib
+    from convnet_amd.matrix import _conv_call
+    from hip_adapter import _desc
+    T, D, Wm = _local_mats(ops, g, t0 if t0 is not None else np.zeros(g.in_shape(), np.float32), dy, w, "x")
+    _conv_call(getattr(lib, case.entry), (D, Wm, T), _desc(g), float(case.st))
+    return ops.read(T).reshape(g.in_shape())
+
+
+def call_local_outp(case, g, x, dy, t0=None, ops=WHOLE):
+    from convnet_amd._lib import lib
+    from convnet_amd.matrix import _conv_call
+    from hip_adapter import _desc
+    X, D, T = _local_mats(ops, g, x, dy, t0 if t0 is not None else np.zeros(g.bank_shape(), np.float32), "w")
+    _conv_call(getattr(lib, case.entry), (X, D, T), _desc(g), float(case.st), float(case.so))
+    return ops.read(T).reshape(g.bank_shape())
 
 
 # ---- shared with tests/test_full_geometry_gpu.py -----------------------------------------------------------------------------------

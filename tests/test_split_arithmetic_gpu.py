@@ -32,7 +32,7 @@ pytestmark = pytest.mark.gpu
 import oracle  # noqa: E402
 from oracle import Geom  # noqa: E402
 from gemm_launch_trace import (both_paths as _both_paths, run_case as _run_case, call_conv_fprop, call_conv_dgrad,  # noqa: E402
-                               call_conv_wgrad, call_dot)
+                               call_conv_wgrad, call_dot, call_local_up, call_local_down, call_local_outp)
 
 BF16_MAX = np.array([0x7F7F0000], np.uint32).view(np.float32)[0]         # 3.3895314e38
 BF16_RNE_LIMIT = np.array([0x7F7F7FFF], np.uint32).view(np.float32)[0]   # 3.3961773e38: the largest fp32 that rounds to a finite bf16
@@ -514,7 +514,6 @@ def _fc_case(hip, case, kind, rng):
 def _local_case(case, kind, rng):
     import local_ref as L
     from local_ref import LocalGeom
-    import test_local_gpu as TL
     N, C, H, W, F, Ky, Kx, sy, sx, pad = case.shape
     g = LocalGeom(N=N, C=C, H=H, W=W, F=F, Ky=Ky, Kx=Kx, sy=sy, sx=sx, pady=pad, padx=pad)
     x = rng.standard_normal(g.in_shape(), dtype=np.float32)
@@ -545,29 +544,21 @@ def _local_case(case, kind, rng):
         bias = _scaled(kind, rng, (F, g.My, g.Mx), _scale_of(x), _scale_of(w), g.K) if case.entry == "localUpBiasAct" else None
 
         def fn():
-            if bias is None:
-                return TL.run_up(g, x, w, t0, case.st, "localUp")
-            from convnet_amd._lib import lib
-            from hip_adapter import _desc, _mat, _w_local, _x, _y
-            import ctypes
-            X, Wm, T = _x(g, x), _w_local(g, w), _y(g, t0 if t0 is not None else np.zeros(g.out_shape()))
-            lib.localUpBiasAct(X.GetMat(), Wm.GetMat(), _mat(bias, 1, F * g.M).GetMat(), T.GetMat(), ctypes.byref(X.shape_),
-                               ctypes.byref(Wm.shape_), ctypes.byref(T.shape_), _desc(g), float(case.st), int(case.relu))
-            return T.ToNumpy().reshape(g.out_shape())
+            return call_local_up(case, g, x, w, t0, bias)
         exact, mag = L.torch_up(g, x, w), L.torch_up(g, np.abs(x), np.abs(w))
         extra = {"t0": t0, "bias": None if bias is None else bias[..., None]}
     elif case.op == "local_down":
         t0 = _scaled(kind, rng, g.in_shape(), _scale_of(dy), _scale_of(w), F * Ky * Kx) if case.st else None
 
         def fn():
-            return TL.run_down(g, dy, w, t0, case.st, "localDown")
+            return call_local_down(case, g, dy, w, t0)
         exact, mag = L.torch_down(g, dy, w), L.torch_down(g, np.abs(dy), np.abs(w))
         extra = {"t0": t0}
     else:
         t0 = _scaled(kind, rng, g.bank_shape(), _scale_of(x), _scale_of(dy), N) if case.st else None
 
         def fn():
-            return TL.run_outp(g, x, dy, t0, case.st, case.so, "localOutp")[0]
+            return call_local_outp(case, g, x, dy, t0)
         exact, mag = L.torch_outp(g, x, dy), L.torch_outp(g, np.abs(x), np.abs(dy))
         extra = {"t0": t0}
     ys, yf, names = _run_case(case, fn)
