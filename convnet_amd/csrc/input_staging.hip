@@ -327,6 +327,99 @@ __global__ void __launch_bounds__(256) stage_images_u8_kernel(const unsigned cha
   }
 }
 
+// The crops of the same decoded image files as STORED BYTES: case n's img_height x img_width crop of its resized image, planar R, G, B,
+// at rows + n * 3 * H * W — a row of an HDF5 byte dataset, a column of a byte chunk (image2hdf5).  The tables and the integer arithmetic
+// are stage_images_u8's; there is no cast, no mean / std and no patch.  The output is contiguous along the crop column, so nothing is
+// transposed and no tile goes through LDS: consecutive lanes take consecutive groups of four crop columns of one (case, crop row),
+// `1 << lanes_shift` lanes per row (64 from 256 columns on, fewer for a narrow crop so that its lanes are not idle), 256 >> lanes_shift
+// rows per block.  What a (case, crop row) contributes to all its pixels is worked out once by one thread and kept in LDS, where its
+// lanes read it: the two source rows' byte offsets, the row coefficients, the image's width, its first column tap, the left edge, the
+// mirror flag and where the row starts in the output.  A thread resamples its four pixels in all three colours (the 12 source bytes of
+// a pixel are interleaved in two source rows) and stores each colour as ONE dword where it owns four columns and the address is 4-byte
+// aligned, as single bytes elsewhere: 3 * H * W and H * W need not be multiples of 4, so that differs per case and per plane.
+// Everything read from a table is clamped as in stage_images_u8_kernel; every store lies inside rows by construction.
+struct CropRow {
+  size_t row0, row1;      // byte offsets of the two source rows in the buffer
+  size_t out;             // where the crop row starts in the R plane of its case
+  long col_taps;          // number of the image's first column tap
+  int width, new_w;       // source and resized width, >= 1
+  int b0, b1;             // the row coefficients
+  int left, mirror;       // where the crop starts in the resized row, and whether it walks backwards
+};
+
+__global__ void __launch_bounds__(256) crop_images_u8_kernel(const unsigned char* __restrict__ bytes, size_t num_bytes,
+                                                             const long long* __restrict__ image_table, int num_images,
+                                                             const int* __restrict__ taps, long num_taps,
+                                                             const int* __restrict__ case_table, unsigned char* __restrict__ rows,
+                                                             long total_rows, int W, int H, int lanes_shift) {
+  __shared__ CropRow terms[256];
+  const int rows_per_block = 256 >> lanes_shift;
+  const long first_row = (long)blockIdx.x * rows_per_block;
+  const size_t last = num_bytes - 1;
+  const size_t plane = (size_t)H * W;
+  if ((int)threadIdx.x < rows_per_block && first_row + threadIdx.x < total_rows) {
+    const long row = first_row + threadIdx.x;      // (case, crop row), the crop row fastest
+    const long n = row / H;
+    const int r = (int)(row - n * H);
+    const int* c = case_table + 4 * (size_t)n;
+    const long long* im = image_table + 6 * (size_t)min(max(c[0], 0), num_images - 1);
+    const auto dim = [](long long v) { return (int)min(max(v, 1LL), 1LL << 30); };
+    const int w = dim(im[1]), h = dim(im[2]), new_w = dim(im[3]), new_h = dim(im[4]);
+    const long first_tap = (long)min(max(im[5], 0LL), (long long)num_taps - 1);
+    const long rr = min(max((long)min(max(c[2], -(1 << 30)), 1 << 30) + r, 0L), (long)new_h - 1);   // the row of the resized image
+    const int* t = taps + 3 * min(first_tap + new_w + rr, num_taps - 1);
+    const int sy = min(max(t[0], 0), h - 1);
+    const size_t base = (size_t)min(max(im[0], 0LL), (long long)last);
+    CropRow& k = terms[threadIdx.x];
+    k.row0 = base + (size_t)sy * w * 3;
+    k.row1 = base + (size_t)min(sy + 1, h - 1) * w * 3;
+    k.out = (size_t)n * 3 * plane + (size_t)r * W;
+    k.col_taps = first_tap;
+    k.width = w;
+    k.new_w = new_w;
+    k.b0 = t[1];
+    k.b1 = t[2];
+    k.left = min(max(c[1], -(1 << 30)), 1 << 30);
+    k.mirror = c[3] != 0;
+  }
+  __syncthreads();
+  const int j = threadIdx.x >> lanes_shift, lane = threadIdx.x & ((1 << lanes_shift) - 1);
+  if (first_row + j >= total_rows) return;
+  const CropRow k = terms[j];
+  for (long c0 = 4L * lane; c0 < W; c0 += 4L << lanes_shift) {
+    const int count = (int)min(4L, W - c0);          // the columns of this group inside the crop
+    unsigned int px[3] = {0u, 0u, 0u};               // four columns of a colour, the first in the low byte
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (i < count) {
+        const long c = c0 + i;
+        const long rc = min(max(k.left + (k.mirror ? W - 1 - c : c), 0L), (long)k.new_w - 1);   // the column of the resized image
+        const int* t = taps + 3 * min(k.col_taps + rc, num_taps - 1);
+        const int sx = min(max(t[0], 0), k.width - 1), a0 = t[1], a1 = t[2];
+        const size_t x0 = (size_t)sx * 3, x1 = (size_t)min(sx + 1, k.width - 1) * 3;
+#pragma unroll
+        for (int color = 0; color < 3; ++color) {
+          const int h0 = resample_row(bytes, last, k.row0 + x0 + color, k.row0 + x1 + color, a0, a1);
+          const int h1 = resample_row(bytes, last, k.row1 + x0 + color, k.row1 + x1 + color, a0, a1);
+          const int v = (((k.b0 * ((2048 * h0) >> 4)) >> 16) + ((k.b1 * ((2048 * h1) >> 4)) >> 16) + 2) >> 2;
+          px[color] |= (unsigned int)(v & 255) << (8 * i);
+        }
+      }
+    }
+#pragma unroll
+    for (int color = 0; color < 3; ++color) {
+      unsigned char* p = rows + k.out + plane * color + (size_t)c0;
+      if (count == 4 && (reinterpret_cast<uintptr_t>(p) & 3) == 0) {
+        *reinterpret_cast<unsigned int*>(p) = px[color];
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (i < count) p[i] = (unsigned char)(px[color] >> (8 * i));
+      }
+    }
+  }
+}
+
 // 0: the launcher's choice; 1: every block stages all the clip's planes of its tile; 2: one plane per block (tools/clips_bench.py's A/B)
 int g_stage_clips_grid = 0;
 
@@ -528,6 +621,26 @@ int stage_images_u8(void* bytes, size_t num_bytes, void* image_table, int num_im
                      static_cast<const int*>(case_table), s.norm ? mean->data_device : nullptr, s.norm ? sdev->data_device : nullptr,
                      patches->data_device, s.jitter ? width_offset->data_device : nullptr, s.jitter ? height_offset->data_device : nullptr,
                      s.jitter ? flip->data_device : nullptr, s.num_images, img_width, img_height, patch_width, patch_height);
+  return hipGetLastError() == hipSuccess ? 0 : CUDA_ERROR;
+}
+
+int crop_images_u8(void* bytes, size_t num_bytes, void* image_table, int num_images, void* taps, int num_taps, void* case_table,
+                   int num_cases, void* rows, int img_width, int img_height) {
+  if (!bytes || !image_table || !taps || !case_table || !rows) return ERROR_GENERIC;
+  if (num_bytes == 0 || num_taps <= 0 || num_images <= 0 || num_cases <= 0 || img_width <= 0 || img_height <= 0)
+    return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (num_images > (1 << 24)) return ERROR_UNSUPPORTED;
+  int lanes_shift = 0;   // lanes per (case, crop row): the power of two that covers its groups of four columns, 64 at the most
+  while (lanes_shift < 6 && (4L << lanes_shift) < img_width) ++lanes_shift;
+  const long total_rows = (long)num_cases * img_height;
+  const long rows_per_block = 256 >> lanes_shift;
+  const long blocks = (total_rows + rows_per_block - 1) / rows_per_block;
+  if (blocks > 0x7fffffffL) return ERROR_UNSUPPORTED;
+  KernelTimer timer("crop_images_u8_kernel", "input_staging", 0.0, 5.0 * 3.0 * (double)total_rows * img_width);
+  hipLaunchKernelGGL(crop_images_u8_kernel, dim3((unsigned)blocks), dim3(256), 0, stream(), static_cast<const unsigned char*>(bytes),
+                     num_bytes, static_cast<const long long*>(image_table), num_images, static_cast<const int*>(taps), (long)num_taps,
+                     static_cast<const int*>(case_table), static_cast<unsigned char*>(rows), total_rows, img_width, img_height,
+                     lanes_shift);
   return hipGetLastError() == hipSuccess ? 0 : CUDA_ERROR;
 }
 

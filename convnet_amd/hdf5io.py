@@ -233,10 +233,10 @@ class File:
     def RowReader(self, name):
         return RowReader(self, name)
 
-    def CreateRows(self, name, num_rows, num_dims):
+    def CreateRows(self, name, num_rows, num_dims, dtype=np.float32):
         """A (num_rows, num_dims) float dataset created empty, to be filled by ``RowWriter.WriteRows`` (DataWriter::SetNumDims,
-        src/datawriter.cc:29-45)."""
-        return RowWriter(self, name, num_rows, num_dims)
+        src/datawriter.cc:29-45); ``dtype=np.uint8``: an unsigned 8-bit one (apps/image2hdf5.cc)."""
+        return RowWriter(self, name, num_rows, num_dims, dtype)
 
 
 class RowWriter:
@@ -244,12 +244,16 @@ class RowWriter:
     by hyperslabs of consecutive rows."""
 
     @_serialized
-    def __init__(self, file, name, num_rows, num_dims):
+    def __init__(self, file, name, num_rows, num_dims, dtype=np.float32):
         L = _lib()
         self.file_, self.name_, self.num_rows_, self.num_dims_ = file, name, int(num_rows), int(num_dims)
+        self.dataset_ = -1
+        self.dtype_ = np.dtype(dtype)              # the stored type: float32, or unsigned 8-bit for rows of bytes
+        if self.dtype_ not in (np.float32, np.uint8):
+            raise ValueError(f"dataset {name}: rows are written as float32 or uint8, not {self.dtype_}")
         dims = (ctypes.c_uint64 * 2)(self.num_rows_, self.num_dims_)
         space = L.H5Screate_simple(2, dims, None)
-        self.dataset_ = L.H5Dcreate2(file.id, name.encode(), _T["float"], space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT) if space >= 0 else -1
+        self.dataset_ = L.H5Dcreate2(file.id, name.encode(), _T[self.dtype_], space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT) if space >= 0 else -1
         if space >= 0:
             L.H5Sclose(space)
         if self.dataset_ < 0:
@@ -257,10 +261,11 @@ class RowWriter:
 
     @_serialized
     def WriteRows(self, data, row_start):
-        """``data``: a C-contiguous float32 array of whole rows, written to rows ``row_start`` ... of the dataset."""
+        """``data``: a C-contiguous array of whole rows in the dataset's stored type (float32 unless it was created as uint8), written to
+        rows ``row_start`` ... of the dataset."""
         L = _lib()
-        if not isinstance(data, np.ndarray) or data.dtype != np.float32 or not data.flags.c_contiguous or data.size % self.num_dims_:
-            raise ValueError(f"dataset {self.name_}: WriteRows needs a contiguous float32 array of whole rows of {self.num_dims_}")
+        if not isinstance(data, np.ndarray) or data.dtype != self.dtype_ or not data.flags.c_contiguous or data.size % self.num_dims_:
+            raise ValueError(f"dataset {self.name_}: WriteRows needs a contiguous {self.dtype_} array of whole rows of {self.num_dims_}")
         num_rows = data.size // self.num_dims_
         if self.dataset_ < 0:
             raise OSError(f"dataset {self.name_} of {self.file_.path} is closed")
@@ -272,7 +277,7 @@ class RowWriter:
         mspace = L.H5Screate_simple(2, count, None)
         rc = L.H5Sselect_hyperslab(fspace, H5S_SELECT_SET, start, None, count, None) if fspace >= 0 and mspace >= 0 else -1
         if rc >= 0:
-            rc = L.H5Dwrite(self.dataset_, _T["float"], mspace, fspace, H5P_DEFAULT, data.ctypes.data_as(ctypes.c_void_p))
+            rc = L.H5Dwrite(self.dataset_, _T[self.dtype_], mspace, fspace, H5P_DEFAULT, data.ctypes.data_as(ctypes.c_void_p))
         if mspace >= 0:
             L.H5Sclose(mspace)
         if fspace >= 0:

@@ -51,6 +51,19 @@ def _byte_columns(entry, what, holder, unit, t, dims, count):
     return ctypes.c_void_p(t.data_ptr())
 
 
+_IMAGE_TENSORS = {"bytes": (torch.uint8, None), "rows": (torch.uint8, None), "image table": (torch.int64, 6),
+                  "tap table": (torch.int32, 3), "case table": (torch.int32, 4)}
+
+
+def _check_image_tensors(entry, *tensors):
+    """The guard of the entries that read decoded images: every (tensor, what) must be contiguous, on the device, of its type and width."""
+    for t, what in tensors:
+        dtype, width = _IMAGE_TENSORS[what]
+        if t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or (width and (t.dim() != 2 or t.shape[1] != width)):
+            raise MatrixError(f"Error: {entry} : the {what} must be a contiguous {dtype} tensor on the device"
+                              + (f" with rows of {width}" if width else ""))
+
+
 class Matrix:
     # reference statics: temp_/ones_ pools, rnd_ state (src/matrix.cc:10-16)
     _temp = None
@@ -384,11 +397,8 @@ class Matrix:
         Device tensors, all contiguous: ``bytes_`` torch.uint8; ``image_table`` torch.int64 (images, 6); ``taps`` torch.int32 (taps, 3);
         ``case_table`` torch.int32 (cases of ``dest``, 4).  ``mean`` / ``std``: (3 * image_size_y * image_size_x, 1) or both None.
         (y, x) sizes in, like ExtractPatches."""
-        for t, dtype, width, what in ((bytes_, torch.uint8, None, "bytes"), (image_table, torch.int64, 6, "image table"),
-                                      (taps, torch.int32, 3, "tap table"), (case_table, torch.int32, 4, "case table")):
-            if t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or (width and (t.dim() != 2 or t.shape[1] != width)):
-                raise MatrixError(f"Error: stage_images_u8 : the {what} must be a contiguous {dtype} tensor on the device"
-                                  + (f" with rows of {width}" if width else ""))
+        _check_image_tensors("stage_images_u8", (bytes_, "bytes"), (image_table, "image table"), (taps, "tap table"),
+                             (case_table, "case table"))
         if case_table.shape[0] != dest.GetRows():
             raise MatrixError(f"Error: stage_images_u8 : the case table has {case_table.shape[0]} rows for {dest.GetRows()} cases")
         ptr = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
@@ -396,6 +406,21 @@ class Matrix:
                                  ptr(case_table), _opt(mean), _opt(std), dest.GetMat(), _opt(width_offset), _opt(height_offset),
                                  _opt(flip_bit), int(image_size_x), int(image_size_y), int(patch_size_x), int(patch_size_y)),
              "Error staging images")
+
+    @staticmethod
+    def CropImagesU8(bytes_, image_table, taps, case_table, rows, image_size_y, image_size_x):
+        """The crops of decoded images kept at their original sizes as stored bytes (include/convnet_hip.h: crop_images_u8).  The first
+        four tensors are StageImagesU8's; ``rows``: a contiguous torch.uint8 device tensor of cases * 3 * image_size_y * image_size_x
+        bytes, one planar R, G, B row per row of the case table."""
+        _check_image_tensors("crop_images_u8", (bytes_, "bytes"), (image_table, "image table"), (taps, "tap table"),
+                             (case_table, "case table"), (rows, "rows"))
+        dims = 3 * int(image_size_y) * int(image_size_x)
+        if rows.numel() != case_table.shape[0] * dims:
+            raise MatrixError(f"Error: crop_images_u8 : rows holds {rows.numel()} bytes for {case_table.shape[0]} cases of {dims}")
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
+        _chk(lib.crop_images_u8(ptr(bytes_), bytes_.numel(), ptr(image_table), image_table.shape[0], ptr(taps), taps.shape[0],
+                                ptr(case_table), case_table.shape[0], ptr(rows), int(image_size_x), int(image_size_y)),
+             "Error cropping images")
 
     def Mult(self, val):
         if isinstance(val, Matrix):

@@ -251,6 +251,21 @@ void convnet_hip_set_stage_clips_grid(int mode);
 int stage_images_u8(void* bytes, size_t num_bytes, void* image_table, int num_images, void* taps, int num_taps, void* case_table,
                     cudamat* mean, cudamat* std, cudamat* patches, cudamat* width_offset, cudamat* height_offset, cudamat* flip,
                     int img_width, int img_height, int patch_width, int patch_height);
+/* The crops of the same decoded image files as STORED BYTES (apps/image2hdf5.cc; convnet_amd/image2hdf5.py).  bytes / num_bytes,
+ * image_table / num_images, taps / num_taps and case_table are stage_images_u8's, with the same meaning; case_table has num_cases rows.
+ * rows is a plain device pointer to num_cases * 3 * img_height * img_width unsigned bytes: case n owns bytes n * 3 * H * W ..., planar
+ * R, G, B, row-major inside a plane — the row RawImageFileIterator::GetNext leaves in its buffer, a row of dataset `data`, and a column
+ * of the dims x num_cases byte chunk stage_patches_u8 and chunk_moments_u8 take.  Each byte is the resized-image byte of the
+ * definition above (h(y), then result; integers only): crop column c is resized column left + (mirrored ? img_width - 1 - c : c),
+ * crop row r is resized row top + r.  No cast, no mean / std, no patch offsets.  Every index read from a table is clamped on the
+ * device exactly as in stage_images_u8 (the image number, the tap rows, the source indices, the byte address, sizes >= 1): a wrong
+ * table gives wrong pixels, never a read outside bytes / image_table / taps or a write outside rows.  rows needs no alignment: a colour
+ * of four adjacent columns is stored as one dword where its address is 4-byte aligned and as single bytes elsewhere.
+ * ERROR_GENERIC for a NULL pointer; ERROR_INCOMPATIBLE_DIMENSIONS for num_bytes == 0 or any of num_taps, num_images, num_cases,
+ * img_height, img_width below 1; ERROR_UNSUPPORTED for more than 2^24 images (or a grid beyond 2^31 - 1 blocks).  Nothing is launched
+ * on an error.  One launch per call, no atomics, no workspace. */
+int crop_images_u8(void* bytes, size_t num_bytes, void* image_table, int num_images, void* taps, int num_taps, void* case_table,
+                   int num_cases, void* rows, int img_width, int img_height);
 /* ---- feature extraction: src/datawriter.cc (DataWriter::Write / WriteHDF5SeqBuf; csrc/feature_rows.hip) -------------------------
  * A layer state becomes rows of a feature file's dataset, averaged on the way.  state is (N, D), case fastest; sum has its shape (NULL
  * is fine when passes == 1); rows is (D, R): R rows of D contiguous floats; carry is (D, 1) (NULL is fine when group == 1).
