@@ -157,7 +157,7 @@ def ComputeMean(data_config, layer_name, num_colors, *, raw_chunks=True):
     dataset name (``DATASETS``; no S / U for a constant channel), and under ``"info"`` what the pass did: ``path`` ("kernel" or
     "float"), ``dataset_size``, ``dims``, ``image_size`` (y, x) and ``chunks``."""
     import torch
-    from .datahandler import DataHandler
+    from .datahandler import DataHandler, size_yx
     from .matrix import Matrix
     C = int(num_colors)
     cfg = StoredRowsConfig(data_config, layer_name)
@@ -181,11 +181,7 @@ def ComputeMean(data_config, layer_name, num_colors, *, raw_chunks=True):
         else:
             sums = _FloatSums(Matrix, dims, C, size)
             stage = lambda start, end, state: st.form_.Stage(st, start, end, state)
-        num_chunks = -(-size // chunk)
-        dh.StartPreload()
-        for k in range(num_chunks):
-            dh.PipelinedDiskAccess(preload_next=k + 1 < num_chunks)
-            valid = min(chunk, size - k * chunk)       # (a last chunk wraps to the first rows behind its valid part: not counted)
+        for _, valid in dh.ChunkPass():                # (what a last chunk holds behind its valid part is not counted)
             if kernel:
                 Matrix.ChunkMomentsU8(st.form_.data_, dims, chunk, 0, valid, C, acc)
             else:
@@ -195,11 +191,8 @@ def ComputeMean(data_config, layer_name, num_colors, *, raw_chunks=True):
             stats = FinishMoments(acc.cpu().numpy().view(np.uint64), size, dims, C)
         else:
             stats = sums.Finish()
-        dsc = cfg.data_config[0]
-        size_y = dsc.image_size_y if dsc.has_image_size_y() else dsc.image_size
-        size_x = dsc.image_size_x if dsc.has_image_size_x() else dsc.image_size
-        stats["info"] = {"path": "kernel" if kernel else "float", "dataset_size": size, "dims": dims, "image_size": (size_y, size_x),
-                         "chunks": num_chunks}
+        stats["info"] = {"path": "kernel" if kernel else "float", "dataset_size": size, "dims": dims,
+                         "image_size": size_yx(cfg.data_config[0], "image_size"), "chunks": -(-size // chunk)}
         return stats
     finally:
         dh.close()

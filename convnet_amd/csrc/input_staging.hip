@@ -50,6 +50,38 @@ __global__ void __launch_bounds__(256) extract_patches_kernel(const float* __res
   }
 }
 
+// What the jitter of case n contributes to every address of patch row `row`: the source row (clamped into the image), the source column of
+// patch column 0 and the direction the patch columns walk in (-1: flipped).  Patch column dc reads source column first + step * dc,
+// clamped into the image by its reader.  No jitter: the patch is the image.
+struct Jitter {
+  int row, first, step;
+};
+template <bool JITTER>
+__device__ __forceinline__ Jitter jitter_terms(const float* __restrict__ wo, const float* __restrict__ ho, const float* __restrict__ flip, int n,
+                                               int row, int W, int H, int pw, int ph) {
+  int sr = row, first = 0, step = 1;
+  if (JITTER) {
+    // (an offset beyond the image lands on the nearest border whatever its size: cut it short, so that nothing below overflows)
+    sr += min(max((int)ho[n], -H - ph), H + ph);
+    first = min(max((int)wo[n], -W - pw), W + pw);
+    if (flip[n] > 0.5f) {
+      first = W - first - 1;
+      step = -1;
+    }
+  }
+  return {min(max(sr, 0), H - 1), first, step};
+}
+
+// The write side of a 64 x 64 tile of one plane row, transposed: lane tx walks the images of patch column j, so a wave stores 256
+// contiguous bytes of the CHWN batch.  `out` is where the plane row starts: patch column dc of image n is out[n + N * dc].
+__device__ __forceinline__ void store_tile(const float (&tile)[64][65], float* __restrict__ out, int N, int n0, int pw, int c0, int tx, int ty) {
+#pragma unroll 4
+  for (int j = ty; j < 64; j += 4) {
+    const int dc = c0 + j, n = n0 + tx;
+    if (n < N && dc < pw) out[(size_t)n + (size_t)N * dc] = tile[tx][j];
+  }
+}
+
 // The same crop + flip + transpose from a chunk kept in its stored type (one unsigned byte per pixel), with the cast and the mean / std
 // normalisation of the SOURCE pixel on the way.  tile = 64 images x 64 patch columns of one (colour, patch row): twice the float
 // kernel's in both directions, because a byte run of 32 columns is only 32 B.  Read side: the 64 lanes of a wave walk the source
@@ -62,10 +94,10 @@ __global__ void __launch_bounds__(256) extract_patches_kernel(const float* __res
 // the chunk.
 template <bool NORM, bool JITTER>
 __global__ void __launch_bounds__(256) stage_patches_u8_kernel(const unsigned char* __restrict__ chunk, const float* __restrict__ case_index,
-                                                               const float* __restrict__ mean, const float* __restrict__ sdev,
-                                                               float* __restrict__ patches, const float* __restrict__ wo,
-                                                               const float* __restrict__ ho, const float* __restrict__ flip, int N,
-                                                               int num_cases, int W, int H, int pw, int ph, int colors) {
+                                                               int num_cases, int colors, const float* __restrict__ mean,
+                                                               const float* __restrict__ sdev, float* __restrict__ patches,
+                                                               const float* __restrict__ wo, const float* __restrict__ ho,
+                                                               const float* __restrict__ flip, int N, int W, int H, int pw, int ph) {
   __shared__ float tile[64][65];
   __shared__ size_t case_base[64];   // where the image's case starts in the chunk
   __shared__ int row_base[64];       // where its source row starts inside a case (< dims)
@@ -77,22 +109,12 @@ __global__ void __launch_bounds__(256) stage_patches_u8_kernel(const unsigned ch
   const int n0 = blockIdx.z * 64;
   if (ty == 0 && n0 + tx < N) {
     const int n = n0 + tx;
-    int sr = row, first = 0, step = 1;
-    if (JITTER) {
-      // (an offset beyond the image lands on the nearest border whatever its size: cut it short, so that nothing below overflows)
-      sr += min(max((int)ho[n], -H - ph), H + ph);
-      first = min(max((int)wo[n], -W - pw), W + pw);
-      if (flip[n] > 0.5f) {
-        first = W - first - 1;
-        step = -1;
-      }
-    }
-    sr = min(max(sr, 0), H - 1);
+    const Jitter k = jitter_terms<JITTER>(wo, ho, flip, n, row, W, H, pw, ph);
     const int col = min(max((int)case_index[n], 0), num_cases - 1);
     case_base[tx] = (size_t)colors * W * H * (size_t)col;
-    row_base[tx] = W * (sr + H * color);
-    col_first[tx] = first;
-    col_step[tx] = step;
+    row_base[tx] = W * (k.row + H * color);
+    col_first[tx] = k.first;
+    col_step[tx] = k.step;
   }
   __syncthreads();
 #pragma unroll 4
@@ -107,11 +129,7 @@ __global__ void __launch_bounds__(256) stage_patches_u8_kernel(const unsigned ch
     }
   }
   __syncthreads();
-#pragma unroll 4
-  for (int j = ty; j < 64; j += 4) {
-    const int dc = c0 + j, n = n0 + tx;
-    if (n < N && dc < pw) patches[(size_t)n + (size_t)N * (dc + (size_t)pw * (row + (size_t)ph * color))] = tile[tx][j];
-  }
+  store_tile(tile, patches + (size_t)N * pw * (row + (size_t)ph * color), N, n0, pw, c0, tx, ty);
 }
 
 // The same staging for CLIPS out of a buffer that holds every frame once (one frame per column, [colour][row][col]): plane
@@ -125,11 +143,11 @@ __global__ void __launch_bounds__(256) stage_patches_u8_kernel(const unsigned ch
 // patch are loaded with image 0's LDS terms or clamped (in range) and never stored.
 template <bool NORM, bool JITTER>
 __global__ void __launch_bounds__(256) stage_clips_u8_kernel(const unsigned char* __restrict__ frames, const float* __restrict__ first_frame,
+                                                             int num_frames, int clip_frames, int frames_per_block, int colors,
                                                              const float* __restrict__ mean, const float* __restrict__ sdev,
                                                              float* __restrict__ patches, const float* __restrict__ wo,
-                                                             const float* __restrict__ ho, const float* __restrict__ flip, int N,
-                                                             int num_frames, int clip_frames, int frames_per_block, int W, int H, int pw,
-                                                             int ph, int colors) {
+                                                             const float* __restrict__ ho, const float* __restrict__ flip, int N, int W,
+                                                             int H, int pw, int ph) {
   __shared__ float tile[64][65];
   __shared__ int frame_first[64];    // the clip's first frame column, clamped into the buffer
   __shared__ int row_base[64];       // where the source row starts inside a frame (< frame_dims)
@@ -144,20 +162,11 @@ __global__ void __launch_bounds__(256) stage_clips_u8_kernel(const unsigned char
   const int n0 = blockIdx.z * 64;
   if (ty == 0) {
     const int n = n0 + tx < N ? n0 + tx : 0;
-    int sr = row, first = 0, step = 1;
-    if (JITTER) {
-      sr += min(max((int)ho[n], -H - ph), H + ph);
-      first = min(max((int)wo[n], -W - pw), W + pw);
-      if (flip[n] > 0.5f) {
-        first = W - first - 1;
-        step = -1;
-      }
-    }
-    sr = min(max(sr, 0), H - 1);
+    const Jitter k = jitter_terms<JITTER>(wo, ho, flip, n, row, W, H, pw, ph);
     frame_first[tx] = min(max((int)first_frame[n], 0), num_frames - 1);
-    row_base[tx] = W * (sr + H * color);
-    col_first[tx] = first;
-    col_step[tx] = step;
+    row_base[tx] = W * (k.row + H * color);
+    col_first[tx] = k.first;
+    col_step[tx] = k.step;
   }
   __syncthreads();
   const size_t frame_dims = (size_t)colors * W * H;
@@ -204,11 +213,7 @@ __global__ void __launch_bounds__(256) stage_clips_u8_kernel(const unsigned char
         }
       }
     } else {
-#pragma unroll 4
-      for (int j = ty; j < 64; j += 4) {
-        const int dc = c0 + j, n = n0 + tx;
-        if (n < N && dc < pw) out[(size_t)n + (size_t)N * dc] = tile[tx][j];
-      }
+      store_tile(tile, out, N, n0, pw, c0, tx, ty);
     }
     __syncthreads();
   }
@@ -226,6 +231,64 @@ __global__ void __launch_bounds__(256) stage_clips_u8_kernel(const unsigned char
 // kept in LDS; the pixel loop loads one column tap (12 B, consecutive lanes consecutive taps unless mirrored) and 12 bytes.
 // Integer arithmetic only up to the cast (include/convnet_hip.h has the formula).  Everything read from a table is clamped: the image
 // number, the tap numbers, the source row and column, the byte address.
+struct ImageRow {
+  size_t row0, row1;      // byte offsets of the two source rows in the buffer
+  long col_taps;          // number of the image's first column tap
+  int width, new_w;       // source and resized width, >= 1
+  int b0, b1;             // the row coefficients
+  int left, mirror;       // where the crop starts in the resized row, and whether it walks backwards
+};
+
+// Crop row r (0 ... img_height - 1) of the case whose case-table row is c, resolved through the image and tap tables.  The tables come
+// from the host, so every value read from them is clamped here, once: the image number, the sizes (1 ... 2^30), the tap numbers, the
+// crop's corner (+-2^30, so that the 64-bit sums below cannot overflow), the source row and the byte address.
+__device__ __forceinline__ ImageRow image_row(const int* __restrict__ c, const long long* __restrict__ image_table, int num_images,
+                                              const int* __restrict__ taps, long num_taps, size_t last, int r) {
+  const long long* im = image_table + 6 * (size_t)min(max(c[0], 0), num_images - 1);
+  const auto dim = [](long long v) { return (int)min(max(v, 1LL), 1LL << 30); };
+  const int w = dim(im[1]), h = dim(im[2]), new_w = dim(im[3]), new_h = dim(im[4]);
+  const long first_tap = (long)min(max(im[5], 0LL), (long long)num_taps - 1);
+  const long rr = min(max((long)min(max(c[2], -(1 << 30)), 1 << 30) + r, 0L), (long)new_h - 1);   // the row of the resized image
+  const int* t = taps + 3 * min(first_tap + new_w + rr, num_taps - 1);
+  const int sy = min(max(t[0], 0), h - 1);
+  const size_t base = (size_t)min(max(im[0], 0LL), (long long)last);
+  ImageRow k;
+  k.row0 = base + (size_t)sy * w * 3;
+  k.row1 = base + (size_t)min(sy + 1, h - 1) * w * 3;
+  k.col_taps = first_tap;
+  k.width = w;
+  k.new_w = new_w;
+  k.b0 = t[1];
+  k.b1 = t[2];
+  k.left = min(max(c[1], -(1 << 30)), 1 << 30);
+  k.mirror = c[3] != 0;
+  return k;
+}
+
+__device__ inline int resample_row(const unsigned char* __restrict__ bytes, size_t last, size_t at0, size_t at1, int a0, int a1) {
+  const int p0 = bytes[at0 < last ? at0 : last], p1 = bytes[at1 < last ? at1 : last];
+  return (((2048 * ((p0 * a0 + p1 * a1) >> 4)) >> 16) + 2) >> 2;
+}
+
+// The three colours of crop column c (0 ... W - 1) of that row: the column of the resized image, its tap, the width pass on both source
+// rows and the height pass (include/convnet_hip.h has the formula).  A pixel's 12 source bytes are interleaved in the two rows.
+__device__ __forceinline__ void resample_pixel(const unsigned char* __restrict__ bytes, size_t last, const int* __restrict__ taps, long num_taps,
+                                               const ImageRow& k, int c, int W, int (&v)[3]) {
+  const long rc = min(max((long)k.left + (k.mirror ? W - 1 - c : c), 0L), (long)k.new_w - 1);   // the column of the resized image
+  const int* t = taps + 3 * min(k.col_taps + rc, num_taps - 1);
+  const int sx = min(max(t[0], 0), k.width - 1), a0 = t[1], a1 = t[2];
+  const size_t x0 = (size_t)sx * 3, x1 = (size_t)min(sx + 1, k.width - 1) * 3;
+#pragma unroll
+  for (int color = 0; color < 3; ++color) {
+    const int h0 = resample_row(bytes, last, k.row0 + x0 + color, k.row0 + x1 + color, a0, a1);
+    const int h1 = resample_row(bytes, last, k.row1 + x0 + color, k.row1 + x1 + color, a0, a1);
+    v[color] = (((k.b0 * ((2048 * h0) >> 4)) >> 16) + ((k.b1 * ((2048 * h1) >> 4)) >> 16) + 2) >> 2;
+  }
+}
+
+// (stage_images_u8_kernel keeps its own spelling of the case terms, the jitter, the resample and the store — ImageCase and the kernel
+// below — instead of jitter_terms / image_row / resample_pixel / store_tile: built on them it took 3 % longer on the MI355X, NOTES.md.  A
+// clamp that changes in image_row changes here too.)
 struct ImageCase {
   size_t row0, row1;      // byte offsets of the two source rows in the buffer
   int width;              // source width, >= 1
@@ -235,11 +298,6 @@ struct ImageCase {
   int left, mirror;       // where the crop starts in the resized row, and whether it walks backwards
   int col_first, col_step, crop_row;   // the jitter: crop column of patch column 0, direction, crop row
 };
-
-__device__ inline int resample_row(const unsigned char* __restrict__ bytes, size_t last, size_t at0, size_t at1, int a0, int a1) {
-  const int p0 = bytes[at0 < last ? at0 : last], p1 = bytes[at1 < last ? at1 : last];
-  return (((2048 * ((p0 * a0 + p1 * a1) >> 4)) >> 16) + 2) >> 2;
-}
 
 template <bool NORM, bool JITTER>
 __global__ void __launch_bounds__(256) stage_images_u8_kernel(const unsigned char* __restrict__ bytes, size_t num_bytes,
@@ -334,17 +392,13 @@ __global__ void __launch_bounds__(256) stage_images_u8_kernel(const unsigned cha
 // `1 << lanes_shift` lanes per row (64 from 256 columns on, fewer for a narrow crop so that its lanes are not idle), 256 >> lanes_shift
 // rows per block.  What a (case, crop row) contributes to all its pixels is worked out once by one thread and kept in LDS, where its
 // lanes read it: the two source rows' byte offsets, the row coefficients, the image's width, its first column tap, the left edge, the
-// mirror flag and where the row starts in the output.  A thread resamples its four pixels in all three colours (the 12 source bytes of
+// mirror flag (image_row's terms) and where the row starts in the output.  A thread resamples its four pixels in all three colours (the 12 source bytes of
 // a pixel are interleaved in two source rows) and stores each colour as ONE dword where it owns four columns and the address is 4-byte
 // aligned, as single bytes elsewhere: 3 * H * W and H * W need not be multiples of 4, so that differs per case and per plane.
 // Everything read from a table is clamped as in stage_images_u8_kernel; every store lies inside rows by construction.
 struct CropRow {
-  size_t row0, row1;      // byte offsets of the two source rows in the buffer
+  ImageRow image;
   size_t out;             // where the crop row starts in the R plane of its case
-  long col_taps;          // number of the image's first column tap
-  int width, new_w;       // source and resized width, >= 1
-  int b0, b1;             // the row coefficients
-  int left, mirror;       // where the crop starts in the resized row, and whether it walks backwards
 };
 
 __global__ void __launch_bounds__(256) crop_images_u8_kernel(const unsigned char* __restrict__ bytes, size_t num_bytes,
@@ -361,26 +415,8 @@ __global__ void __launch_bounds__(256) crop_images_u8_kernel(const unsigned char
     const long row = first_row + threadIdx.x;      // (case, crop row), the crop row fastest
     const long n = row / H;
     const int r = (int)(row - n * H);
-    const int* c = case_table + 4 * (size_t)n;
-    const long long* im = image_table + 6 * (size_t)min(max(c[0], 0), num_images - 1);
-    const auto dim = [](long long v) { return (int)min(max(v, 1LL), 1LL << 30); };
-    const int w = dim(im[1]), h = dim(im[2]), new_w = dim(im[3]), new_h = dim(im[4]);
-    const long first_tap = (long)min(max(im[5], 0LL), (long long)num_taps - 1);
-    const long rr = min(max((long)min(max(c[2], -(1 << 30)), 1 << 30) + r, 0L), (long)new_h - 1);   // the row of the resized image
-    const int* t = taps + 3 * min(first_tap + new_w + rr, num_taps - 1);
-    const int sy = min(max(t[0], 0), h - 1);
-    const size_t base = (size_t)min(max(im[0], 0LL), (long long)last);
-    CropRow& k = terms[threadIdx.x];
-    k.row0 = base + (size_t)sy * w * 3;
-    k.row1 = base + (size_t)min(sy + 1, h - 1) * w * 3;
-    k.out = (size_t)n * 3 * plane + (size_t)r * W;
-    k.col_taps = first_tap;
-    k.width = w;
-    k.new_w = new_w;
-    k.b0 = t[1];
-    k.b1 = t[2];
-    k.left = min(max(c[1], -(1 << 30)), 1 << 30);
-    k.mirror = c[3] != 0;
+    terms[threadIdx.x].image = image_row(case_table + 4 * (size_t)n, image_table, num_images, taps, num_taps, last, r);
+    terms[threadIdx.x].out = (size_t)n * 3 * plane + (size_t)r * W;
   }
   __syncthreads();
   const int j = threadIdx.x >> lanes_shift, lane = threadIdx.x & ((1 << lanes_shift) - 1);
@@ -392,18 +428,10 @@ __global__ void __launch_bounds__(256) crop_images_u8_kernel(const unsigned char
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       if (i < count) {
-        const long c = c0 + i;
-        const long rc = min(max(k.left + (k.mirror ? W - 1 - c : c), 0L), (long)k.new_w - 1);   // the column of the resized image
-        const int* t = taps + 3 * min(k.col_taps + rc, num_taps - 1);
-        const int sx = min(max(t[0], 0), k.width - 1), a0 = t[1], a1 = t[2];
-        const size_t x0 = (size_t)sx * 3, x1 = (size_t)min(sx + 1, k.width - 1) * 3;
+        int v[3];
+        resample_pixel(bytes, last, taps, num_taps, k.image, (int)c0 + i, W, v);
 #pragma unroll
-        for (int color = 0; color < 3; ++color) {
-          const int h0 = resample_row(bytes, last, k.row0 + x0 + color, k.row0 + x1 + color, a0, a1);
-          const int h1 = resample_row(bytes, last, k.row1 + x0 + color, k.row1 + x1 + color, a0, a1);
-          const int v = (((k.b0 * ((2048 * h0) >> 4)) >> 16) + ((k.b1 * ((2048 * h1) >> 4)) >> 16) + 2) >> 2;
-          px[color] |= (unsigned int)(v & 255) << (8 * i);
-        }
+        for (int color = 0; color < 3; ++color) px[color] |= (unsigned int)(v[color] & 255) << (8 * i);
       }
     }
 #pragma unroll
@@ -495,27 +523,27 @@ int check_rowvec(const cudamat* mat, const cudamat* vec, const cudamat* target) 
   return 0;
 }
 
-// The arguments of a byte-staging entry (stage_patches_u8, stage_clips_u8) and what checking them works out.  A case is ``planes``
-// columns of ``dims`` bytes out of ``count`` (1: a chunk of cases; clip_frames: a buffer of frames), ``index`` names the (first) column
-// of every image, and a block stages ``planes_per_block`` planes of its 64 x 64 tile: the kernel's arguments between count and geometry.
+// The arguments the byte-staging entries (stage_patches_u8, stage_clips_u8, stage_images_u8) share and what checking them works out.  A
+// case is ``planes`` columns of ``dims`` bytes out of ``count`` (1: a chunk of cases or of images; clip_frames: a buffer of frames),
+// ``index`` names the (first) column of every case where the entry has one (nullptr: stage_images_u8, whose tables are plain device
+// pointers), and a block stages ``planes_per_block`` planes of ``colors_per_block`` colours of its 64 x 64 tile.
 struct StageU8 {
-  void* data;
   int dims, count;
   cudamat *index, *mean, *sdev, *patches, *width_offset, *height_offset, *flip;
-  int img_width, img_height, patch_width, patch_height, planes, planes_per_block;
+  int img_width, img_height, patch_width, patch_height, planes, planes_per_block, colors_per_block;
   bool norm, jitter;
   int num_colors, num_images;   // (0 images: nothing to launch)
   long grid_y;
+  const float *index_dev, *mean_dev, *sdev_dev, *wo_dev, *ho_dev, *flip_dev;   // the operands on the device; nullptr: not given
 };
 
-// Error code or 0, in the precedence tests/test_stage_patches_gpu.py and tests/test_stage_clips_gpu.py list.  ``indexed`` false: the
-// entry has no per-case column index (stage_images_u8, whose tables are plain device pointers), and s.index is not looked at.
-int check_stage_u8(StageU8& s, bool indexed = true) {
-  if (!s.data || (indexed && !s.index) || !s.patches) return ERROR_NOT_ON_DEVICE;
+// Error code or 0, in the precedence tests/test_stage_patches_gpu.py, test_stage_clips_gpu.py and test_stage_images_gpu.py list, behind
+// the entry's own code for a null pointer.
+int check_stage_u8(StageU8& s) {
   s.norm = s.mean || s.sdev;
   s.jitter = s.width_offset || s.height_offset || s.flip;
   if ((s.norm && !(s.mean && s.sdev)) || (s.jitter && !(s.width_offset && s.height_offset && s.flip))) return ERROR_INCOMPATIBLE_DIMENSIONS;
-  if ((indexed && !s.index->on_device) || !s.patches->on_device || (s.norm && (!s.mean->on_device || !s.sdev->on_device)) ||
+  if ((s.index && !s.index->on_device) || !s.patches->on_device || (s.norm && (!s.mean->on_device || !s.sdev->on_device)) ||
       (s.jitter && (!s.width_offset->on_device || !s.height_offset->on_device || !s.flip->on_device)))
     return ERROR_NOT_ON_DEVICE;
   if (s.patches->is_trans) return ERROR_TRANSPOSED;
@@ -526,15 +554,18 @@ int check_stage_u8(StageU8& s, bool indexed = true) {
   if (s.dims % ((long)s.img_width * s.img_height) != 0) return ERROR_INCOMPATIBLE_DIMENSIONS;
   s.num_colors = s.dims / (s.img_width * s.img_height);
   const size_t num_images = s.num_images = s.patches->size[0];
-  if ((long)s.patches->size[1] != (long)s.planes * s.num_colors * s.patch_width * s.patch_height || (indexed && numel(s.index) != num_images))
+  if ((long)s.patches->size[1] != (long)s.planes * s.num_colors * s.patch_width * s.patch_height || (s.index && numel(s.index) != num_images))
     return ERROR_INCOMPATIBLE_DIMENSIONS;
   if (s.norm && (s.mean->size[0] != s.dims || s.mean->size[1] != 1 || s.sdev->size[0] != s.dims || s.sdev->size[1] != 1))
     return ERROR_INCOMPATIBLE_DIMENSIONS;
   if (s.jitter && (numel(s.width_offset) != num_images || numel(s.height_offset) != num_images || numel(s.flip) != num_images))
     return ERROR_INCOMPATIBLE_DIMENSIONS;
   if (s.count > (1 << 24)) return ERROR_UNSUPPORTED;   // a column number must be exact as a float
+  const auto dev = [](const cudamat* m) { return m ? m->data_device : nullptr; };
+  s.index_dev = dev(s.index), s.mean_dev = dev(s.mean), s.sdev_dev = dev(s.sdev);
+  s.wo_dev = dev(s.width_offset), s.ho_dev = dev(s.height_offset), s.flip_dev = dev(s.flip);
   if (num_images == 0) return 0;
-  s.grid_y = (long)s.patch_height * s.num_colors * divup(s.planes, s.planes_per_block);
+  s.grid_y = (long)s.patch_height * divup(s.num_colors, s.colors_per_block) * divup(s.planes, s.planes_per_block);
   return s.grid_y > 65535 || divup(s.num_images, 64) > 65535 ? ERROR_UNSUPPORTED : 0;
 }
 
@@ -542,15 +573,21 @@ int check_stage_u8(StageU8& s, bool indexed = true) {
 #define STAGE_U8_KERNEL(kernel, s) \
   ((s).norm ? ((s).jitter ? kernel<true, true> : kernel<true, false>) : ((s).jitter ? kernel<false, true> : kernel<false, false>))
 
-template <typename Kernel, typename... Planes>
-int launch_stage_u8(const StageU8& s, Kernel kernel, Planes... planes) {
+// ``source``: the kernel's own arguments, in front of the shared operands and the geometry
+template <typename Kernel, typename... Source>
+int launch_stage_u8(const StageU8& s, Kernel kernel, Source... source) {
   const dim3 grid(divup(s.patch_width, 64), (unsigned)s.grid_y, divup(s.num_images, 64));
-  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream(), static_cast<const unsigned char*>(s.data), s.index->data_device,
-                     s.norm ? s.mean->data_device : nullptr, s.norm ? s.sdev->data_device : nullptr, s.patches->data_device,
-                     s.jitter ? s.width_offset->data_device : nullptr, s.jitter ? s.height_offset->data_device : nullptr,
-                     s.jitter ? s.flip->data_device : nullptr, s.num_images, s.count, planes..., s.img_width, s.img_height, s.patch_width,
-                     s.patch_height, s.num_colors);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream(), source..., s.mean_dev, s.sdev_dev, s.patches->data_device, s.wo_dev, s.ho_dev,
+                     s.flip_dev, s.num_images, s.img_width, s.img_height, s.patch_width, s.patch_height);
   return hipGetLastError() == hipSuccess ? 0 : CUDA_ERROR;
+}
+
+// What stage_images_u8 and crop_images_u8 take alike — the decoded images, their three tables and the crop size — and the codes both
+// report first; ``target`` is where the entry writes.
+int check_image_tables(const void* bytes, size_t num_bytes, const void* image_table, const void* taps, int num_taps, const void* case_table,
+                       const void* target, int img_width, int img_height) {
+  if (!bytes || !image_table || !taps || !case_table || !target) return ERROR_GENERIC;
+  return num_bytes == 0 || num_taps <= 0 || img_width <= 0 || img_height <= 0 ? ERROR_INCOMPATIBLE_DIMENSIONS : 0;
 }
 
 }  // namespace
@@ -583,11 +620,13 @@ int extract_patches(cudamat* images, cudamat* patches, cudamat* width_offset, cu
 int stage_patches_u8(void* chunk, int dims, int num_cases, cudamat* case_index, cudamat* mean, cudamat* sdev, cudamat* patches,
                      cudamat* width_offset, cudamat* height_offset, cudamat* flip, int img_width, int img_height, int patch_width,
                      int patch_height) {
-  StageU8 s{chunk, dims, num_cases, case_index, mean, sdev, patches, width_offset, height_offset, flip, img_width, img_height, patch_width,
-            patch_height, 1, 1};
+  if (!chunk || !case_index || !patches) return ERROR_NOT_ON_DEVICE;
+  StageU8 s{dims, num_cases, case_index, mean, sdev, patches, width_offset, height_offset, flip, img_width, img_height, patch_width,
+            patch_height, 1, 1, 1};
   if (const int e = check_stage_u8(s); e || s.num_images == 0) return e;
   KernelTimer timer("stage_patches_u8_kernel", "input_staging", 0.0, 5.0 * numel(patches));
-  return launch_stage_u8(s, STAGE_U8_KERNEL(stage_patches_u8_kernel, s));
+  return launch_stage_u8(s, STAGE_U8_KERNEL(stage_patches_u8_kernel, s), static_cast<const unsigned char*>(chunk), s.index_dev, num_cases,
+                         s.num_colors);
 }
 
 void convnet_hip_set_stage_clips_grid(int mode) { g_stage_clips_grid = mode == 1 || mode == 2 ? mode : 0; }
@@ -595,40 +634,35 @@ void convnet_hip_set_stage_clips_grid(int mode) { g_stage_clips_grid = mode == 1
 int stage_clips_u8(void* frames, int frame_dims, int num_frames, cudamat* first_frame, int clip_frames, cudamat* mean, cudamat* sdev,
                    cudamat* patches, cudamat* width_offset, cudamat* height_offset, cudamat* flip, int img_width, int img_height,
                    int patch_width, int patch_height) {
+  if (!frames || !first_frame || !patches) return ERROR_NOT_ON_DEVICE;
   const int frames_per_block = g_stage_clips_grid == 2 ? 1 : clip_frames;
-  StageU8 s{frames, frame_dims, num_frames, first_frame, mean, sdev, patches, width_offset, height_offset, flip, img_width, img_height,
-            patch_width, patch_height, clip_frames, frames_per_block};
+  StageU8 s{frame_dims, num_frames, first_frame, mean, sdev, patches, width_offset, height_offset, flip, img_width, img_height,
+            patch_width, patch_height, clip_frames, frames_per_block, 1};
   if (const int e = check_stage_u8(s); e || s.num_images == 0) return e;
   KernelTimer timer("stage_clips_u8_kernel", "input_staging", 0.0, (5.0 + (s.norm ? 8.0 / frames_per_block : 0.0)) * numel(patches));
-  return launch_stage_u8(s, STAGE_U8_KERNEL(stage_clips_u8_kernel, s), clip_frames, frames_per_block);
+  return launch_stage_u8(s, STAGE_U8_KERNEL(stage_clips_u8_kernel, s), static_cast<const unsigned char*>(frames), s.index_dev, num_frames,
+                         clip_frames, frames_per_block, s.num_colors);
 }
 
 int stage_images_u8(void* bytes, size_t num_bytes, void* image_table, int num_images, void* taps, int num_taps, void* case_table,
                     cudamat* mean, cudamat* sdev, cudamat* patches, cudamat* width_offset, cudamat* height_offset, cudamat* flip,
                     int img_width, int img_height, int patch_width, int patch_height) {
-  if (!bytes || !image_table || !taps || !case_table || !patches) return ERROR_GENERIC;
-  // the rest is stage_patches_u8's checker on a crop of three colours
-  if (img_width <= 0 || img_height <= 0 || (long)img_width * img_height > (1 << 28) || num_bytes == 0 || num_taps <= 0)
-    return ERROR_INCOMPATIBLE_DIMENSIONS;
-  StageU8 s{bytes, 3 * img_width * img_height, num_images, nullptr, mean, sdev, patches, width_offset, height_offset, flip, img_width,
-            img_height, patch_width, patch_height, 1, 1};
-  if (const int e = check_stage_u8(s, false); e || s.num_images == 0) return e;
-  if (s.patch_height > 65535) return ERROR_UNSUPPORTED;
+  if (const int e = check_image_tables(bytes, num_bytes, image_table, taps, num_taps, case_table, patches, img_width, img_height)) return e;
+  if ((long)img_width * img_height > (1 << 28)) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  // the rest is stage_patches_u8's checker on a crop of three colours, which a block stages together
+  StageU8 s{3 * img_width * img_height, num_images, nullptr, mean, sdev, patches, width_offset, height_offset, flip, img_width, img_height,
+            patch_width, patch_height, 1, 1, 3};
+  if (const int e = check_stage_u8(s); e || s.num_images == 0) return e;
   KernelTimer timer("stage_images_u8_kernel", "input_staging", 0.0, 16.0 * numel(patches));
-  const dim3 grid(divup(s.patch_width, 64), s.patch_height, divup(s.num_images, 64));
-  hipLaunchKernelGGL(STAGE_U8_KERNEL(stage_images_u8_kernel, s), grid, dim3(256), 0, stream(), static_cast<const unsigned char*>(bytes),
-                     num_bytes, static_cast<const long long*>(image_table), num_images, static_cast<const int*>(taps), (long)num_taps,
-                     static_cast<const int*>(case_table), s.norm ? mean->data_device : nullptr, s.norm ? sdev->data_device : nullptr,
-                     patches->data_device, s.jitter ? width_offset->data_device : nullptr, s.jitter ? height_offset->data_device : nullptr,
-                     s.jitter ? flip->data_device : nullptr, s.num_images, img_width, img_height, patch_width, patch_height);
-  return hipGetLastError() == hipSuccess ? 0 : CUDA_ERROR;
+  return launch_stage_u8(s, STAGE_U8_KERNEL(stage_images_u8_kernel, s), static_cast<const unsigned char*>(bytes), num_bytes,
+                         static_cast<const long long*>(image_table), num_images, static_cast<const int*>(taps), (long)num_taps,
+                         static_cast<const int*>(case_table));
 }
 
 int crop_images_u8(void* bytes, size_t num_bytes, void* image_table, int num_images, void* taps, int num_taps, void* case_table,
                    int num_cases, void* rows, int img_width, int img_height) {
-  if (!bytes || !image_table || !taps || !case_table || !rows) return ERROR_GENERIC;
-  if (num_bytes == 0 || num_taps <= 0 || num_images <= 0 || num_cases <= 0 || img_width <= 0 || img_height <= 0)
-    return ERROR_INCOMPATIBLE_DIMENSIONS;
+  if (const int e = check_image_tables(bytes, num_bytes, image_table, taps, num_taps, case_table, rows, img_width, img_height)) return e;
+  if (num_images <= 0 || num_cases <= 0) return ERROR_INCOMPATIBLE_DIMENSIONS;
   if (num_images > (1 << 24)) return ERROR_UNSUPPORTED;
   int lanes_shift = 0;   // lanes per (case, crop row): the power of two that covers its groups of four columns, 64 at the most
   while (lanes_shift < 6 && (4L << lanes_shift) < img_width) ++lanes_shift;

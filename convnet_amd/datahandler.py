@@ -201,16 +201,19 @@ _REFUSED_TYPES = {
     "CROPS": "crops of raw images", "VIDEO_RAW": "video files decoded on the host"}
 
 
-def _raw_image_size(dsc):
-    """(y, x) of the size every image of an IMAGE_RAW stream is resized to cover (src/datahandler.cc:725-726)."""
-    return (dsc.raw_image_size_y if dsc.has_raw_image_size_y() else dsc.raw_image_size,
-            dsc.raw_image_size_x if dsc.has_raw_image_size_x() else dsc.raw_image_size)
+def size_yx(dsc, field, default=None):
+    """(y, x) of a stream's ``field`` (image_size; raw_image_size, the size every image of an IMAGE_RAW stream is resized to cover,
+    src/datahandler.cc:725-726; gpu_image_size): ``field_y`` / ``field_x`` where the config sets them, else ``field`` for both — or
+    ``default`` = (y, x), for the size that has no field of its own (gpu_image_size: the image size)."""
+    y, x = default if default is not None else (getattr(dsc, field),) * 2
+    return (getattr(dsc, field + "_y") if getattr(dsc, f"has_{field}_y")() else y,
+            getattr(dsc, field + "_x") if getattr(dsc, f"has_{field}_x")() else x)
 
 
 def _check_image_stream(dsc):
     """What an IMAGE_RAW stream cannot be here, each with a message of its own naming the layer and the field."""
     head = f"Data stream for layer {dsc.layer_name}: "
-    raw_y, raw_x = _raw_image_size(dsc)
+    raw_y, raw_x = size_yx(dsc, "raw_image_size")
     if raw_y <= 0 or raw_x <= 0:
         raise SystemExit(head + "data_type IMAGE_RAW without a raw_image_size (the size every image is resized to cover) is not supported; "
                          "set raw_image_size, or raw_image_size_y and raw_image_size_x.")
@@ -229,8 +232,7 @@ def _check_image_stream(dsc):
     if dsc.num_colors != 3:
         raise SystemExit(head + f"num_colors {dsc.num_colors} is not supported on an IMAGE_RAW stream: a decoded image has 3 colour planes "
                          "(the reference writes three into a buffer of num_colors).")
-    size_y = dsc.image_size_y if dsc.has_image_size_y() else dsc.image_size
-    size_x = dsc.image_size_x if dsc.has_image_size_x() else dsc.image_size
+    size_y, size_x = size_yx(dsc, "image_size")
     if size_y <= 0 or size_x <= 0:
         raise SystemExit(head + "an IMAGE_RAW stream needs an image_size (the crop taken from every resized image).")
     if size_y > raw_y or size_x > raw_x:
@@ -351,12 +353,11 @@ class _Stream:
         if dsc.gpu_id != 0:
             raise SystemExit(f"Data stream for layer {name}: gpu_id {dsc.gpu_id} is not supported: one process drives one GPU, gpu_id 0.")
         self.config_, self.layer_name_ = dsc, name
-        size_y = dsc.image_size_y if dsc.has_image_size_y() else dsc.image_size
-        size_x = dsc.image_size_x if dsc.has_image_size_x() else dsc.image_size
+        size_y, size_x = size_yx(dsc, "image_size")
         if self.is_images_:          # ImageDataIterator (:723-754): a list of image files, resized to cover the raw size and cropped
             from . import image_iterators
             self.file_ = None
-            self.raw_size_y_, self.raw_size_x_ = _raw_image_size(dsc)
+            self.raw_size_y_, self.raw_size_x_ = size_yx(dsc, "raw_image_size")
             self.reader_ = image_iterators.ImageReader(image_iterators.ReadFileList(dsc.file_pattern), size_y, size_x, self.raw_size_y_,
                                                        self.raw_size_x_, dsc.avg10_full_image, dsc.parallel_disk_access, name)
         else:
@@ -372,8 +373,7 @@ class _Stream:
                 self.close()
                 raise
             self.frames_ = 1 if dsc.pick_first else dsc.seq_length
-        self.jitter_ = j = _Jitter(size_y, size_x, dsc.gpu_image_size_y if dsc.has_gpu_image_size_y() else size_y,
-                                   dsc.gpu_image_size_x if dsc.has_gpu_image_size_x() else size_x, dsc.can_translate, dsc.can_flip)
+        self.jitter_ = j = _Jitter(size_y, size_x, *size_yx(dsc, "gpu_image_size", (size_y, size_x)), dsc.can_translate, dsc.can_flip)
         self.width_offset_, self.height_offset_, self.flip_bit_ = j.width_offset_, j.height_offset_, j.flip_bit_
         self.num_colors_ = dsc.num_colors
         self.normalize_ = dsc.normalize or dsc.pixelwise_normalize
@@ -557,6 +557,11 @@ class _ImagesDisk(_RowsDisk):
         self.image_of_file_ = [{} for _ in range(count)]
         return (self.start_bytes_,), self.dtype_
 
+    def Used(self, buf):
+        """What the chunk in host buffer ``buf`` filled: the bytes, the image table, the taps and the case table (views)."""
+        return (self.bytes_[buf][:self.bytes_used_[buf]], self.image_table_[buf][:self.images_used_[buf]],
+                self.taps_[buf][:self.taps_used_[buf]], self.case_table_[buf])
+
     def LoadPiece(self, out, buf, at, row, n):
         """The files of rows ``row:row + n`` that the buffer does not hold yet go behind what it holds (a run at chunk position 0 begins
         it); cases ``at`` ... of the case table get their image and the crop of their position in the RESIZED image."""
@@ -730,20 +735,24 @@ class _ImagesOnceForm(_Form):
         if used > self.data_.numel():
             self.data_ = torch.empty(2 * used, dtype=torch.uint8, device=dev)
         self.data_[:used].copy_(src[:used], non_blocking=True)
-        self.image_table_ = torch.from_numpy(d.image_table_[buf][:d.images_used_[buf]]).to(dev)
-        self.taps_ = torch.from_numpy(d.taps_[buf][:d.taps_used_[buf]]).to(dev)
-        self.case_host_ = d.case_table_[buf].copy()
+        _, image_table, taps, case_table = d.Used(buf)
+        self.image_table_, self.taps_ = torch.from_numpy(image_table).to(dev), torch.from_numpy(taps).to(dev)
+        self.case_host_ = case_table.copy()
         self.case_table_ = torch.from_numpy(self.case_host_).to(dev)
 
     def SwapEntries(self, a, b):
         self.case_host_[a], self.case_host_[b] = self.case_host_[b].copy(), self.case_host_[a].copy()
         self.case_table_ = torch.from_numpy(self.case_host_).to(self.data_.device)
 
+    def Cases(self, start, end):
+        """The chunk on the device as the image entries take it: the bytes, the image table, the taps and cases ``start:end``."""
+        return self.data_[:self.bytes_used_], self.image_table_, self.taps_, self.case_table_[start:end]
+
     def Stage(self, st, start, end, output):
         j = st.jitter_
         offsets = (j.width_offset_, j.height_offset_, j.flip_bit_) if j.Jitters() else (None, None, None)
-        Matrix.StageImagesU8(self.data_[:self.bytes_used_], self.image_table_, self.taps_, self.case_table_[start:end], *st.Normalizers(),
-                             output, *offsets, j.image_size_y_, j.image_size_x_, j.gpu_image_size_y_, j.gpu_image_size_x_)
+        Matrix.StageImagesU8(*self.Cases(start, end), *st.Normalizers(), output, *offsets, j.image_size_y_, j.image_size_x_,
+                             j.gpu_image_size_y_, j.gpu_image_size_x_)
 
 
 class _DiskSide:
@@ -1029,7 +1038,7 @@ class DataHandler:
 
     # ---- DataHandler::PipelinedDiskAccess / StartPreload / WaitForPreload (:202-237) ----
     def PipelinedDiskAccess(self, preload_next=True):
-        """``preload_next=False``: the chunk that is uploaded now is the last one a single pass needs (compute_mean)."""
+        """``preload_next=False``: the chunk that is uploaded now is the last one a single pass needs (ChunkPass)."""
         if self.pipeline_loads_:
             self.WaitForPreload()
             buf = self.pending_
@@ -1045,6 +1054,20 @@ class DataHandler:
             self.col_index_.Reset()
         if self.pipeline_loads_ and preload_next:
             self.StartPreload()
+
+    def ChunkPass(self):
+        """ONE pass over the dataset, chunk by chunk (compute_mean, image2hdf5): starts the preload; per chunk waits for it, uploads the
+        chunk and preloads the next one unless this is the last, then yields the chunk's number and how many of its cases count (a last
+        chunk wraps to the first rows behind its valid part).  ``pass_wait_seconds_``: the time the pass spent waiting and uploading."""
+        import time
+        num_chunks = -(-self.dataset_size_ // self.chunk_size_)
+        self.pass_wait_seconds_ = 0.0
+        self.StartPreload()
+        for k in range(num_chunks):
+            t0 = time.perf_counter()
+            self.PipelinedDiskAccess(preload_next=k + 1 < num_chunks)
+            self.pass_wait_seconds_ += time.perf_counter() - t0
+            yield k, min(self.chunk_size_, self.dataset_size_ - k * self.chunk_size_)
 
     def StartPreload(self):
         import threading

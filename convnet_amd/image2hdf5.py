@@ -111,15 +111,10 @@ def _gpu_rows(file_list, crop, resize, chunk, data, mean_file, out, info):
         rows = torch.empty(chunk * dims, dtype=torch.uint8, device=dev)
         slots = [_Slot(torch, chunk, dims) for _ in range(2)]
         acc = torch.zeros(2 * dims + NUM_COLORS * NUM_COLORS, dtype=torch.int64, device=dev) if mean_file else None
-        num_chunks = -(-size // chunk)
-        dh.StartPreload()
-        for k in range(num_chunks):
-            t0 = time.perf_counter()
-            dh.PipelinedDiskAccess(preload_next=k + 1 < num_chunks)     # waits for this chunk's decode, starts the next one's
-            info["load_wait_seconds"] += time.perf_counter() - t0
-            valid = min(chunk, size - k * chunk)       # (a last chunk wraps to the first files behind its valid part: not counted)
+        for k, valid in dh.ChunkPass():                # (waits for this chunk's decode, starts the next one's)
+            info["load_wait_seconds"] = dh.pass_wait_seconds_
             crops = rows[:valid * dims]
-            Matrix.CropImagesU8(form.data_[:form.bytes_used_], form.image_table_, form.taps_, form.case_table_[:valid], crops, crop, crop)
+            Matrix.CropImagesU8(*form.Cases(0, valid), crops, crop, crop)
             if acc is not None:
                 Matrix.ChunkMomentsU8(crops, dims, valid, 0, valid, NUM_COLORS, acc)
             slot = slots[k % 2]

@@ -1,4 +1,4 @@
-// Force-included in front of convnet_amd/csrc/input_staging.hip when tests/test_crop_images_emulated.py compiles it as host C++: what
+// Force-included in front of convnet_amd/csrc/input_staging.hip when tests/test_input_staging_emulated.py compiles it as host C++: what
 // that file needs beyond tests/emu/hip/hip_runtime.h.  A static __shared__ array is one array per block there (blocks run one after the
 // other on one OS thread, so a function-local static serves), and the kernels clamp 64-bit indices with min / max.
 #pragma once

@@ -11,20 +11,10 @@ double-precision reference (tests/emu/emu_main.cc).
 No GPU; not a product path.  What this cannot see: timing, late-landing loads (tests/test_patch_wide_cpu.py / test_wgrad_wide_cpu.py model
 those), the M0 range above 84 KB, instruction hazards.  CONVNET_EMU_ALL=1 runs every case (~5 minutes) instead of a subset (~1.5)."""
 import os
-import shutil
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-
-
-def _clang():
-    for c in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++")):
-        if c and os.path.exists(c):
-            return c
-    return None
+import emu_build
 
 
 SOURCES = ["gather_gemm.hip", "patch_gemm.hip", "wgrad_wide.hip", "fewc_conv.hip", "pool_norm.hip", "elementwise.hip"]
@@ -32,30 +22,16 @@ SOURCES = ["gather_gemm.hip", "patch_gemm.hip", "wgrad_wide.hip", "fewc_conv.hip
 
 @pytest.fixture(scope="module")
 def emu_binary(tmp_path_factory):
-    cc = _clang()
-    if not cc:
-        pytest.skip("no clang++ (the kernels use clang's vector extensions and __bf16)")
-    oracle_dir = os.path.join(ROOT, "oracle")
+    oracle_dir = os.path.join(emu_build.ROOT, "oracle")
     if not os.path.exists(os.path.join(oracle_dir, "liboracle.so")):
         pytest.skip("oracle/liboracle.so is not built (python -c 'import __graft_entry__ as g; g.build()')")
-    d = tmp_path_factory.mktemp("emu")
-    flags = ["-std=c++17", "-O1", "-x", "c++", "-I", os.path.join(HERE, "emu"), "-I", os.path.join(ROOT, "convnet_amd", "csrc"), "-Wno-everything"]
-    jobs = [(os.path.join(ROOT, "convnet_amd", "csrc", f), str(d / (f + ".o"))) for f in SOURCES] + [(os.path.join(HERE, "emu", "emu_main.cc"), str(d / "emu_main.o"))]
-    procs = [subprocess.Popen([cc, *flags, "-c", src, "-o", obj], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for src, obj in jobs]
-    for p, (src, _) in zip(procs, jobs):
-        out, _ = p.communicate()
-        assert p.returncode == 0, src + "\n" + out
-    exe = d / "emu_main"
-    subprocess.run([cc, *[o for _, o in jobs], "-o", str(exe), "-L", oracle_dir, "-loracle", "-Wl,-rpath," + oracle_dir], check=True)
-    return str(exe)
+    return emu_build.build(tmp_path_factory.mktemp("emu"), SOURCES, "emu_main.cc", "the kernels use clang's vector extensions and __bf16",
+                           link_args=["-L", oracle_dir, "-loracle", "-Wl,-rpath," + oracle_dir])
 
 
 def test_wide_kernels_run_correctly_in_emulation(emu_binary):
     which = "all" if os.environ.get("CONVNET_EMU_ALL") else "quick"
-    r = subprocess.run([emu_binary, which], capture_output=True, text=True, timeout=1200)
-    lines = r.stdout.strip().splitlines()
-    print(r.stdout)
-    assert r.returncode == 0 and lines and lines[-1] == "ALL PASSED", r.stdout + r.stderr
+    lines = emu_build.run(emu_binary, which, timeout=1200)
     # the calibration cases and both new kernels really ran
     assert any(l.startswith("PASS abi convUp") for l in lines) and any(l.startswith("PASS abi convOutpBias") for l in lines)
     assert any(l.startswith("PASS gpp(raw)") for l in lines) and any(l.startswith("PASS gpw fprop") for l in lines)
@@ -67,25 +43,22 @@ def test_wide_kernels_run_correctly_in_emulation(emu_binary):
 def test_wide_wgrad_kernel_single_block_epilogue_in_emulation(emu_binary):
     """one block per tile (forced: the launch policy splits the reduction at emulation sizes): scaleTargets, scaleOutput and the bias
     row in the kernel's own epilogue, through the 16-byte write-out and through the direct one (F % 4 != 0)"""
-    r = subprocess.run([emu_binary, "wgwfin"], capture_output=True, text=True, timeout=1200)
-    lines = r.stdout.strip().splitlines()
-    assert r.returncode == 0 and lines[-1] == "ALL PASSED" and sum("splits=1 " in l and l.startswith("PASS wgw") for l in lines) == 2, r.stdout + r.stderr
+    lines = emu_build.run(emu_binary, "wgwfin", timeout=1200)
+    assert sum("splits=1 " in l and l.startswith("PASS wgw") for l in lines) == 2, lines
 
 
 def test_wide_patch_kernel_tail_split_in_emulation(emu_binary):
     """11 tiles on an 8-slot "chip": the last round's three tiles are cut into three K-ranges (the kernel's tail-split branch, its raw
     partial tiles, gpw_tail_fix_kernel) — forced by the harness, the cost model never picks it at emulation sizes"""
-    r = subprocess.run([emu_binary, "gpwtail"], capture_output=True, text=True, timeout=1200)
-    lines = r.stdout.strip().splitlines()
-    assert r.returncode == 0 and lines[-1] == "ALL PASSED" and "tail_splits=3" in lines[0], r.stdout + r.stderr
+    lines = emu_build.run(emu_binary, "gpwtail", timeout=1200)
+    assert "tail_splits=3" in lines[0], lines
 
 
 def test_group_patch_kernel_tail_split_in_emulation(emu_binary):
     """gpv_kernel (5 x 5 stride 2: superchunks of three and two chunks): 13 tiles on an 8-slot "chip", the last round's five tiles cut
     into three K-ranges whose borders fall inside a tap row's groups"""
-    r = subprocess.run([emu_binary, "gpvtail"], capture_output=True, text=True, timeout=1200)
-    lines = r.stdout.strip().splitlines()
-    assert r.returncode == 0 and lines[-1] == "ALL PASSED" and "tail_splits=3" in lines[0], r.stdout + r.stderr
+    lines = emu_build.run(emu_binary, "gpvtail", timeout=1200)
+    assert "tail_splits=3" in lines[0], lines
 
 
 def test_split_builds_error_against_double_in_emulation(emu_binary):
@@ -94,8 +67,5 @@ def test_split_builds_error_against_double_in_emulation(emu_binary):
     NN / TN products) on N(0,1) data and on data whose terms cancel in pairs along the axis each product reduces over, against double:
     max |out - exact| / sum|ab| within tests/emu/prec.h's bounds.  The 1e-4 parity cases above cannot tell a dropped cross term from
     rounding; these can (the bounds' calibration against the m*m-dropped and zero-l-plane mutants is in tests/emu/prec.h)."""
-    r = subprocess.run([emu_binary, "prec"], capture_output=True, text=True, timeout=1200)
-    lines = r.stdout.strip().splitlines()
-    print(r.stdout)
-    assert r.returncode == 0 and lines and lines[-1] == "ALL PASSED", r.stdout + r.stderr
-    assert sum(l.startswith("PASS prec") for l in lines) == 32, r.stdout
+    lines = emu_build.run(emu_binary, "prec", timeout=1200)
+    assert sum(l.startswith("PASS prec") for l in lines) == 32, lines

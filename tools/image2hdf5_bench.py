@@ -42,8 +42,7 @@ def leg_a(args, f, out):
     dh.DiskAccess()
     half = dh.disk_.halves_["input"]
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()     # noqa: E731
-    data = dev(dh.host_[0]["input"][:half.bytes_used_[0]])
-    table, taps, cases = dev(half.image_table_[0][:half.images_used_[0]]), dev(half.taps_[0][:half.taps_used_[0]]), dev(half.case_table_[0])
+    data, table, taps, cases = (dev(a) for a in half.Used(0))
     dh.close()
     floats = DataHandler(config(f, N), raw_chunks=False)                # the same crops, resized on the host
     want = np.asarray(floats.DiskAccess()["input"]).astype(np.uint8)

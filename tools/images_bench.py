@@ -88,8 +88,7 @@ def leg_a(args, f, out):
     dh.DiskAccess()
     half = dh.disk_.halves_["input"]
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()     # noqa: E731
-    data = dev(dh.host_[0]["input"][:half.bytes_used_[0]])
-    table, taps, cases = dev(half.image_table_[0][:half.images_used_[0]]), dev(half.taps_[0][:half.taps_used_[0]]), dev(half.case_table_[0])
+    data, table, taps, cases = (dev(a) for a in half.Used(0))
     source_pixels = int(sum(int(w) * int(h) for _, w, h, _, _, _ in half.image_table_[0][:N].tolist()))
     dh.close()
     floats = DataHandler(config(f, N), raw_chunks=False)                # the same crops, resized on the host: kept as bytes
@@ -155,7 +154,7 @@ def leg_b_c(args, f, out):
                 ts.append((time.perf_counter() - t0) * 1e3)
             half = dh.disk_.halves_["input"]
             if raw:
-                nbytes = half.bytes_used_[0] + 48 * half.images_used_[0] + 12 * half.taps_used_[0] + 16 * chunk
+                nbytes = sum(a.nbytes for a in half.Used(0))
             else:
                 nbytes = dh.host_[0]["input"].nbytes
             key = name + ("_avg10" if avg10 else "")
