@@ -17,42 +17,15 @@
 namespace chip {
 alignas(16) float smem[40960 + 4096];   // 160 KB + slack: the block's LDS
 alignas(16) float rn_smem[40960];          // pool_norm.hip names its dynamic LDS array differently
-hipStream_t stream() { return nullptr; }
-static std::vector<char> g_ws[3];
-static void* arena(int i, size_t bytes) {
-  if (g_ws[i].size() < bytes + 64) g_ws[i].resize(bytes + 64);
-  return (void*)(((uintptr_t)g_ws[i].data() + 63) & ~(uintptr_t)63);
-}
-void* workspace(size_t b) { return arena(0, b); }
-void* workspace_aux(size_t b) { return arena(1, b); }
-void* workspace_planes(size_t b) { return arena(2, b); }
-const float* zero_page() {
-  alignas(64) static float z[64] = {};
-  z[32] = z[33] = z[34] = z[35] = 1.f;
-  return z;
-}
-int matrix_path() { return 1; }
-void set_last_error(const char*) {}
-const char* g_last_kernel = "";
-void note_kernel(const char* name, double, int, int) { g_last_kernel = name; }
-KernelTimer::KernelTimer(const char*, const char*, double, double, double) : slot(-1) {}
-KernelTimer::~KernelTimer() {}
-// deferred epilogues (state.hip): off here — every entry launches when it is called
-bool defer_begin(int, void (*)(PendingOp&)) { return false; }
-PendingOp& pending() {
-  static PendingOp p = {};
-  return p;
-}
-void flush_pending() {}
-long g_absorbed = 0;
 }  // namespace chip
 
-extern "C" int copy_on_device(cudamat* src, cudamat* dst) {   // state.hip's
-  std::memcpy(dst->data_device, src->data_device, sizeof(float) * (size_t)src->size[0] * src->size[1]);
-  return 0;
-}
-
 using namespace chip;
+
+static std::string last_kernel() {   // the kernel the last conv / dot call reported (state.hip)
+  ConvnetHipKernelInfo info;
+  convnet_hip_last_kernel_info(&info);
+  return info.name;
+}
 
 struct Geo {
   int N, C, H, W, F, Ky, Kx, sy, sx, pad;   // pad >= 0; the library's ConvDesc carries it negated
@@ -248,7 +221,7 @@ static void abi_conv_case(const Geo& g, const char* which, int patch_mode = 0) {
             ref[((size_t)(f * My + oy) * Mx + ox) * g.N + n] = s;
           }
     convUp(&mx, &mw, &my, &sx, &sw, &sy, desc(g), 0.f);
-    verdict("abi convUp " + gname(g) + " [" + chip::g_last_kernel + "]", rel_err(y, ref), true);
+    verdict("abi convUp " + gname(g) + " [" + last_kernel() + "]", rel_err(y, ref), true);
   } else if (what == "down") {
     std::vector<double> ref((size_t)g.C * g.H * g.W * g.N);
     for (int c = 0; c < g.C; ++c)
@@ -268,7 +241,7 @@ static void abi_conv_case(const Geo& g, const char* which, int patch_mode = 0) {
             ref[((size_t)(c * g.H + iy) * g.W + ix) * g.N + n] = s;
           }
     convDown(&my, &mw, &mx, &sy, &sw, &sx, desc(g), 0.f);
-    verdict("abi convDown " + gname(g) + " [" + chip::g_last_kernel + "]", rel_err(x, ref), patch_mode == 0 || std::string(chip::g_last_kernel).find("gpw") == 0);
+    verdict("abi convDown " + gname(g) + " [" + last_kernel() + "]", rel_err(x, ref), patch_mode == 0 || last_kernel().find("gpw") == 0);
   } else {   // "outp": weight gradients + bias gradient
     std::vector<double> ref((size_t)g.F * K), refb(g.F);
     for (int f = 0; f < g.F; ++f) {
@@ -420,6 +393,38 @@ static void sgd_case(int rows, int cols) {
   oracle_sgd_step(g2.data(), p2.data(), h2.data(), rows, cols, 0.0005f, 0.f, 0.01f, 0.9f, 0.f, 0.f);
   verdict("abi sgd_momentum_step " + std::to_string(rows) + " x " + std::to_string(cols), std::max(rel_err_f(p, p2.data(), n), rel_err_f(h, h2.data(), n)), rc == 0);
 }
+// The deferred epilogues of state.hip: with the switch on, convUp is parked, add_row_vec of the shared bias and lower_bound_scalar(0)
+// join its fused epilogue (two calls absorbed), and the result is that of the three eager calls, bit for bit
+static void deferred_case(const Geo& g) {
+  convnet_hip_set_patch_mode(0);
+  const int My = g.My(), Mx = g.Mx(), K = g.C * g.Ky * g.Kx;
+  const size_t n = (size_t)g.F * My * Mx * g.N;
+  auto xv = rnd((size_t)g.C * g.H * g.W * g.N, 81), wv = rnd((size_t)g.F * K, 82), bv = rnd(g.F, 83);
+  cudamat mx = mat(al16(xv), g.N, g.H * g.W * g.C), mw = mat(al16(wv), g.F, K), mb = mat(al16(bv), 1, g.F);
+  Shape4D sx{{g.N, g.W, g.H, g.C}}, sw{{g.F, g.Kx, g.Ky, g.C}}, sy{{g.N, Mx, My, g.F}};
+  std::vector<float> out[2] = {rnd(n, 84), rnd(n, 84)};
+  long absorbed[2];
+  int rc = 0;
+  for (int on = 0; on < 2; ++on) {
+    float* y = al16(out[on]);
+    cudamat my = mat(y, g.N, My * Mx * g.F), rows = mat(y, g.N * My * Mx, g.F);   // (the host's reshape for the shared bias)
+    convnet_hip_set_deferred_epilogues(on);
+    const long before = convnet_hip_deferred_absorbed();
+    convUp(&mx, &mw, &my, &sx, &sw, &sy, desc(g), 0.f);
+    rc |= add_row_vec(&rows, &mb, &rows) | lower_bound_scalar(&rows, 0.f, &rows);
+    convnet_hip_set_deferred_epilogues(0);   // (launches whatever is still parked)
+    absorbed[on] = convnet_hip_deferred_absorbed() - before;
+  }
+  size_t differing = 0, positive = 0;   // (positive: the bias and the ReLU left something of both kinds)
+  for (size_t i = 0; i < n; ++i) {
+    differing += std::memcmp(al16(out[0]) + i, al16(out[1]) + i, 4) != 0;
+    positive += al16(out[0])[i] > 0.f;
+  }
+  const bool ok = rc == 0 && differing == 0 && absorbed[0] == 0 && absorbed[1] == 2 && positive > 0 && positive < n;
+  std::printf("%s abi deferred convUp + add_row_vec + lower_bound_scalar %s: absorbed %ld eager, %ld deferred; %zu of %zu differ\n", ok ? "PASS" : "FAIL",
+              gname(g).c_str(), absorbed[0], absorbed[1], differing, n);
+  if (!ok) ++g_fail;
+}
 
 // ---- precision mode: error against double in units of 2^-24 of sum|ab| (prec.h), N(0,1) data and pairwise cancellation -----------------
 // axis: what the product reduces over and the cancellation pairs — "channels" / "taps" (C = 3: x columns and filter taps, stride and
@@ -514,7 +519,7 @@ static void prec_conv(const Geo& g, const char* which, const char* axis, int pat
       out = cat.data();
     }
     const std::string name = "abi conv" + what + " " + gname(g) + " mode " + std::to_string(patch_mode) + "/" + std::to_string(wgrad_tile) + " [" +
-                             chip::g_last_kernel + "]";
+                             last_kernel() + "]";
     if (!prec::verdict(name.c_str(), fam ? "cancellation" : "normal", prec::err(out, ref, mag))) ++g_fail;
   }
 }
@@ -547,7 +552,7 @@ static void prec_dot(int N, int D, int F) {
       else if (form == 1) { cudamat a = mat(dy, N, F), b = mat(w, F, D); rc = dot(&a, &b, &mt, 0.f, 1.f); }
       else { cudamat a = mat(dy, N, F), b = mat(x, N, D); a.is_trans = 1; rc = dot(&a, &b, &mt, 0.f, 1.f); }
       const std::string name = std::string("abi dot ") + (form == 0 ? "NT" : form == 1 ? "NN" : "TN") + " N" + std::to_string(N) + " D" + std::to_string(D) +
-                               " F" + std::to_string(F) + " [" + chip::g_last_kernel + "]";
+                               " F" + std::to_string(F) + " [" + last_kernel() + "]";
       if (rc || !prec::verdict(name.c_str(), fam ? "cancellation" : "normal", prec::err(t, ref, mag))) ++g_fail;
     }
   }
@@ -556,6 +561,7 @@ static void prec_dot(int N, int D, int F) {
 int main(int argc, char** argv) {
   const std::string what = argc > 1 ? argv[1] : "quick";   // abi | gpp | gpw | gpv | gpvtail | gpwtail | wgw | wgwvar | wgwfin | quick (a subset of each, ~1 minute) | all
   const bool all = what == "all", quick = what == "quick";   // ("all" does not include gpwtail: its 8-slot chip is a process-wide setting)
+  convnet_hip_set_matrix_path(1);   // the split builds: the product's default kernels
   if (what == "prec") {   // every split build emulation runs, N(0,1) and pairwise-cancelling data, error vs double per sum|ab|
     prec_conv(Geo{64, 3, 16, 16, 96, 7, 7, 2, 2, 2}, "up", "taps", 0, 0);        // gfc_kernel
     prec_conv(Geo{48, 3, 16, 16, 96, 7, 7, 2, 2, 2}, "up", "taps", 0, 0);        // generic-k ggp_kernel<1,4,3,64,split,pre>
@@ -574,6 +580,7 @@ int main(int argc, char** argv) {
     abi_conv_case(Geo{64, 16, 9, 9, 128, 3, 3, 1, 1, 1}, "up");      // ggp_kernel<2,2,2,128>, pre-split filter planes
     abi_conv_case(Geo{32, 16, 9, 9, 128, 3, 3, 1, 1, 1}, "outp");    // wg_kernel<2,2,2,2>, K = 144: bias row in the second k tile
     abi_conv_case(Geo{64, 3, 15, 15, 96, 7, 7, 2, 2, 1}, "up");      // conv1 type: gfc_kernel (patch-resident, filter bank in LDS), 12 tiles on 4 blocks
+    deferred_case(Geo{32, 16, 9, 9, 128, 3, 3, 1, 1, 1});            // the parked convUp takes the bias and the ReLU of the two calls behind it
     if (!quick) {
       abi_conv_case(Geo{48, 3, 15, 15, 96, 7, 7, 2, 2, 1}, "up");      // conv1 type, N % 32 != 0: generic-k order on ggp_kernel<1,4,3,64>
       abi_conv_case(Geo{32, 3, 27, 27, 80, 7, 7, 2, 2, 1}, "up");      // conv1 type: gfc_kernel, two column groups (12 = 8 + 4 pixels), 80 of 96 rows, 24 tiles on 4 blocks

@@ -354,7 +354,18 @@ inline size_t max(size_t a, size_t b) { return a > b ? a : b; }
 inline unsigned long long min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
 inline unsigned long long max(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
 enum hipMemcpyKind { hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2, hipMemcpyDeviceToDevice = 3 };
-inline hipError_t hipMalloc(void** p, size_t n) { *p = std::malloc(n ? n : 1); return hipSuccess; }
+inline hipError_t hipMalloc(void** p, size_t n) { return posix_memalign(p, 256, n ? n : 1); }   // aligned as the device's, exactly n bytes
+inline hipError_t hipFree(void* p) { std::free(p); return hipSuccess; }
+// what state.hip needs beyond the kernels' files: one device, and events that record nothing
+typedef void* hipEvent_t;
+enum { hipEventDisableTiming = 2 };
+inline hipError_t hipSetDevice(int) { return hipSuccess; }
+inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
+inline hipError_t hipEventCreate(hipEvent_t* e) { *e = nullptr; return hipSuccess; }
+inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = nullptr; return hipSuccess; }
+inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
+inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
+inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.f; return hipSuccess; }
 inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { std::memcpy(d, s, n); return hipSuccess; }
 inline hipError_t hipMemset(void* d, int v, size_t n) { std::memset(d, v, n); return hipSuccess; }
 inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { std::memcpy(d, s, n); return hipSuccess; }

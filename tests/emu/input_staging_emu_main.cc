@@ -10,7 +10,7 @@
 //   the 64-column tile — for 1, 5, 37, 64 and 68 cases (a narrow tile, a wide one that is no multiple of 4, a full one on the 16-byte
 //   store path, a second tile), all four builds; offsets from 0 to the maximum, flip values on both sides of 0.5, repeated columns.
 // * the entries' error codes.
-// Add -fsanitize=address to both compiles and the link to have the buffer bounds checked.  Prints one line per case; exit status 0 only
+// Add -fsanitize=address to every compile and the link to have the buffer bounds checked.  Prints one line per case; exit status 0 only
 // if all pass.  tests/test_input_staging_emulated.py builds and runs it.
 #include "input_staging_emu_prelude.h"
 #include <algorithm>
@@ -20,11 +20,6 @@
 #include <random>
 #include <vector>
 #include "common.h"
-namespace chip {
-hipStream_t stream() { return nullptr; }
-KernelTimer::KernelTimer(const char*, const char*, double, double, double) : slot(-1) {}
-KernelTimer::~KernelTimer() {}
-}
 struct Tap { int s, a0, a1; };
 static std::vector<Tap> mk_taps(int ssize, int dsize) {
   std::vector<Tap> t;

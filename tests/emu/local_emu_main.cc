@@ -11,35 +11,6 @@
 
 #include "../../convnet_amd/csrc/gather_gemm.h"
 
-namespace chip {
-int g_path = 0;
-hipStream_t stream() { return nullptr; }
-static std::vector<char> g_ws[3];
-static void* arena(int i, size_t bytes) {
-  if (g_ws[i].size() < bytes + 64) g_ws[i].resize(bytes + 64);
-  return (void*)(((uintptr_t)g_ws[i].data() + 63) & ~(uintptr_t)63);
-}
-void* workspace(size_t b) { return arena(0, b); }
-void* workspace_aux(size_t b) { return arena(1, b); }
-void* workspace_planes(size_t b) { return arena(2, b); }
-const float* zero_page() {
-  alignas(64) static float z[64] = {};
-  return z;
-}
-int matrix_path() { return g_path; }
-void set_last_error(const char*) {}
-void note_kernel(const char*, double, int, int) {}
-KernelTimer::KernelTimer(const char*, const char*, double, double, double) : slot(-1) {}
-KernelTimer::~KernelTimer() {}
-bool defer_begin(int, void (*)(PendingOp&)) { return false; }
-PendingOp& pending() {
-  static PendingOp p = {};
-  return p;
-}
-void flush_pending() {}
-long g_absorbed = 0;
-}  // namespace chip
-
 struct G {
   int N, C, H, W, F, Ky, Kx, sy, sx, py, px;   // py / px >= 0 (pbtxt padding)
   int My() const { return (H + 2 * py - Ky) / sy + 1; }
@@ -65,7 +36,7 @@ static double rel(const std::vector<float>& a, const std::vector<double>& b) {
 }
 
 static bool run(const G& g, int path, float st, float so) {
-  chip::g_path = path;
+  convnet_hip_set_matrix_path(path);
   const int My = g.My(), Mx = g.Mx(), M = My * Mx, K = g.C * g.Ky * g.Kx;
   std::mt19937 rng(g.N * 131 + g.C * 7 + path);
   std::normal_distribution<float> nd;

@@ -21,13 +21,14 @@ def clang():
 
 
 def build(out_dir, kernels, main, why, extras=None, link_args=()):
-    """Compiles ``kernels`` (files of convnet_amd/csrc) and ``main`` (a file of tests/emu), all at once, and links them in ``out_dir``;
-    returns the program's path.  ``extras``: file name -> further compile arguments; ``link_args`` go behind the objects.  Without a
-    clang++ the test is skipped; ``why`` says what the kernels need it for."""
+    """Compiles ``kernels`` (files of convnet_amd/csrc), the library's own state.hip (stream, arenas, deferred epilogues, kernel report:
+    no program has a stand-in for it) and ``main`` (a file of tests/emu), all at once, and links them in ``out_dir``; returns the
+    program's path.  ``extras``: file name -> further compile arguments; ``link_args`` go behind the objects.  Without a clang++ the
+    test is skipped; ``why`` says what the kernels need it for."""
     cc = clang()
     if not cc:
         pytest.skip(f"no clang++ ({why})")
-    jobs = [(os.path.join(CSRC, f), os.path.join(str(out_dir), f + ".o")) for f in kernels]
+    jobs = [(os.path.join(CSRC, f), os.path.join(str(out_dir), f + ".o")) for f in ["state.hip", *kernels]]
     jobs.append((os.path.join(EMU, main), os.path.join(str(out_dir), main + ".o")))
     procs = [subprocess.Popen([cc, *FLAGS, *(extras or {}).get(os.path.basename(src), []), "-c", src, "-o", obj], stdout=subprocess.PIPE,
                               stderr=subprocess.STDOUT, text=True) for src, obj in jobs]

@@ -38,6 +38,8 @@ def test_wide_kernels_run_correctly_in_emulation(emu_binary):
     assert any(l.startswith("PASS gpw dgrad") for l in lines) and any(l.startswith("PASS wgw wgrad") for l in lines)
     # gpv_kernel: conv2's forward form and its four stride classes (the latter through convDown)
     assert any(l.startswith("PASS gpv fprop") for l in lines) and any(l.startswith("PASS abi convDown") and "k5 s2" in l and "gpw_kernel(dgrad)" in l for l in lines)
+    # the library's own state.hip is what runs: a parked convUp absorbed the two element-wise calls behind it, same bits as eager
+    assert any(l.startswith("PASS abi deferred convUp") and "2 deferred; 0 of" in l for l in lines)
 
 
 def test_wide_wgrad_kernel_single_block_epilogue_in_emulation(emu_binary):

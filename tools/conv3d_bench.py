@@ -5,8 +5,8 @@ the library's per-launch timer, summed over the call's launches; median of `--re
   * the 3-D entry of this library as it ships, and the same entry with its batched forms off (CONVNET_CONV3D_BATCH=0: no filter-bank
     preparation shared between frames, dW accumulated frame by frame), and
   * the reference's form — the loop of 2-D entries over frame slices, with its Scale pass for dgrad (cudamat_conv3d_gemm.cu) — on ANOTHER
-    build of the library, given by --baseline-lib (a file name under convnet_amd/lib or a path; tools/build_prev_lib.sh builds the parent
-    commit's).  Each leg runs in a child process of this call (the library is chosen at import, CONVNET_HIP_LIB), so both are measured on
+    build of the library, given by --baseline-lib (a file name under convnet_amd/lib or a path; python -m convnet_amd.build --rev REV builds the
+    parent commit's).  Each leg runs in a child process of this call (the library is chosen at import, CONVNET_HIP_LIB), so both are measured on
     the same GPU minutes apart; boxes differ by +-4 %, so only pairs of one call compare.
 Then the pooling kernels over time (bytes needed / time against 6.3 TB/s) and the video_small training step at batch 32 on path 1
 (images/s, share of kernel time per kernel family).
