@@ -26,7 +26,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib")
 OUT = os.path.join(LIB, "libconvnet_hip.so")
-SOURCES = ["state.hip", "gather_gemm.hip", "patch_gemm.hip", "wgrad_wide.hip", "fewc_conv.hip", "local_conv.hip", "conv3d.hip", "batch_norm.hip", "pool_norm.hip", "elementwise.hip", "input_staging.hip", "dataset_moments.hip", "feature_rows.hip", "comm.hip", "rccl_abi_check.hip", "probe.hip"]
+SOURCES = ["state.hip", "gather_gemm.hip", "patch_gemm.hip", "wgrad_wide.hip", "fewc_conv.hip", "local_conv.hip", "conv3d.hip", "batch_norm.hip", "pool_norm.hip", "resample.hip", "elementwise.hip", "input_staging.hip", "dataset_moments.hip", "feature_rows.hip", "comm.hip", "rccl_abi_check.hip", "probe.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-comment", "-Wno-inline-asm"]
 # Per-file additions.  patch_gemm.hip: the SLP vectoriser packs the split's fp32 subtractions into v_pk_add_f32 (+ the v_mov / s_nop
 # that feed them) — fewer instructions on paper, but beside MFMAs a packed fp32 op costs more issue time than the two plain ones

@@ -24,7 +24,8 @@ from typing import Callable, NamedTuple, Optional
 import torch
 
 from . import pbtxt
-from .edge import AvgPoolEdge, ConvEdge, Edge, EdgeWithWeight, FCEdge, LocalEdge, MaxPoolEdge, ResponseNormEdge
+from .edge import (AvgPoolEdge, ConvEdge, Edge, EdgeWithWeight, FCEdge, LocalEdge, MaxPoolEdge, ResponseNormEdge, RGBToYUVEdge,
+                   UpSampleEdge)
 from .layer import Layer, LinearLayer, LogisticLayer, ReLULayer, SoftmaxDistLayer, SoftmaxLayer
 from .matrix import Matrix
 from .optimizer import RunFusedSteps
@@ -162,6 +163,7 @@ class ConvNet(TrainLoopMixin):
             if l.UseBatchNormalization():
                 self._check_batch_norm(l)
             self._check_slices(l)
+            self._check_resample_edges(l)
             if not l.incoming_edge_:
                 self.input_layers_.append(l)
                 self.data_layers_.append(l)
@@ -270,6 +272,23 @@ class ConvNet(TrainLoopMixin):
             for e in l.incoming_edge_:
                 if e.GetSourceSliceName():
                     raise SystemExit(f"batch_normalize on layer {name}: not supported on a layer fed from a slice (edge {e.GetName()})")
+
+    @staticmethod
+    def _check_resample_edges(l):
+        """What an UPSAMPLE or RGBTOYUV edge out of layer l cannot be; each stops with its reason."""
+        for e in l.outgoing_edge_:
+            if isinstance(e, RGBToYUVEdge) and l.incoming_edge_ and not e.IsBackPropBlocked():
+                # (an input layer takes no derivative, src/convnet.cc:370; nor does anything behind a blocked edge)
+                raise SystemExit(f"Error: Edge {e.GetName()}: RGBTOYUV has no backward pass (\"RGBtoYUV backprop Not implemented.\"), and its "
+                                 f"source layer {l.GetName()} needs a derivative: read an input layer, or set block_backprop on the edge.")
+            if isinstance(e, UpSampleEdge) and l.incoming_edge_ and not e.IsBackPropBlocked():
+                others = [f.GetName() for f in l.outgoing_edge_
+                          if f is not e and not f.IsBackPropBlocked() and f.GetSourceSliceName() == e.GetSourceSliceName()]
+                if others:
+                    # UpSampleEdge::ComputeDown ignores `overwrite` (src/upsample_edge.cc:30-34)
+                    raise SystemExit(f"Error: Edge {e.GetName()}: the backward pass of UPSAMPLE overwrites the derivative of its source layer "
+                                     f"{l.GetName()}, which edge {others[0]} also back-propagates into: its part would be lost.  Give the "
+                                     "UPSAMPLE edge a source layer of its own, or set block_backprop on one of the two.")
 
     @staticmethod
     def _check_batch_norm(l):

@@ -1,8 +1,8 @@
 """Edges (operators) — mirror of src/edge.{h,cc}, edge_with_weight.cc, conv_edge.cc, fc_edge.cc,
-maxpool_edge.cc, avgpool_edge.cc, response_norm_edge.cc: same class names, same
+maxpool_edge.cc, avgpool_edge.cc, response_norm_edge.cc, upsample_edge.cc, rgb_to_yuv_edge.cc: same class names, same
 ComputeUp / ComputeDown / ComputeOuter / UpdateWeights contract, same parameter slicing.
 
-Up-down-sample / RGB->YUV edges are out of hot-path scope.
+DOWNSAMPLE is refused: the reference's class is dead (ChooseEdgeClass has the reason).
 ``fused`` selects the library's fused entry points (conv+bias+ReLU epilogue, one-pass bias
 gradient); the unfused path issues exactly the reference's Matrix-call sequence.  What an edge class can
 fuse it says itself (``CanFuseUp``, ``can_fuse_mask``); which of it a net uses is ConvNet's per-layer plan.
@@ -32,7 +32,15 @@ class Edge:
     def ChooseEdgeClass(edge_config):
         # src/edge.cc:19-66
         table = {"FC": FCEdge, "CONVOLUTIONAL": ConvEdge, "MAXPOOL": MaxPoolEdge, "AVERAGE_POOL": AvgPoolEdge,
-                 "RESPONSE_NORM": ResponseNormEdge, "CONV_ONETOONE": ConvOneToOneEdge, "LOCAL": LocalEdge}
+                 "RESPONSE_NORM": ResponseNormEdge, "CONV_ONETOONE": ConvOneToOneEdge, "LOCAL": LocalEdge,
+                 "UPSAMPLE": UpSampleEdge, "RGBTOYUV": RGBToYUVEdge}
+        if edge_config.edge_type == "DOWNSAMPLE":
+            # src/downsample_edge.cc:18-23 MULTIPLIES the image size by the factor where it must divide: the destination layer gets the
+            # wrong size and the pool reads outside the image.  The edge is dead in the reference; there is nothing to mirror
+            raise SystemExit(f"Error: Edge {edge_config.source}:{edge_config.dest}: edge_type DOWNSAMPLE is not supported: the reference "
+                             "sizes its destination as image_size * sample_factor and reads outside the image.  Use AVERAGE_POOL with "
+                             f"kernel_size = stride = sample_factor ({edge_config.sample_factor}): the same forward pass with a correct "
+                             "backward pass.")
         if edge_config.edge_type not in table:
             raise SystemExit(f"Error: Undefined edge type {edge_config.edge_type} (out of hot-path scope).")
         return table[edge_config.edge_type](edge_config)
@@ -881,3 +889,65 @@ class ResponseNormEdge(Edge):
             return
         Matrix.ConvResponseNormCrossMapUndo(deriv_output, input, output, deriv_input, self.num_input_channels_,
                                             self.num_filters_response_norm_, self.add_scale_, self.pow_scale_, self.blocked_)
+
+
+class UpSampleEdge(Edge):
+    """src/upsample_edge.{h,cc}: every pixel of the source map is repeated sample_factor x sample_factor times (include/convnet_hip.h:
+    UpSampleGemm).  With ``overwrite`` false the repeated map is ADDED to the destination, so an upsampled coarse map and a convolution
+    can sum into one layer.
+    ComputeDown is the reference's: the MEAN over each factor x factor block of derivatives, written over whatever ``deriv_input`` held —
+    ``overwrite`` is ignored.  The adjoint of the replication would be the sum, so the gradients below this edge are 1 / factor^2 of the
+    true ones (NOTES.md; the reference's own GradChecker says so), and a second back-propagated edge out of the same source layer would
+    lose its derivative: ConvNet.BuildNet refuses that net."""
+
+    def __init__(self, c):
+        super().__init__(c)
+        self.sample_factor_ = c.sample_factor
+        if self.sample_factor_ < 1:
+            raise SystemExit(f"Error: Edge {self.name_}: sample_factor {self.sample_factor_} is not supported on an UPSAMPLE edge: "
+                             "it must be at least 1.")
+
+    def SetImageSize(self, y, x, t):
+        # src/upsample_edge.cc:18-23
+        super().SetImageSize(y, x, t)
+        if t > 1:
+            raise SystemExit(f"Error: Edge {self.name_}: UPSAMPLE is not supported on a layer with image_size_t > 1 ({t} frames)")
+        self.num_modules_y_, self.num_modules_x_, self.num_modules_t_ = y * self.sample_factor_, x * self.sample_factor_, t
+
+    def GetDescription(self):
+        # src/upsample_edge.cc:8-16 (two blanks behind the name and a trailing newline, as the reference writes them)
+        return (f"{self.name_}  Upsample factor {self.sample_factor_} Layer: {self.image_size_y_}-{self.image_size_x_}-"
+                f"{self.num_input_channels_} : {self.num_modules_y_}-{self.num_modules_x_}-{self.num_output_channels_}\n")
+
+    def ComputeUp(self, input, output, overwrite, train=True, fuse_relu=None):
+        Matrix.ConvUpSample(input, output, self.sample_factor_, 0 if overwrite else 1)
+
+    def ComputeDown(self, deriv_output, input, output, deriv_input, overwrite, fuse_mask=None):
+        assert fuse_mask is None
+        Matrix.ConvDownSample(deriv_output, deriv_input, self.sample_factor_)
+
+
+class RGBToYUVEdge(Edge):
+    """src/rgb_to_yuv_edge.{h,cc}: the colour transform of include/convnet_hip.h (RGBToYUV) on a 3-channel source.  The reference class
+    never sets num_modules, so its destination comes out 1 x 1; here the destination has the source's size.  No backward pass."""
+
+    def SetImageSize(self, y, x, t):
+        super().SetImageSize(y, x, t)
+        if t > 1:
+            raise SystemExit(f"Error: Edge {self.name_}: RGBTOYUV is not supported on a layer with image_size_t > 1 ({t} frames)")
+        if self.num_input_channels_ != 3 or self.num_output_channels_ != 3:
+            raise SystemExit(f"Error: Edge {self.name_}: RGBTOYUV needs 3 channels in and out: num_channels is {self.num_input_channels_} "
+                             f"on its source and {self.num_output_channels_} on its destination.")
+        self.num_modules_y_, self.num_modules_x_, self.num_modules_t_ = y, x, t
+
+    def GetDescription(self):
+        return f"{self.name_} RGB to YUV {self.image_size_y_}-{self.image_size_x_}"
+
+    def ComputeUp(self, input, output, overwrite, train=True, fuse_relu=None):
+        if not overwrite:
+            raise SystemExit(f"Error: Edge {self.name_}: some other edge is writing to this RGBTOYUV edge's destination as well: "
+                             "the transform overwrites it.")
+        Matrix.ConvRGBToYUV(input, output)
+
+    def ComputeDown(self, deriv_output, input, output, deriv_input, overwrite, fuse_mask=None):
+        raise SystemExit("RGBtoYUV backprop Not implemented.")   # src/rgb_to_yuv_edge.cc:17-22

@@ -653,6 +653,36 @@ class Matrix:
                             conv_desc, float(scale_targets))
 
     @staticmethod
+    def _check_resample(entry, small, large, factor):
+        """The guard of the resampling entries, which return nothing (include/convnet_hip.h: a refused call only leaves a text):
+        ``large`` must be ``factor`` x ``small`` on both axes, with its images and channels."""
+        (n, w, h, c), (ln, lw, lh, lc) = small.shape_.shape, large.shape_.shape
+        if factor < 1 or (ln, lw, lh, lc) != (n, w * factor, h * factor, c):
+            raise MatrixError(f"Error: {entry} : shape {(ln, lw, lh, lc)} is not factor {factor} x shape {(n, w, h, c)}")
+        if (small.GetRows(), small.GetCols(), large.GetRows(), large.GetCols()) != (n, w * h * c, n, lw * lh * c):
+            raise MatrixError(f"Error: {entry} : a matrix does not have the size of its shape")
+
+    @staticmethod
+    def ConvUpSample(input, output, factor, scale_targets):
+        # src/matrix.cc:992-1001
+        Matrix._check_resample("UpSampleGemm", input, output, int(factor))
+        lib.UpSampleGemm(input.GetMat(), output.GetMat(), ctypes.byref(input.shape_), ctypes.byref(output.shape_), int(factor), float(scale_targets))
+
+    @staticmethod
+    def ConvDownSample(input, output, factor):
+        # src/matrix.cc:1003-1011
+        Matrix._check_resample("DownSampleGemm", output, input, int(factor))
+        lib.DownSampleGemm(input.GetMat(), output.GetMat(), ctypes.byref(input.shape_), ctypes.byref(output.shape_), int(factor))
+
+    @staticmethod
+    def ConvRGBToYUV(input, output):
+        # src/matrix.cc:1013-1028 (there a (N * pixels, 3) x (3, 3) product with the same nine constants)
+        if (input.GetRows(), input.GetCols()) != (output.GetRows(), output.GetCols()) or input.GetCols() % 3 != 0:
+            raise MatrixError(f"Error: RGBToYUV : operands {(input.GetRows(), input.GetCols())} and {(output.GetRows(), output.GetCols())} "
+                              "must be equal in size with a column count divisible by 3")
+        lib.RGBToYUV(input.GetMat(), output.GetMat())
+
+    @staticmethod
     def ConvResponseNormCrossMap(input, output, numFilters, sizeF, addScale, powScale, blocked, relu=False):
         fn = lib.ResponseNormCrossMapRelu if relu else lib.ResponseNormCrossMapGemm
         fn(input.GetMat(), output.GetMat(), int(numFilters), int(sizeF), float(addScale), float(powScale), bool(blocked))

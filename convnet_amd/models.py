@@ -21,6 +21,10 @@ text so they can also be written to disk and fed to the reference's own binaries
                      with layer slices: grouped convolutions.
 * ``inception_small()`` — a small net with one module of three branches (1x1, 3x3, 5x5; as a stride-2 reduction module also a pooled
                      fourth) concatenated into one layer through ``dest_slice``.
+* ``conv_autoencoder()`` — a convolutional autoencoder: conv / max-pool encoder, conv / ``UPSAMPLE`` decoder, LINEAR output trained with
+                     SQUARED_ERROR against a target stream.
+* ``skip_sum_small()`` — a small net whose input goes through an ``RGBTOYUV`` edge and in which a coarse branch upsampled by 4 and a
+                     1x1 branch sum into one layer.
 tests/test_models.py checks the first two against the reference's files when they are mounted.
 """
 
@@ -388,6 +392,54 @@ def inception_small(image_size=12, num_classes=10, relu=True, pooled_branch=Fals
     if pooled_branch:
         s += _on(_pool("stem", "mix", 3, 2, 1, kind=kind), "", "pool")
     s += _pool("mix", "pool", 3, 2, kind=kind) + _fc("pool", "output", init_wt=init_wt, grad_check=gc)
+    return s
+
+
+def _upsample(src, dst, factor):
+    return f'edge {{\n  source: "{src}"\n  dest: "{dst}"\n  edge_type: UPSAMPLE\n  sample_factor: {factor}\n}}\n\n'
+
+
+_SQUARED_ERROR = "  loss_function: SQUARED_ERROR\n  performance_metric: SQUARED_ERROR\n"
+
+
+def conv_autoencoder(image_size=32, grad_check=False, init_wt=1.0, relu=True, eps=0.0001):
+    """A convolutional autoencoder: 3 x S x S -> conv3p1/16 ReLU -> max2s2 -> conv3p1/32 ReLU -> max2s2 (S/4) -> conv3p1/32 -> UPSAMPLE 2
+    -> conv3p1/16 ReLU -> UPSAMPLE 2 -> conv3p1 into a LINEAR output of 3 x S x S trained with SQUARED_ERROR against a target stream of
+    its own (the image, for an autoencoder).  The loss is summed over the 3 x S x S outputs, hence the small learning rate ``eps`` (at 0.01
+    the net diverges within three steps).  ``image_size`` must be a multiple of 4.  relu=False: LINEAR layers and average pooling (a
+    smooth net, for grad checks)."""
+    gc = _gc(grad_check, 6)
+    R, kind = ("RECTIFIED_LINEAR", "MAXPOOL") if relu else ("LINEAR", "AVERAGE_POOL")
+    s = _header("conv_autoencoder")
+    s += _layer("input", 3, size=image_size)
+    s += _layer("enc1", 16, R) + _layer("pool1", 16) + _layer("enc2", 32, R) + _layer("pool2", 32)
+    s += _layer("dec1", 32) + _layer("up1", 32) + _layer("dec2", 16, R) + _layer("up2", 16)
+    s += _layer("output", 3, "LINEAR", extra=_SQUARED_ERROR)
+    s += _conv("input", "enc1", 3, 1, 1, init_wt=init_wt, eps=eps, grad_check=gc) + _pool("enc1", "pool1", 2, 2, kind=kind)
+    s += _conv("pool1", "enc2", 3, 1, 1, init_wt=init_wt, eps=eps, grad_check=gc) + _pool("enc2", "pool2", 2, 2, kind=kind)
+    s += _conv("pool2", "dec1", 3, 1, 1, init_wt=init_wt, eps=eps, grad_check=gc) + _upsample("dec1", "up1", 2)
+    s += _conv("up1", "dec2", 3, 1, 1, init_wt=init_wt, eps=eps, grad_check=gc) + _upsample("dec2", "up2", 2)
+    s += _conv("up2", "output", 3, 1, 1, init_wt=init_wt, eps=eps, grad_check=gc)
+    return s
+
+
+def skip_sum_small(image_size=16, num_classes=10, colour=True, grad_check=False, init_wt=1.0, relu=True):
+    """A small net with a skip sum: the input goes through an RGBTOYUV edge (``colour``; False feeds the stem from the input directly),
+    conv3p1/8 ReLU ``stem``; a coarse branch (avg4s4 -> conv3p1/6 -> UPSAMPLE 4) and a fine 1x1 branch (CONV_ONETOONE / 6) both write the
+    ReLU layer ``sum`` — the 1x1 edge first, so the upsampled map is ADDED to it — then avg4s4 -> FC softmax.  ``image_size`` must be
+    a multiple of 4.  relu=False: LINEAR layers (a smooth net, for grad checks)."""
+    gc = _gc(grad_check, 6)
+    R = "RECTIFIED_LINEAR" if relu else "LINEAR"
+    s = _header("skip_sum_small")
+    s += _layer("input", 3, size=image_size) + (_layer("yuv", 3) if colour else "")
+    s += _layer("stem", 8, R) + _layer("pool", 8) + _layer("coarse", 6) + _layer("sum", 6, R)
+    s += _layer("pool2", 6) + _layer("output", num_classes, "SOFTMAX")
+    if colour:
+        s += 'edge {\n  source: "input"\n  dest: "yuv"\n  edge_type: RGBTOYUV\n}\n\n'
+    s += _conv("yuv" if colour else "input", "stem", 3, 1, 1, init_wt=init_wt, grad_check=gc)
+    s += _pool("stem", "pool", 4, 4, kind="AVERAGE_POOL") + _conv("pool", "coarse", 3, 1, 1, init_wt=init_wt, grad_check=gc)
+    s += _nin("stem", "sum", init_wt=init_wt, grad_check=gc) + _upsample("coarse", "sum", 4)
+    s += _pool("sum", "pool2", 4, 4, kind="AVERAGE_POOL") + _fc("pool2", "output", init_wt=init_wt, grad_check=gc)
     return s
 
 

@@ -454,6 +454,29 @@ void MaxPoolUndo(cudamat* images, cudamat* maxGrads, cudamat* maxActs,
 void AvgPoolUndo(cudamat* avgGrads, cudamat* targets, Shape4D* avgGrads_shape,
                  Shape4D* targets_shape, ConvDesc conv_desc, float scaleTargets);
 
+/* ---- resampling and colour transform: cudamat_conv_gemm.cuh:94-97, cudamat_conv.cuh:72-78 (csrc/resample.hip) ---------
+ * UpSampleGemm: targets (N, X*f, Y*f, C) from images (N, X, Y, C), f = factor >= 1, the image need not be square:
+ *   scaleTargets == 0:  targets[n, c, Y, X] = images[n, c, Y / f, X / f]; the target is not read (NaNs in it do not survive);
+ *   otherwise:          targets = scaleTargets * targets + images[...], one multiply and one add, each rounded (scaleTargets == 1: one add).
+ *   The replicated value is the input value ITSELF.  The reference forms f*f * x / (f*f) through its average-pool undo
+ *   (cudamat_conv_gemm.cu:1503-1541; CPU build: f*f * (x * (1 / (f*f))), src/CPUMatrix.cc:869-899): bit for bit x for power-of-two
+ *   factors, within 2^-22 relative of x (three roundings of 2^-24, with slack) for the others.
+ * DownSampleGemm: targets (N, X, Y, C) = the mean of each f x f block of images (N, X*f, Y*f, C), overwriting: bit for bit what
+ *   AvgPoolGemm leaves for kernel = stride = f, padding 0, scaleTargets 0, scaleOutput 1 on the same operands.
+ * RGBToYUV: operands (N, 3 * pixels), colour planes outermost (cudamat_conv_others.cu:296-325, the constants of src/matrix.cc:1013-1028):
+ *   Y = fmaf(0.0722f, B, fmaf(0.7152f, G, 0.2126f * R)), U = fmaf(0.436f, B, fmaf(-0.33609f, G, -0.09991f * R)),
+ *   V = fmaf(-0.05639f, B, fmaf(-0.55861f, G, 0.615f * R)); targets == images is allowed.
+ * A NULL or transposed operand, an operand that is not on the device, factor < 1, targets that are not factor x images on both axes,
+ * differing image or channel counts, a matrix that does not have the size of its shape, a column count not divisible by 3: the call
+ * leaves a text that begins with the entry's -Gemm name in get_last_cuda_error() and launches nothing.  Views from get_slice are served:
+ * the 16-byte arm needs N % 4 == 0 and 16-byte bases (RGBToYUV: N * pixels % 4 == 0), anything else runs the scalar arm.
+ * UpSample / DownSample are the same functions, as for the pool entries. */
+void UpSampleGemm(cudamat* images, cudamat* targets, Shape4D* images_shape, Shape4D* targets_shape, int factor, float scaleTargets);
+void DownSampleGemm(cudamat* images, cudamat* targets, Shape4D* images_shape, Shape4D* targets_shape, int factor);
+void UpSample(cudamat* images, cudamat* targets, Shape4D* images_shape, Shape4D* targets_shape, int factor, float scaleTargets);
+void DownSample(cudamat* images, cudamat* targets, Shape4D* images_shape, Shape4D* targets_shape, int factor);
+void RGBToYUV(cudamat* images, cudamat* targets);
+
 /* ---- cross-map response normalisation: cudamat_conv_gemm.cuh:100-106, cudamat_conv.cuh:35-42 ---------
  * In place: targets == images (forward, also ...Relu) is allowed for numFilters <= 768 only — above that the kernel walks the
  * channels in global memory and subtracts from its window sum channels it has already overwritten: the call prints
