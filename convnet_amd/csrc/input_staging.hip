@@ -448,6 +448,177 @@ __global__ void __launch_bounds__(256) crop_images_u8_kernel(const unsigned char
   }
 }
 
+// The frames of ONE geometry resized to stored bytes (video2hdf5): every frame is `height` rows of `width` interleaved R, G, B pixels,
+// the frames back to back, and every frame becomes new_height x new_width planar R, G, B bytes by the same new_width column taps and
+// new_height row taps.  What crop_images_u8 reads per (case, row) and per pixel from global tables is the same for every frame here, so a
+// block owns a tile of kRfRows x kRfCols output pixels of one frame and keeps in LDS
+//   the tile's column and row taps (source indices clamped into the frame, the column mirrored), read once;
+//   the source rows the tile needs, cut to the source columns it needs: 16-byte loads where the address allows, dwords and single bytes
+//     at the two ragged ends of a row (a frame starts anywhere), kept at their alignment so that LDS and global chunks coincide;
+//   the width pass h(y, .) of each of those rows, computed ONCE as bytes, planar, four columns to a dword;
+// and takes the height pass from there: a thread makes four adjacent columns in all three colours and stores each colour as one dword
+// where the address is 4-byte aligned, as single bytes elsewhere.  The source rows of a tile are the span from the smallest to the
+// largest row its row taps name when that span fits the kRfSlots slots (adjacent output rows then share their source rows: every resize
+// that shrinks the height less than 2x), else the two rows of every output row side by side (nothing shared, nothing lost).  A tile whose
+// source columns do not fit a slot (a width shrunk more than ~2.5x, or taps that name columns all over the row) is not staged: its
+// width pass reads the bytes from global memory one by one (resample_row), the scalar arm.  Both decisions come from the clamped taps'
+// minima and maxima, so taps in any order give the pixels of the definition and never an access outside the buffers.  h(y, .) is kept
+// as a byte, which it is for taps whose coefficients sum to 2048.
+constexpr int kRfCols = 128;                 // output columns of a tile: 32 lanes x 4
+constexpr int kRfRows = 16;                  // output rows of a tile
+constexpr int kRfSlots = 2 * kRfRows;        // source rows of a tile
+constexpr int kRfPitch = 1040;               // bytes of a staged source row, its lead of up to 15 and the over-read of the last pixel included
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
+
+// the three bytes at byte `at` of an LDS row as one value (two aligned dwords)
+__device__ __forceinline__ unsigned int lds_pixel(const unsigned int* row, int at) {
+  const unsigned long long two = ((unsigned long long)row[(at >> 2) + 1] << 32) | row[at >> 2];
+  return (unsigned int)(two >> (8 * (at & 3)));
+}
+
+__global__ void __launch_bounds__(256) resize_frames_u8_kernel(const unsigned char* __restrict__ bytes, size_t num_bytes, int width, int height,
+                                                               const int* __restrict__ taps, int W, int H, int mirrored,
+                                                               unsigned char* __restrict__ rows, int col_tiles, int row_tiles) {
+  __shared__ __attribute__((aligned(16))) unsigned int src[kRfSlots][kRfPitch / 4];
+  __shared__ unsigned int hb[kRfSlots][3][kRfCols / 4];   // h(slot's row, column) of a colour, four columns to a dword
+  __shared__ int col_tap[kRfCols][4];                     // {x0, x1, a0, a1} of the tile's output columns
+  __shared__ int row_tap[kRfRows][4];                     // {y0, y1, b0, b1} of its output rows
+  __shared__ int row_slot[kRfRows][2];                    // the slots of y0 and y1
+  __shared__ int slot_y[kRfSlots], slot_lead[kRfSlots];   // a slot's source row, and its first byte's address mod 16
+  __shared__ int tile[6];                                 // first source column, staged bytes per row, staged, first source row, dense, slots
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ct = blockIdx.x % col_tiles, rt = (blockIdx.x / col_tiles) % row_tiles;
+  const size_t n = blockIdx.x / col_tiles / row_tiles;
+  const int c0 = ct * kRfCols, r0 = rt * kRfRows;
+  const int ncols = min(kRfCols, W - c0), nrows = min(kRfRows, H - r0);
+  const unsigned char* frame = bytes + n * ((size_t)width * height * 3);
+  if (tid < kRfCols) {   // (columns past the tile's last repeat it: every entry is a tap of the table)
+    const int c = c0 + min(tid, ncols - 1);
+    const int* t = taps + 3 * (size_t)(mirrored ? W - 1 - c : c);
+    const int x0 = min(max(t[0], 0), width - 1);
+    col_tap[tid][0] = x0, col_tap[tid][1] = min(x0 + 1, width - 1), col_tap[tid][2] = t[1], col_tap[tid][3] = t[2];
+  } else if (tid < kRfCols + kRfRows) {
+    const int i = tid - kRfCols;
+    const int* t = taps + 3 * ((size_t)W + r0 + min(i, nrows - 1));
+    const int y0 = min(max(t[0], 0), height - 1);
+    row_tap[i][0] = y0, row_tap[i][1] = min(y0 + 1, height - 1), row_tap[i][2] = t[1], row_tap[i][3] = t[2];
+  }
+  __syncthreads();
+  if (wave < 2) {   // wave 0: the source columns of the tile; wave 1: its source rows
+    int lo = wave == 0 ? min(col_tap[lane][0], col_tap[lane + 64][0]) : row_tap[lane & (kRfRows - 1)][0];
+    int hi = wave == 0 ? max(col_tap[lane][1], col_tap[lane + 64][1]) : row_tap[lane & (kRfRows - 1)][1];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      lo = min(lo, __shfl_xor(lo, o, 64));
+      hi = max(hi, __shfl_xor(hi, o, 64));
+    }
+    if (lane == 0) {
+      if (wave == 0) {
+        const long len = 3L * ((long)hi - lo + 1);
+        tile[0] = lo, tile[1] = (int)min(len, (long)kRfPitch), tile[2] = len + 32 <= kRfPitch;
+      } else {
+        const long span = (long)hi - lo + 1;
+        tile[3] = lo, tile[4] = span <= kRfSlots, tile[5] = span <= kRfSlots ? (int)span : 2 * nrows;
+      }
+    }
+  }
+  __syncthreads();
+  const int lo = tile[0], len = tile[1], staged = tile[2], ymin = tile[3], dense = tile[4], slots = tile[5];
+  if (tid < slots) {
+    const int y = dense ? ymin + tid : row_tap[tid >> 1][tid & 1];
+    slot_y[tid] = y;
+    slot_lead[tid] = (int)(reinterpret_cast<uintptr_t>(frame + (size_t)y * width * 3 + (size_t)lo * 3) & 15);
+  } else if (tid >= 64 && tid < 64 + kRfRows) {
+    const int i = tid - 64;
+    row_slot[i][0] = dense ? row_tap[i][0] - ymin : 2 * i;
+    row_slot[i][1] = dense ? row_tap[i][1] - ymin : 2 * i + 1;
+  }
+  __syncthreads();
+  if (staged) {   // a wave per source row: byte k of the LDS row is byte k - lead of the row's needed part, so 16-byte chunks coincide
+    for (int s = wave; s < slots; s += 4) {
+      const int lead = slot_lead[s], end = lead + len;
+      const unsigned char* g = frame + (size_t)slot_y[s] * width * 3 + (size_t)lo * 3 - lead;   // 16-byte aligned; read from g + lead on
+      unsigned char* row = reinterpret_cast<unsigned char*>(src[s]);
+      for (int k = 16 * lane; k < end; k += 16 * 64) {
+        if (k >= lead && k + 16 <= end) {
+          *reinterpret_cast<u32x4*>(row + k) = *reinterpret_cast<const u32x4*>(g + k);
+        } else {
+#pragma unroll
+          for (int d = k; d < k + 16; d += 4) {
+            if (d >= lead && d + 4 <= end) {
+              *reinterpret_cast<unsigned int*>(row + d) = *reinterpret_cast<const unsigned int*>(g + d);
+            } else {
+#pragma unroll
+              for (int b = d; b < d + 4; ++b)
+                if (b >= lead && b < end) row[b] = g[b];
+            }
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const int group = tid & 31, sub = tid >> 5;   // four adjacent columns; one of 8 rows at a time
+  if (4 * group < ncols) {
+    int x0[4], x1[4], a0[4], a1[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int* t = col_tap[4 * group + i];
+      x0[i] = 3 * (t[0] - lo), x1[i] = 3 * (t[1] - lo), a0[i] = t[2], a1[i] = t[3];
+    }
+    for (int s = sub; s < slots; s += 8) {
+      unsigned int h[3] = {0u, 0u, 0u};
+      if (staged) {
+        const unsigned int* row = src[s];
+        const int lead = slot_lead[s];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const unsigned int p0 = lds_pixel(row, lead + x0[i]), p1 = lds_pixel(row, lead + x1[i]);
+#pragma unroll
+          for (int color = 0; color < 3; ++color) {
+            const int v = (int)((p0 >> (8 * color)) & 255) * a0[i] + (int)((p1 >> (8 * color)) & 255) * a1[i];
+            h[color] |= (unsigned int)(((((2048 * (v >> 4)) >> 16) + 2) >> 2) & 255) << (8 * i);
+          }
+        }
+      } else {
+        const size_t at = n * ((size_t)width * height * 3) + ((size_t)slot_y[s] * width + lo) * 3, last = num_bytes - 1;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int color = 0; color < 3; ++color)
+            h[color] |= (unsigned int)(resample_row(bytes, last, at + x0[i] + color, at + x1[i] + color, a0[i], a1[i]) & 255) << (8 * i);
+      }
+#pragma unroll
+      for (int color = 0; color < 3; ++color) hb[s][color][group] = h[color];
+    }
+  }
+  __syncthreads();
+  if (4 * group >= ncols) return;
+  const size_t plane = (size_t)H * W;
+  const int count = min(4, ncols - 4 * group);
+  for (int i = sub; i < nrows; i += 8) {
+    const int s0 = row_slot[i][0], s1 = row_slot[i][1], b0 = row_tap[i][2], b1 = row_tap[i][3];
+#pragma unroll
+    for (int color = 0; color < 3; ++color) {
+      const unsigned int h0 = hb[s0][color][group], h1 = hb[s1][color][group];
+      unsigned int px = 0u;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int v0 = (int)((h0 >> (8 * k)) & 255), v1 = (int)((h1 >> (8 * k)) & 255);
+        px |= (unsigned int)(((((b0 * ((2048 * v0) >> 4)) >> 16) + ((b1 * ((2048 * v1) >> 4)) >> 16) + 2) >> 2) & 255) << (8 * k);
+      }
+      unsigned char* p = rows + n * 3 * plane + plane * color + (size_t)(r0 + i) * W + (size_t)(c0 + 4 * group);
+      if (count == 4 && (reinterpret_cast<uintptr_t>(p) & 3) == 0) {
+        *reinterpret_cast<unsigned int*>(p) = px;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (k < count) p[k] = (unsigned char)(px >> (8 * k));
+      }
+    }
+  }
+}
+
 // 0: the launcher's choice; 1: every block stages all the clip's planes of its tile; 2: one plane per block (tools/clips_bench.py's A/B)
 int g_stage_clips_grid = 0;
 
@@ -675,6 +846,23 @@ int crop_images_u8(void* bytes, size_t num_bytes, void* image_table, int num_ima
                      num_bytes, static_cast<const long long*>(image_table), num_images, static_cast<const int*>(taps), (long)num_taps,
                      static_cast<const int*>(case_table), static_cast<unsigned char*>(rows), total_rows, img_width, img_height,
                      lanes_shift);
+  return hipGetLastError() == hipSuccess ? 0 : CUDA_ERROR;
+}
+
+int resize_frames_u8(void* bytes, size_t num_bytes, int num_frames, int width, int height, void* taps, int new_width, int new_height,
+                     int mirrored, void* rows) {
+  if (!bytes || !taps || !rows) return ERROR_GENERIC;
+  if (num_frames <= 0 || width <= 0 || height <= 0 || new_width <= 0 || new_height <= 0) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  const size_t pixels = (size_t)width * height;   // (< 2^62)
+  if (pixels > ~(size_t)0 / 3 / (size_t)num_frames || num_bytes < pixels * 3 * (size_t)num_frames) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  const int col_tiles = divup(new_width, kRfCols), row_tiles = divup(new_height, kRfRows);
+  const long tiles = (long)col_tiles * row_tiles;
+  if (tiles > 0x7fffffffL / num_frames || width > 0x7fffffff / 3) return ERROR_UNSUPPORTED;   // (a source row's bytes are counted in an int)
+  KernelTimer timer("resize_frames_u8_kernel", "input_staging", 0.0,
+                    3.0 * num_frames * ((double)pixels + (double)new_width * new_height));
+  hipLaunchKernelGGL(resize_frames_u8_kernel, dim3((unsigned)(tiles * num_frames)), dim3(256), 0, stream(),
+                     static_cast<const unsigned char*>(bytes), num_bytes, width, height, static_cast<const int*>(taps), new_width, new_height,
+                     mirrored != 0, static_cast<unsigned char*>(rows), col_tiles, row_tiles);
   return hipGetLastError() == hipSuccess ? 0 : CUDA_ERROR;
 }
 

@@ -147,6 +147,17 @@ def Resize(image, raw_y, raw_x):
     return Bilinear(wide, Taps(new_w, new_w), Taps(h, new_h))
 
 
+def ResizeTo(image, new_h, new_w):
+    """resizeOCV applied unconditionally, as RawVideoFileIterator::GetNext does (src/video_iterators.cc:160): the image stretched to
+    new_h x new_w, no aspect ratio kept, nothing cropped — first the width at the old height, rounded to a byte, then the height
+    (include/convnet_hip.h: h(y), then result).  The same size gives the same bytes: both passes are then the identity."""
+    h, w = image.shape[:2]
+    if new_w < 1 or new_h < 1:
+        raise SystemExit(f"{new_w} x {new_h} is not an image size.")
+    wide = Bilinear(image, Taps(w, new_w), Taps(h, h))
+    return Bilinear(wide, Taps(new_w, new_w), Taps(h, new_h))
+
+
 # ---- positions and crops ----------------------------------------------------------------------------------------------------------------------
 def Coordinates(width, height, position, size_y, size_x):
     """GetCoordinates (:143-171): (left, top, mirrored) of ``position``: centre, top-left, top-right, bottom-right, bottom-left, then the

@@ -422,6 +422,23 @@ class Matrix:
                                 ptr(case_table), case_table.shape[0], ptr(rows), int(image_size_x), int(image_size_y)),
              "Error cropping images")
 
+    @staticmethod
+    def ResizeFramesU8(bytes_, num_frames, height, width, taps, rows, new_height, new_width, mirrored):
+        """Frames of one geometry stretched to new_height x new_width as stored bytes (include/convnet_hip.h: resize_frames_u8).  Device
+        tensors, all contiguous: ``bytes_`` torch.uint8, at least num_frames * height * width * 3 values, interleaved R, G, B; ``taps``
+        torch.int32 (new_width + new_height, 3), the column taps, then the row taps; ``rows`` torch.uint8, num_frames * 3 * new_height *
+        new_width values, one planar R, G, B row per frame.  (y, x) sizes in, like ExtractPatches."""
+        _check_image_tensors("resize_frames_u8", (bytes_, "bytes"), (taps, "tap table"), (rows, "rows"))
+        if taps.shape[0] != int(new_width) + int(new_height):
+            raise MatrixError(f"Error: resize_frames_u8 : the tap table has {taps.shape[0]} rows for {int(new_width)} columns and "
+                              f"{int(new_height)} rows")
+        dims = 3 * int(new_height) * int(new_width)
+        if rows.numel() != int(num_frames) * dims:
+            raise MatrixError(f"Error: resize_frames_u8 : rows holds {rows.numel()} bytes for {int(num_frames)} frames of {dims}")
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
+        _chk(lib.resize_frames_u8(ptr(bytes_), bytes_.numel(), int(num_frames), int(width), int(height), ptr(taps), int(new_width),
+                                  int(new_height), int(bool(mirrored)), ptr(rows)), "Error resizing frames")
+
     def Mult(self, val):
         if isinstance(val, Matrix):
             _chk(lib.mult_elementwise(self.GetMat(), val.GetMat(), self.GetMat(), 0.0), "mult")

@@ -266,6 +266,25 @@ int stage_images_u8(void* bytes, size_t num_bytes, void* image_table, int num_im
  * on an error.  One launch per call, no atomics, no workspace. */
 int crop_images_u8(void* bytes, size_t num_bytes, void* image_table, int num_images, void* taps, int num_taps, void* case_table,
                    int num_cases, void* rows, int img_width, int img_height);
+/* The frames of a video as STORED BYTES (apps/video2hdf5.cc over RawVideoFileIterator, src/video_iterators.cc:150-165;
+ * convnet_amd/video2hdf5.py): num_frames frames of ONE geometry, each stretched to new_height x new_width — resizeOCV applied
+ * unconditionally, no aspect ratio kept, no crop.  All buffers are plain device pointers:
+ *   bytes  num_bytes unsigned bytes: the frames back to back, each `height` rows of `width` interleaved R, G, B pixels.  No alignment
+ *          is asked for (width * height * 3 need not be a multiple of 4): wide loads are used where an address allows them.
+ *   taps   new_width + new_height rows of 3 signed 32-bit values {source index, coefficient 0, coefficient 1}: the column taps, then
+ *          the row taps — ImageTaps(width, height, new_width, new_height) concatenated, stage_images_u8's layout for one image.
+ *   rows   num_frames * 3 * new_height * new_width unsigned bytes: frame n owns bytes n * 3 * H * W ..., planar R, G, B, row-major in
+ *          a plane — a row of dataset `data`.  No alignment is asked for: a colour of four adjacent columns is stored as one dword
+ *          where its address is 4-byte aligned and as single bytes elsewhere, as in crop_images_u8.
+ * Each byte is the resized-image byte of the definition above (h(y), then result; integers only, h(y) kept as a byte), of resized
+ * column (mirrored ? new_width - 1 - c : c) for output column c.  Source indices read from taps are clamped on the device into
+ * [0, width - 1] and [0, height - 1], every store lies inside rows by construction and the host check below keeps every load inside
+ * bytes: a wrong tap table gives wrong pixels, never an access outside the buffers.
+ * ERROR_GENERIC for a NULL pointer; ERROR_INCOMPATIBLE_DIMENSIONS for any of num_frames, width, height, new_width, new_height below 1
+ * or num_bytes < num_frames * width * height * 3 (computed in size_t); ERROR_UNSUPPORTED for a grid beyond 2^31 - 1 blocks (or a
+ * source row of more than 2^31 - 1 bytes).  Nothing is launched on an error.  One launch per call, no atomics, no workspace. */
+int resize_frames_u8(void* bytes, size_t num_bytes, int num_frames, int width, int height, void* taps, int new_width, int new_height,
+                     int mirrored, void* rows);
 /* ---- feature extraction: src/datawriter.cc (DataWriter::Write / WriteHDF5SeqBuf; csrc/feature_rows.hip) -------------------------
  * A layer state becomes rows of a feature file's dataset, averaged on the way.  state is (N, D), case fastest; sum has its shape (NULL
  * is fine when passes == 1); rows is (D, R): R rows of D contiguous floats; carry is (D, 1) (NULL is fine when group == 1).
