@@ -385,6 +385,179 @@ __global__ void __launch_bounds__(256) stage_images_u8_kernel(const unsigned cha
   }
 }
 
+// The same staging for a jitter_raw_image stream (src/image_iterators.cc:231-285: the random translated crop, zoom and rotation of the
+// decoded image): an image-table row of 11 values describes a VIEW of the file (first byte, crop width and height, the file's row
+// stride), the size the crop is resized to, and — for a rotated image — where its rotation rows start in the tap table and the size of
+// the window that is cut from the rotated image (include/convnet_hip.h has the layout and the formula).  A case's crop lies in that
+// window.  An unrotated pixel is the resized crop's byte, as in stage_images_u8_kernel; a rotated pixel is the fixed-point blend of up to
+// four resized-crop bytes around its source point, each the two-pass value of up to four source bytes, 0 outside the resized crop.  The
+// tile, the LDS transpose, the wave stores and the three colours per thread are stage_images_u8_kernel's (a source pixel's colours are
+// adjacent bytes).  Once per block the first wave works out what a (case, patch row) contributes to all its pixels: the view, the sizes,
+// the tap rows, the crop column walk, and for an unrotated image the two source rows and the row coefficients, for a rotated one X0 / Y0
+// of the window row.  A rotated pixel loads its column's rotation row, then per neighbour of non-zero weight a column tap, a row tap and
+// 12 bytes; neighbours of weight 0 (a turn by a multiple of 90 degrees has only those) and neighbours outside the resized crop load
+// nothing.  ROTATE false is the arm for a launch without a rotated image: a rotated flag in the table is then not honoured.
+// Integer arithmetic only up to the cast.  Everything read from a table is clamped: the image number, the sizes (1 ... 2^30), the stride
+// (0 ... 2^32), the tap and rotation rows, the window's column and row, the source indices inside the view, X / Y (+-2^30), the byte address.
+struct JitterCase {
+  size_t base;            // the view's first byte in the buffer
+  size_t stride;          // bytes from one row of the view to the next
+  size_t row0, row1;      // unrotated: byte offsets of the two source rows
+  long taps;              // number of the image's first column tap; its row taps follow the new_w column taps
+  long rot;               // rotated: number of the rotation row of window column 0
+  int width, height;      // the view's size, >= 1
+  int new_w, new_h;       // the size it is resized to, >= 1
+  int win_w;              // the window's width (unrotated: new_w)
+  int b0, b1;             // unrotated: the row coefficients
+  int x0, y0;             // rotated: X0 and Y0 of the window row
+  int rotated;
+  int left, mirror;       // where the crop starts in the window's row, and whether it walks backwards
+  int col_first, col_step, crop_row;   // the patch jitter: crop column of patch column 0, direction, crop row
+};
+
+// The three colours of pixel (ry, rx) of the resized view, 0 <= rx < new_w and 0 <= ry < new_h: both taps, the width pass on both
+// source rows and the height pass.
+__device__ __forceinline__ void resized_view_pixel(const unsigned char* __restrict__ bytes, size_t last, const int* __restrict__ taps,
+                                                   long num_taps, const JitterCase& k, int rx, int ry, int (&v)[3]) {
+  const int* tc = taps + 3 * min(k.taps + rx, num_taps - 1);
+  const int* tr = taps + 3 * min(k.taps + k.new_w + ry, num_taps - 1);
+  const int sx = min(max(tc[0], 0), k.width - 1), a0 = tc[1], a1 = tc[2];
+  const int sy = min(max(tr[0], 0), k.height - 1), b0 = tr[1], b1 = tr[2];
+  const size_t row0 = k.base + (size_t)sy * k.stride, row1 = k.base + (size_t)min(sy + 1, k.height - 1) * k.stride;
+  const size_t x0 = (size_t)sx * 3, x1 = (size_t)min(sx + 1, k.width - 1) * 3;
+#pragma unroll
+  for (int color = 0; color < 3; ++color) {
+    const int h0 = resample_row(bytes, last, row0 + x0 + color, row0 + x1 + color, a0, a1);
+    const int h1 = resample_row(bytes, last, row1 + x0 + color, row1 + x1 + color, a0, a1);
+    v[color] = (((b0 * ((2048 * h0) >> 4)) >> 16) + ((b1 * ((2048 * h1) >> 4)) >> 16) + 2) >> 2;
+  }
+}
+
+template <bool NORM, bool JITTER, bool ROTATE>
+__global__ void __launch_bounds__(256) stage_images_jitter_u8_kernel(const unsigned char* __restrict__ bytes, size_t num_bytes,
+                                                                     const long long* __restrict__ image_table, int num_images,
+                                                                     const int* __restrict__ taps, long num_taps,
+                                                                     const int* __restrict__ case_table, const float* __restrict__ mean,
+                                                                     const float* __restrict__ sdev, float* __restrict__ patches,
+                                                                     const float* __restrict__ wo, const float* __restrict__ ho,
+                                                                     const float* __restrict__ flip, int N, int W, int H, int pw, int ph) {
+  __shared__ float tile[3][64][65];
+  __shared__ JitterCase cases[64];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;   // 64 x 4
+  const int c0 = blockIdx.x * 64;
+  const int row = blockIdx.y;
+  const int n0 = blockIdx.z * 64;
+  const size_t last = num_bytes - 1;
+  if (ty == 0 && n0 + tx < N) {
+    const int n = n0 + tx;
+    int sr = row, first = 0, step = 1;
+    if (JITTER) {
+      sr += min(max((int)ho[n], -H - ph), H + ph);
+      first = min(max((int)wo[n], -W - pw), W + pw);
+      if (flip[n] > 0.5f) {
+        first = W - first - 1;
+        step = -1;
+      }
+    }
+    sr = min(max(sr, 0), H - 1);
+    const int* c = case_table + 4 * (size_t)n;
+    const long long* im = image_table + 11 * (size_t)min(max(c[0], 0), num_images - 1);
+    const auto dim = [](long long v) { return (int)min(max(v, 1LL), 1LL << 30); };
+    const auto tap = [num_taps](long long v) { return (long)min(max(v, 0LL), (long long)num_taps - 1); };
+    JitterCase& k = cases[tx];
+    k.base = (size_t)min(max(im[0], 0LL), (long long)last);
+    k.width = dim(im[1]);
+    k.height = dim(im[2]);
+    k.new_w = dim(im[3]);
+    k.new_h = dim(im[4]);
+    k.taps = tap(im[5]);
+    k.stride = (size_t)min(max(im[6], 0LL), 1LL << 32);
+    k.rotated = ROTATE && im[7] != 0;
+    k.rot = tap(im[8]);
+    k.win_w = k.rotated ? dim(im[9]) : k.new_w;
+    const int win_h = k.rotated ? dim(im[10]) : k.new_h;
+    const int wr = min(max(min(max(c[2], -(1 << 30)), 1 << 30) + sr, 0), win_h - 1);   // the row of the window
+    k.row0 = k.row1 = 0;
+    k.b0 = k.b1 = k.x0 = k.y0 = 0;
+    if (k.rotated) {
+      const int* t = taps + 3 * min(k.rot + k.win_w + wr, num_taps - 1);
+      k.x0 = t[0];
+      k.y0 = t[1];
+    } else {
+      const int* t = taps + 3 * min(k.taps + k.new_w + wr, num_taps - 1);
+      const int sy = min(max(t[0], 0), k.height - 1);
+      k.row0 = k.base + (size_t)sy * k.stride;
+      k.row1 = k.base + (size_t)min(sy + 1, k.height - 1) * k.stride;
+      k.b0 = t[1];
+      k.b1 = t[2];
+    }
+    k.left = min(max(c[1], -(1 << 30)), 1 << 30);
+    k.mirror = c[3] != 0;
+    k.col_first = first;
+    k.col_step = step;
+    k.crop_row = sr;
+  }
+  __syncthreads();
+#pragma unroll 2
+  for (int j = ty; j < 64; j += 4) {
+    const int n = n0 + j, dc = c0 + tx;
+    if (n < N && dc < pw) {
+      const JitterCase& k = cases[j];
+      const int sc = min(max(k.col_first + k.col_step * dc, 0), W - 1);                  // the column of the crop
+      const int wc = min(max(k.left + (k.mirror ? W - 1 - sc : sc), 0), k.win_w - 1);      // the column of the window
+      int v[3] = {0, 0, 0};
+      if (ROTATE && k.rotated) {
+        const int* t = taps + 3 * min(k.rot + wc, num_taps - 1);                           // {adelta, bdelta, -}
+        const long bound = 1L << 30;
+        const int X = (int)min(max(((long)k.x0 + t[0]) >> 5, -bound), bound), Y = (int)min(max(((long)k.y0 + t[1]) >> 5, -bound), bound);
+        const int sx = X >> 5, sy = Y >> 5, fx = X & 31, fy = Y & 31;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int rx = sx + (q & 1), ry = sy + (q >> 1);
+          const int weight = ((q & 1) ? fx : 32 - fx) * ((q >> 1) ? fy : 32 - fy);
+          if (weight != 0 && rx >= 0 && rx < k.new_w && ry >= 0 && ry < k.new_h) {
+            int p[3];
+            resized_view_pixel(bytes, last, taps, num_taps, k, rx, ry, p);
+#pragma unroll
+            for (int color = 0; color < 3; ++color) v[color] += weight * p[color];
+          }
+        }
+#pragma unroll
+        for (int color = 0; color < 3; ++color) v[color] = (v[color] + 512) >> 10;
+      } else {
+        const int* t = taps + 3 * min(k.taps + wc, num_taps - 1);
+        const int sx = min(max(t[0], 0), k.width - 1), a0 = t[1], a1 = t[2];
+        const size_t x0 = (size_t)sx * 3, x1 = (size_t)min(sx + 1, k.width - 1) * 3;
+#pragma unroll
+        for (int color = 0; color < 3; ++color) {
+          const int h0 = resample_row(bytes, last, k.row0 + x0 + color, k.row0 + x1 + color, a0, a1);
+          const int h1 = resample_row(bytes, last, k.row1 + x0 + color, k.row1 + x1 + color, a0, a1);
+          v[color] = (((k.b0 * ((2048 * h0) >> 4)) >> 16) + ((k.b1 * ((2048 * h1) >> 4)) >> 16) + 2) >> 2;
+        }
+      }
+      const int src = sc + W * k.crop_row;
+#pragma unroll
+      for (int color = 0; color < 3; ++color) {
+        float f = (float)v[color];
+        if (NORM) {
+          const int s = src + W * H * color;
+          f = (f - mean[s]) / sdev[s];
+        }
+        tile[color][j][tx] = f;
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int color = 0; color < 3; ++color) {
+#pragma unroll 4
+    for (int j = ty; j < 64; j += 4) {
+      const int dc = c0 + j, n = n0 + tx;
+      if (n < N && dc < pw) patches[(size_t)n + (size_t)N * (dc + (size_t)pw * (row + (size_t)ph * color))] = tile[color][tx][j];
+    }
+  }
+}
+
 // The crops of the same decoded image files as STORED BYTES: case n's img_height x img_width crop of its resized image, planar R, G, B,
 // at rows + n * 3 * H * W — a row of an HDF5 byte dataset, a column of a byte chunk (image2hdf5).  The tables and the integer arithmetic
 // are stage_images_u8's; there is no cast, no mean / std and no patch.  The output is contiguous along the crop column, so nothing is
@@ -828,6 +1001,29 @@ int stage_images_u8(void* bytes, size_t num_bytes, void* image_table, int num_im
   return launch_stage_u8(s, STAGE_U8_KERNEL(stage_images_u8_kernel, s), static_cast<const unsigned char*>(bytes), num_bytes,
                          static_cast<const long long*>(image_table), num_images, static_cast<const int*>(taps), (long)num_taps,
                          static_cast<const int*>(case_table));
+}
+
+int stage_images_jitter_u8(void* bytes, size_t num_bytes, void* image_table, int num_images, void* taps, int num_taps, void* case_table,
+                           int rotated, cudamat* mean, cudamat* sdev, cudamat* patches, cudamat* width_offset, cudamat* height_offset,
+                           cudamat* flip, int img_width, int img_height, int patch_width, int patch_height) {
+  if (const int e = check_image_tables(bytes, num_bytes, image_table, taps, num_taps, case_table, patches, img_width, img_height)) return e;
+  if ((long)img_width * img_height > (1 << 28)) return ERROR_INCOMPATIBLE_DIMENSIONS;
+  // the rest is stage_images_u8's: stage_patches_u8's checker on a crop of three colours, which a block stages together
+  StageU8 s{3 * img_width * img_height, num_images, nullptr, mean, sdev, patches, width_offset, height_offset, flip, img_width, img_height,
+            patch_width, patch_height, 1, 1, 3};
+  if (const int e = check_stage_u8(s); e || s.num_images == 0) return e;
+  KernelTimer timer(rotated ? "stage_images_jitter_u8_kernel<rotate>" : "stage_images_jitter_u8_kernel", "input_staging", 0.0,
+                    (rotated ? 52.0 : 16.0) * numel(patches));
+  const auto launch = [&](auto kernel) {
+    return launch_stage_u8(s, kernel, static_cast<const unsigned char*>(bytes), num_bytes, static_cast<const long long*>(image_table),
+                           num_images, static_cast<const int*>(taps), (long)num_taps, static_cast<const int*>(case_table));
+  };
+  if (rotated) {
+    if (s.norm) return s.jitter ? launch(stage_images_jitter_u8_kernel<true, true, true>) : launch(stage_images_jitter_u8_kernel<true, false, true>);
+    return s.jitter ? launch(stage_images_jitter_u8_kernel<false, true, true>) : launch(stage_images_jitter_u8_kernel<false, false, true>);
+  }
+  if (s.norm) return s.jitter ? launch(stage_images_jitter_u8_kernel<true, true, false>) : launch(stage_images_jitter_u8_kernel<true, false, false>);
+  return s.jitter ? launch(stage_images_jitter_u8_kernel<false, true, false>) : launch(stage_images_jitter_u8_kernel<false, false, false>);
 }
 
 int crop_images_u8(void* bytes, size_t num_bytes, void* image_table, int num_images, void* taps, int num_taps, void* case_table,

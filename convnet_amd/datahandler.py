@@ -2,7 +2,8 @@
 leaves a batch in every input layer's ``state_`` (N, X*Y*C CHWN) and every output layer's ``data_``.
 ``DataHandler`` (below) is the reference's own, for HDF5 streams and lists of image files: built from a DatasetConfig, it reads
 chunks from disk and stages batches on the GPU — rows of a dataset, clips of consecutive frames of one (``is_sequence``), or crops of
-image files resized on the way (``data_type: IMAGE_RAW``, image_iterators.py); video / text / sliding-window streams are refused.
+image files resized — and with ``jitter_raw_image`` randomly cropped, zoomed and rotated — on the way (``data_type: IMAGE_RAW``,
+image_iterators.py); video / text / sliding-window streams are refused.
 ``ChunkDataHandler`` stages from numpy arrays the caller holds; ``SyntheticDataHandler`` makes noise: inputs are N(0,1) (the real pipeline feeds mean/std-normalised
 pixels, :496-507), labels uniform ints stored as float (N,1); ``num_batches`` distinct batches are
 pre-generated on the device and cycled, so no host work sits inside a timed step."""
@@ -219,14 +220,20 @@ def _check_image_stream(dsc):
                          "set raw_image_size, or raw_image_size_y and raw_image_size_x.")
     if dsc.is_sequence:
         raise SystemExit(head + "is_sequence is not supported on an IMAGE_RAW stream: clips are read from HDF5 frame datasets.")
-    if dsc.jitter_raw_image:
-        raise SystemExit(head + "jitter_raw_image is not supported: the random crop, scale and rotation of the decoded image need "
-                         "warpAffine and the stream of std::default_random_engine.")
-    if dsc.random_rotate_max_angle != 0:
-        raise SystemExit(head + f"random_rotate_max_angle {dsc.random_rotate_max_angle:g} is not supported: rotating the decoded image needs "
-                         "warpAffine.")
-    if dsc.min_scale != 0:
-        raise SystemExit(head + f"min_scale {dsc.min_scale:g} is not supported: it scales the random crop of jitter_raw_image, which is not built.")
+    # jitter_raw_image (image_iterators.Transform): refused where the reference would silently do nothing, or could not run
+    if not dsc.jitter_raw_image and dsc.random_rotate_max_angle != 0:
+        raise SystemExit(head + f"random_rotate_max_angle {dsc.random_rotate_max_angle:g} without jitter_raw_image is not supported: the "
+                         "reference ignores the angle there; set jitter_raw_image: true (and min_scale: 1 or more).")
+    if not dsc.jitter_raw_image and dsc.min_scale != 0:
+        raise SystemExit(head + f"min_scale {dsc.min_scale:g} without jitter_raw_image is not supported: the reference ignores the scale "
+                         "there; set jitter_raw_image: true.")
+    if dsc.jitter_raw_image and dsc.min_scale < 1:
+        raise SystemExit(head + f"jitter_raw_image with min_scale {dsc.min_scale:g} (the default is 0) is not supported: every drawn scale "
+                         "would be ignored, because the reference zooms only by scales above 1; min_scale: 1 gives translation and rotation "
+                         "alone, a larger one zooms in by up to that factor.")
+    if dsc.jitter_raw_image and abs(int(dsc.random_rotate_max_angle)) > 90:
+        raise SystemExit(head + f"jitter_raw_image with random_rotate_max_angle {dsc.random_rotate_max_angle:g} is not supported: beyond 90 "
+                         "degrees the rotated image is smaller than raw_image_size and the reference cannot crop it.")
     if dsc.bbox_file:
         raise SystemExit(head + f"bbox_file ({dsc.bbox_file}) is not supported: crops around bounding boxes are not built.")
     if dsc.num_colors != 3:
@@ -359,7 +366,8 @@ class _Stream:
             self.file_ = None
             self.raw_size_y_, self.raw_size_x_ = size_yx(dsc, "raw_image_size")
             self.reader_ = image_iterators.ImageReader(image_iterators.ReadFileList(dsc.file_pattern), size_y, size_x, self.raw_size_y_,
-                                                       self.raw_size_x_, dsc.avg10_full_image, dsc.parallel_disk_access, name)
+                                                       self.raw_size_x_, dsc.avg10_full_image, dsc.parallel_disk_access, name,
+                                                       dsc.jitter_raw_image, dsc.random_rotate_max_angle, dsc.min_scale)
         else:
             self.file_ = hdf5io.File(dsc.file_pattern)
             self.reader_ = self.file_.RowReader(dsc.dataset_name)
@@ -487,6 +495,12 @@ class _RowsDisk:
         """(shape, dtype) of a host buffer of this stream; ``count`` of them are about to be made."""
         return (self.chunk_size_, self.reader_.GetDims()), self.dtype_
 
+    def Prep(self):
+        """DataIterator::Prep: once per DiskAccess, before any run is loaded — not once per LoadRun piece."""
+        prep = getattr(self.reader_, "Prep", None)
+        if prep is not None:
+            prep(self.chunk_size_)
+
     def LoadRun(self, out, buf, at, row, count, seek=False):
         """``count`` consecutive rows from ``row`` into host buffer ``out`` (number ``buf``) from chunk position ``at`` on, wrapping at the
         end of the dataset (GetNext's wrap, :717-721; LoadChunk's, :305-311)."""
@@ -536,7 +550,8 @@ class _ImagesDisk(_RowsDisk):
     sizes as interleaved R, G, B rows, back to back.  Beside each buffer (numpy, [buffer]): ``image_table_`` {byte offset, w, h, new_w,
     new_h, first tap} per image, ``taps_`` {source index, coefficient 0, coefficient 1} per column and row of every resized image, built
     here in the preload thread, ``case_table_`` {image, left, top, mirrored} per case, and how much of each the chunk filled.  The ten
-    positions of a file share its pixels and its taps.  Buffers start at chunk_size * raw_y * raw_x * 3 * 2 bytes (twice a chunk of images
+    positions of a file share its pixels and its taps.  A ``jitter_raw_image`` stream has the 11-column image table and the rotation rows
+    of ``stage_images_jitter_u8`` instead (``_jittered``), drawn anew for every chunk by the reader's ``Prep``.  Buffers start at chunk_size * raw_y * raw_x * 3 * 2 bytes (twice a chunk of images
     that are exactly the raw size); a chunk that needs more gets new ones of twice its need, through ``grow_`` (the handler's, which
     knows whether host buffers are pinned)."""
 
@@ -550,7 +565,7 @@ class _ImagesDisk(_RowsDisk):
 
     def HostBuffers(self, count):
         r = self.reader_
-        self.image_table_ = [np.zeros((self.chunk_size_, 6), np.int64) for _ in range(count)]
+        self.image_table_ = [np.zeros((self.chunk_size_, 11 if r.jitter_ else 6), np.int64) for _ in range(count)]
         self.taps_ = [np.zeros((self.chunk_size_ * (r.raw_y_ + r.raw_x_) * 2, 3), np.int32) for _ in range(count)]
         self.case_table_ = [np.zeros((self.chunk_size_, 4), np.int32) for _ in range(count)]
         self.bytes_used_, self.images_used_, self.taps_used_ = [0] * count, [0] * count, [0] * count
@@ -573,7 +588,12 @@ class _ImagesDisk(_RowsDisk):
         known = self.image_of_file_[buf]
         files = [f for f in r.FilesOf(row, row + n) if f not in known]
         images = r.Decode(files)
-        sizes = [(im.shape[1], im.shape[0], *ii.ResizedSize(im.shape[1], im.shape[0], r.raw_y_, r.raw_x_)) for im in images]
+        if r.jitter_:                        # (left, top, crop w, crop h, angle, new_w, new_h) per file, and the tap rows it takes
+            sizes = [r.JitterGeometry(f, im.shape[1], im.shape[0]) for f, im in zip(files, images)]
+            tap_rows = [new_w + new_h + ((r.raw_x_ + r.raw_y_) if angle != 0 else 0) for *_, angle, new_w, new_h in sizes]
+        else:
+            sizes = [(im.shape[1], im.shape[0], *ii.ResizedSize(im.shape[1], im.shape[0], r.raw_y_, r.raw_x_)) for im in images]
+            tap_rows = [new_w + new_h for _, _, new_w, new_h in sizes]
         used, taps_used = self.bytes_used_[buf], self.taps_used_[buf]
         need = used + sum(im.size for im in images)
         out = self.bytes_[buf]               # (not the caller's: an earlier piece of this chunk may have replaced it)
@@ -581,25 +601,45 @@ class _ImagesDisk(_RowsDisk):
             grown = self.grow_(buf, 2 * need)
             grown[:used] = out[:used]
             out = grown
-        taps_need = taps_used + sum(new_w + new_h for _, _, new_w, new_h in sizes)
+        taps_need = taps_used + sum(tap_rows)
         if taps_need > len(self.taps_[buf]):
             grown = np.zeros((2 * taps_need, 3), np.int32)
             grown[:taps_used] = self.taps_[buf][:taps_used]
             self.taps_[buf] = grown
-        for f, im, (w, h, new_w, new_h) in zip(files, images, sizes):
+        for f, im, size, count in zip(files, images, sizes, tap_rows):
             k = known[f] = self.images_used_[buf]
             out[used:used + im.size] = im.reshape(-1)
-            cols, rows = ii.ImageTaps(w, h, new_w, new_h)
-            self.taps_[buf][taps_used:taps_used + new_w] = cols
-            self.taps_[buf][taps_used + new_w:taps_used + new_w + new_h] = rows
-            self.image_table_[buf][k] = (used, w, h, new_w, new_h, taps_used)
-            used, taps_used, self.images_used_[buf] = used + im.size, taps_used + new_w + new_h, k + 1
+            t = self.taps_[buf][taps_used:taps_used + count]
+            if r.jitter_:
+                self.image_table_[buf][k] = self._jittered(t, im.shape[1], used, taps_used, *size)
+            else:
+                w, h, new_w, new_h = size
+                t[:new_w], t[new_w:] = ii.ImageTaps(w, h, new_w, new_h)
+                self.image_table_[buf][k] = (used, w, h, new_w, new_h, taps_used)
+            used, taps_used, self.images_used_[buf] = used + im.size, taps_used + count, k + 1
         self.bytes_used_[buf], self.taps_used_[buf] = used, taps_used
         for i in range(n):
             f, position = r.FileAndPosition(row + i)
-            _, _, _, new_w, new_h, _ = self.image_table_[buf][known[f]]
+            new_w, new_h = (r.raw_x_, r.raw_y_) if r.jitter_ else self.image_table_[buf][known[f]][3:5]
             left, top, mirrored = ii.Coordinates(int(new_w), int(new_h), position, r.size_y_, r.size_x_)
             self.case_table_[buf][at + i] = (known[f], left, top, mirrored)
+
+    def _jittered(self, t, width, at, first_tap, left, top, sx, sy, angle, new_w, new_h):
+        """The image-table row of a jittered file (include/convnet_hip.h: stage_images_jitter_u8) whose pixels start at byte ``at``, and
+        its tap rows into ``t``: the view of the crop inside the file, the taps crop -> new_w x new_h, and behind them, when the crop is
+        rotated, the rotation rows of the columns and of the rows that the raw-size window covers."""
+        from . import image_iterators as ii
+        raw_x, raw_y = self.reader_.raw_x_, self.reader_.raw_y_
+        t[:new_w], t[new_w:new_w + new_h] = ii.ImageTaps(sx, sy, new_w, new_h)
+        if angle != 0:
+            adelta, bdelta, X0, Y0 = ii.RotationTables(new_w, new_h, angle)
+            ox, oy = new_w // 2 - raw_x // 2, new_h // 2 - raw_y // 2
+            rot = t[new_w + new_h:]
+            rot[:raw_x, 0], rot[:raw_x, 1] = adelta[ox:ox + raw_x], bdelta[ox:ox + raw_x]
+            rot[raw_x:, 0], rot[raw_x:, 1] = X0[oy:oy + raw_y], Y0[oy:oy + raw_y]
+            rot[:, 2] = 0
+        return (at + (top * width + left) * 3, sx, sy, new_w, new_h, first_tap, width * 3, int(angle != 0), first_tap + new_w + new_h,
+                raw_x, raw_y)
 
 
 class _Index:
@@ -718,13 +758,14 @@ class _ImagesOnceForm(_Form):
     """An IMAGE_RAW stream's byte form: the decoded files of a chunk at their original sizes, each once, and the three tables of
     ``_ImagesDisk`` beside them on the device.  Only the used prefixes are uploaded; the device buffer starts at the host buffer's size and
     is reallocated at twice the need when a chunk needs more; randomize_gpu swaps rows of the case table; a batch is ONE ``StageImagesU8``
-    that resamples, crops, mirrors, normalises and transposes the pixels of the patch — the resized image is never made."""
+    that resamples, crops, mirrors, normalises and transposes the pixels of the patch — the resized image is never made.  A
+    ``jitter_raw_image`` stream takes ``StageImagesJitterU8``, which also crops, zooms and rotates on the way."""
     raw_, frames_once_ = True, False
 
     def __init__(self, st, chunk_size, dataset_size):
         self.disk_ = _ImagesDisk(st.reader_, chunk_size, dataset_size)
         self.data_ = self.image_table_ = self.taps_ = self.case_table_ = self.case_host_ = None
-        self.bytes_used_ = 0
+        self.bytes_used_, self.rotated_ = 0, False
 
     def AllocateMemory(self, st):
         self.data_ = torch.empty(self.disk_.start_bytes_, dtype=torch.uint8, device=Matrix()._dev())
@@ -737,6 +778,7 @@ class _ImagesOnceForm(_Form):
         self.data_[:used].copy_(src[:used], non_blocking=True)
         _, image_table, taps, case_table = d.Used(buf)
         self.image_table_, self.taps_ = torch.from_numpy(image_table).to(dev), torch.from_numpy(taps).to(dev)
+        self.rotated_ = bool(image_table.shape[1] > 7 and image_table[:, 7].any())      # no rotated image: the arm without the blend
         self.case_host_ = case_table.copy()
         self.case_table_ = torch.from_numpy(self.case_host_).to(dev)
 
@@ -751,8 +793,11 @@ class _ImagesOnceForm(_Form):
     def Stage(self, st, start, end, output):
         j = st.jitter_
         offsets = (j.width_offset_, j.height_offset_, j.flip_bit_) if j.Jitters() else (None, None, None)
-        Matrix.StageImagesU8(*self.Cases(start, end), *st.Normalizers(), output, *offsets, j.image_size_y_, j.image_size_x_,
-                             j.gpu_image_size_y_, j.gpu_image_size_x_)
+        sizes = (j.image_size_y_, j.image_size_x_, j.gpu_image_size_y_, j.gpu_image_size_x_)
+        if st.reader_.jitter_:               # jitter_raw_image: the crop view, the zoom and the rotation live in the image table
+            Matrix.StageImagesJitterU8(*self.Cases(start, end), self.rotated_, *st.Normalizers(), output, *offsets, *sizes)
+        else:
+            Matrix.StageImagesU8(*self.Cases(start, end), *st.Normalizers(), output, *offsets, *sizes)
 
 
 class _DiskSide:
@@ -794,6 +839,8 @@ class _DiskSide:
                 self.random_indices_ind_ = 0
             random_rows = self.random_indices_[self.random_indices_ind_:self.random_indices_ind_ + num_rand].tolist()
             self.random_indices_ind_ += num_rand
+        for half in self.halves_.values():       # every stream first (:253-257): an image stream draws its jitter_raw_image entries anew
+            half.Prep()
         for name, half in self.halves_.items():
             out = self.host_[buf][name]
             if random_rows is None:

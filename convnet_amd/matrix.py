@@ -52,7 +52,7 @@ def _byte_columns(entry, what, holder, unit, t, dims, count):
 
 
 _IMAGE_TENSORS = {"bytes": (torch.uint8, None), "rows": (torch.uint8, None), "image table": (torch.int64, 6),
-                  "tap table": (torch.int32, 3), "case table": (torch.int32, 4)}
+                  "jitter image table": (torch.int64, 11), "tap table": (torch.int32, 3), "case table": (torch.int32, 4)}
 
 
 def _check_image_tensors(entry, *tensors):
@@ -406,6 +406,22 @@ class Matrix:
                                  ptr(case_table), _opt(mean), _opt(std), dest.GetMat(), _opt(width_offset), _opt(height_offset),
                                  _opt(flip_bit), int(image_size_x), int(image_size_y), int(patch_size_x), int(patch_size_y)),
              "Error staging images")
+
+    @staticmethod
+    def StageImagesJitterU8(bytes_, image_table, taps, case_table, rotated, mean, std, dest, width_offset, height_offset, flip_bit,
+                            image_size_y, image_size_x, patch_size_y, patch_size_x):
+        """StageImagesU8 for a ``jitter_raw_image`` stream (include/convnet_hip.h: stage_images_jitter_u8): every image is a crop view
+        of its file, resized and — where its row says so — rotated on the way.  ``image_table`` torch.int64 (images, 11); ``taps`` holds
+        the rotation rows too.  ``rotated`` False promises that no row of the image table is rotated: the arm without the blend."""
+        _check_image_tensors("stage_images_jitter_u8", (bytes_, "bytes"), (image_table, "jitter image table"), (taps, "tap table"),
+                             (case_table, "case table"))
+        if case_table.shape[0] != dest.GetRows():
+            raise MatrixError(f"Error: stage_images_jitter_u8 : the case table has {case_table.shape[0]} rows for {dest.GetRows()} cases")
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
+        _chk(lib.stage_images_jitter_u8(ptr(bytes_), bytes_.numel(), ptr(image_table), image_table.shape[0], ptr(taps), taps.shape[0],
+                                        ptr(case_table), int(bool(rotated)), _opt(mean), _opt(std), dest.GetMat(), _opt(width_offset),
+                                        _opt(height_offset), _opt(flip_bit), int(image_size_x), int(image_size_y), int(patch_size_x),
+                                        int(patch_size_y)), "Error staging jittered images")
 
     @staticmethod
     def CropImagesU8(bytes_, image_table, taps, case_table, rows, image_size_y, image_size_x):

@@ -251,6 +251,43 @@ void convnet_hip_set_stage_clips_grid(int mode);
 int stage_images_u8(void* bytes, size_t num_bytes, void* image_table, int num_images, void* taps, int num_taps, void* case_table,
                     cudamat* mean, cudamat* std, cudamat* patches, cudamat* width_offset, cudamat* height_offset, cudamat* flip,
                     int img_width, int img_height, int patch_width, int patch_height);
+/* stage_images_u8 for a jitter_raw_image stream (src/image_iterators.cc:189-202, 231-285: per file a random translated crop, a zoom and
+ * a rotation of the decoded image, drawn anew for every chunk; convnet_amd/image_iterators.py: Transform).  The arguments, the case
+ * table, the cast, mean / std, the patch offsets, the output and the error codes are stage_images_u8's; what differs is the image:
+ *   image_table  num_images rows of 11 signed 64-bit values
+ *                {byte offset, w, h, new_w, new_h, first_tap, row stride, rotated (0 / 1), first rotation row, win_w, win_h}:
+ *                the image is a VIEW of its file — the w x h region Transform crops, whose pixel (y, x) of colour k is the byte at
+ *                byte offset + y * row stride + 3 * x + k — resized to new_w x new_h by the two-pass definition above (x + 1 and y + 1
+ *                clamped to the VIEW's last index, not the file's) with the new_w column taps and new_h row taps from first_tap on.
+ *                rotated 0: that resized view is the image the case table's {left, top, mirrored} refer to (win_w / win_h are not
+ *                read).  rotated 1: the resized view R is rotated and the case table refers to a window of win_w x win_h pixels cut
+ *                from the rotated image.
+ *   taps         also holds, for a rotated image, win_w + win_h rotation rows of 3 signed 32-bit values from `first rotation row` on:
+ *                {adelta, bdelta, unused} of every window column, then {X0, Y0, unused} of every window row.
+ *   rotated      0 promises that no row of image_table is rotated: the launch takes the arm without the blend, which reads every image
+ *                as unrotated.
+ * The rotation, pinned to this text and not to an OpenCV build (it is modelled on the INTER_LINEAR fixed-point warpAffine: coordinates
+ * with 10 fractional bits reduced to 5, constant border 0).  Host side, in double, for new_w x new_h = RX x RY and an angle in degrees:
+ *   a = cos(angle * (pi / 180)), b = sin(angle * (pi / 180)), cx = RX / 2, cy = RY / 2 (integer halves)
+ *   M  = [a, b, (1 - a) * cx - b * cy;  -b, a, b * cx + (1 - a) * cy]                      the forward matrix
+ *   D  = 1 / (M0 * M4 - M1 * M3);  M0' = M4 * D, M4' = M0 * D, M1' = -M1 * D, M3' = -M3 * D
+ *   M2' = -M0' * M2 - M1' * M5,  M5' = -M3' * M2 - M4' * M5                                its inverse
+ *   adelta[x] = rint(M0' * x * 1024), bdelta[x] = rint(M3' * x * 1024)                     rint rounds half to even
+ *   X0[y] = rint((M1' * y + M2') * 1024) + 16,  Y0[y] = rint((M4' * y + M5') * 1024) + 16
+ * The window is cut at (ox, oy) = (RX / 2 - win_w / 2, RY / 2 - win_h / 2): window column c has the rotation row of x = ox + c, window
+ * row r that of y = oy + r.  Per pixel of the window, integers only, arithmetic shifts:
+ *   X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;  sx = X >> 5, sy = Y >> 5, fx = X & 31, fy = Y & 31
+ *   out = ((32 - fx) * (32 - fy) * R(sy, sx) + fx * (32 - fy) * R(sy, sx + 1) + (32 - fx) * fy * R(sy + 1, sx)
+ *          + fx * fy * R(sy + 1, sx + 1) + 512) >> 10,        R(., .) = 0 outside [0, RY) x [0, RX)
+ * (the weights are the warp's 15-bit table entries / 32: at steps of 1/32 they are exact and sum to 32 768, so there is no table and
+ * no fix-up).  A turn by 90 degrees of an odd square is np.rot90 of it, by -90 np.rot90(., -1), by 180 both flips, bit for bit.
+ * Every index read from a table is clamped on the device: the image, tap rows and rotation rows into [0, num_taps), source indices into
+ * the view, the byte address below num_bytes, all sizes to 1 ... 2^30, the row stride to 0 ... 2^32, the window's column and row into
+ * the window, X and Y into +-2^30: a wrong table gives wrong pixels, never a read outside bytes / image_table / taps.  One launch per
+ * call, no atomics, no workspace; nothing is launched on an error. */
+int stage_images_jitter_u8(void* bytes, size_t num_bytes, void* image_table, int num_images, void* taps, int num_taps, void* case_table,
+                           int rotated, cudamat* mean, cudamat* std, cudamat* patches, cudamat* width_offset, cudamat* height_offset,
+                           cudamat* flip, int img_width, int img_height, int patch_width, int patch_height);
 /* The crops of the same decoded image files as STORED BYTES (apps/image2hdf5.cc; convnet_amd/image2hdf5.py).  bytes / num_bytes,
  * image_table / num_images, taps / num_taps and case_table are stage_images_u8's, with the same meaning; case_table has num_cases rows.
  * rows is a plain device pointer to num_cases * 3 * img_height * img_width unsigned bytes: case n owns bytes n * 3 * H * W ..., planar
