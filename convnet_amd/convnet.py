@@ -164,6 +164,7 @@ class ConvNet(TrainLoopMixin):
                 self._check_batch_norm(l)
             self._check_slices(l)
             self._check_resample_edges(l)
+            self._check_gaussian_dropout(l)
             if not l.incoming_edge_:
                 self.input_layers_.append(l)
                 self.data_layers_.append(l)
@@ -198,6 +199,13 @@ class ConvNet(TrainLoopMixin):
     def PlanLayers(self):
         """Every layer's LayerPlan.  BuildNet ends with it; whoever changes a built graph by hand (a test) calls it again."""
         self.plan_ = {l: self._plan_layer(l) for l in self.layers_}
+        # Beside the plan: the hidden Gaussian-dropout layers whose backward pass must leave the state as the reference does, divided by
+        # the noise again, because something reads it afterwards — batch normalisation's derivative, or the undo of a max-pool or
+        # response-norm edge INTO the layer (both compare or combine with their output's state).  The unfused sequence restores it
+        # always; the fused undo only here, and elsewhere leaves the state alone
+        self.gaussian_restore_ = {l for l in self.layers_ if l.gaussian_dropout_ and not l.IsInput() and (
+            not l.FusedGaussianDropout() or l.UseBatchNormalization()
+            or any(isinstance(e, (MaxPoolEdge, ResponseNormEdge)) for e in l.incoming_edge_))}
         # the metric accumulates on the device (GetLoss returns None) only for one output on a fused output entry: the counter is one number
         self.metric_on_device_ = len(self.output_layers_) == 1 and self.plan_[self.output_layers_[0]].output_entry is not None
 
@@ -234,14 +242,20 @@ class ConvNet(TrainLoopMixin):
         # backward.  The reference applies dropout' and ReLU' after ALL outgoing edges have accumulated (src/convnet.cc:390-404), so they
         # ride in the ComputeDown epilogues only where every edge is the only reader of what it reads — the whole layer, or a slice of a
         # layer whose read slices are all of it; a max-pool undo masks but does not scale
+        # A Gaussian-dropout layer takes none of the three dropout fusions below: its derivative is multiplied by the noise and its
+        # activation's derivative taken at state / noise (Layer.ApplyDerivativeofGaussianDropout; a fused one stores no noise, so
+        # store_dropout_noise_ says nothing about it)
+        gaussian = l.gaussian_dropout_
         down_scale = None
-        if fused and hidden and l.is_relu and self._each_alone_and_all_of(l, [e.GetSourceSliceName() for e in l.outgoing_edge_]):
+        if (fused and hidden and l.is_relu and not gaussian
+                and self._each_alone_and_all_of(l, [e.GetSourceSliceName() for e in l.outgoing_edge_])):
             if all(e.can_fuse_mask and not e.IsBackPropBlocked() and not l.store_dropout_noise_
                    and not (isinstance(e, MaxPoolEdge) and scale != 1.0) for e in l.outgoing_edge_):
                 down_scale = scale
         return LayerPlan(fuse_relu=(l.is_relu and not bn) if fuse_up else None, bn_relu=(fused and l.is_relu) if bn else None,
-                         activate=activate, output_entry=entry, logistic_dropout=fused and logistic and not l.IsInput() and l.dropprob_ > 0,
-                         dropout_scale=scale, down_scale=down_scale, logistic_deriv=fused and logistic and hidden)
+                         activate=activate, output_entry=entry,
+                         logistic_dropout=fused and logistic and not l.IsInput() and l.dropprob_ > 0 and not gaussian,
+                         dropout_scale=scale, down_scale=down_scale, logistic_deriv=fused and logistic and hidden and not gaussian)
 
     @staticmethod
     def _each_alone_and_all_of(l, slice_names):
@@ -289,6 +303,19 @@ class ConvNet(TrainLoopMixin):
                     raise SystemExit(f"Error: Edge {e.GetName()}: the backward pass of UPSAMPLE overwrites the derivative of its source layer "
                                      f"{l.GetName()}, which edge {others[0]} also back-propagates into: its part would be lost.  Give the "
                                      "UPSAMPLE edge a source layer of its own, or set block_backprop on one of the two.")
+
+    @staticmethod
+    def _check_gaussian_dropout(l):
+        """Where a Gaussian-dropout layer can stand (Layer.__init__ has checked dropprob); anything else stops with the
+        reason."""
+        if not l.gaussian_dropout_:
+            return
+        name = l.GetName()
+        if l.IsOutput():
+            raise SystemExit(f"gaussian_dropout on layer {name}: not supported on an output layer (the prediction that is compared with "
+                             "the target would be the noised one)")
+        if type(l) not in (LinearLayer, ReLULayer, LogisticLayer):
+            raise SystemExit(f"gaussian_dropout on layer {name}: only LINEAR, RECTIFIED_LINEAR and LOGISTIC activations are supported")
 
     @staticmethod
     def _check_batch_norm(l):
@@ -417,6 +444,10 @@ class ConvNet(TrainLoopMixin):
             elif train and p.logistic_dropout:
                 l.GetState().LogisticDropout(l.dropprob_, p.dropout_scale)
                 continue
+            elif train and l.FusedGaussianDropout():
+                # the activation rides along unless an epilogue or bn_fprop_act has applied it (an input layer has none to apply)
+                l.ApplyGaussianDropout(l.gaussian_act if p.activate else 0)
+                continue
             elif p.activate:
                 l.ApplyActivation()
             l.ApplyDropout(train)
@@ -511,8 +542,17 @@ class ConvNet(TrainLoopMixin):
             p = self.plan_[l]
             for e in l.outgoing_edge_:
                 self._bprop_edge(e.GetDest(), l, e, fuse_mask=p.down_scale)
+            if l in self.gaussian_restore_ and self._in_train_step and self.side_stream_ is not None and self.overlap_wgrad_:
+                # the state is divided by the noise in place, and the weight gradients of this layer's outgoing edges read it on the
+                # side stream: order the rewrite after them (as for batch normalisation below)
+                ev = torch.cuda.Event()
+                ev.record(self.side_stream_)
+                torch.cuda.current_stream().wait_event(ev)
             if p.logistic_deriv:
                 l.GetDeriv().LogisticDerivScaled(l.GetState(), p.dropout_scale)   # dropout' and logistic' in one pass
+            elif l.FusedGaussianDropout():
+                if not l.IsInput():   # (an input layer takes no derivative; a Gaussian layer is never an output)
+                    l.ApplyDerivativeofGaussianDropout(l in self.gaussian_restore_)   # dropout' and the activation's derivative in one pass
             elif p.down_scale is None:   # else dropout' and ReLU' were applied by the edge's epilogue
                 l.ApplyDerivativeofDropout()
                 if not l.IsInput() and not l.IsOutput():

@@ -508,19 +508,24 @@ __global__ void softmax_ce_kernel(const float* __restrict__ mat, const float* __
 }
 
 // ---- Philox-4x32-10 (counter-based; key = (seed, call#), counter = element index / 4) -----------------
+// (USER only names an instantiation.  gauss_kernel takes one of its own, USER 1: with further callers of the SAME functions hipcc
+// selects other multiplies and another schedule for these rounds inside every rng_kernel — the same integers, but the listings of
+// kernels that were measured as they are would move.  One source, two instantiations, rng_kernel's listings unchanged.)
 struct Philox {
   unsigned k0, k1;
+  template <int USER = 0>
   __device__ void round(unsigned (&c)[4], unsigned ka, unsigned kb) const {
     const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
     const unsigned h0 = (unsigned)(p0 >> 32), l0 = (unsigned)p0, h1 = (unsigned)(p1 >> 32), l1 = (unsigned)p1;
     c[0] = h1 ^ c[1] ^ ka; c[1] = l1; c[2] = h0 ^ c[3] ^ kb; c[3] = l0;
   }
+  template <int USER = 0>
   __device__ void gen(unsigned long long idx, unsigned (&c)[4]) const {
     c[0] = (unsigned)idx; c[1] = (unsigned)(idx >> 32); c[2] = 0x9E3779B9u; c[3] = 0xBB67AE85u;
     unsigned ka = k0, kb = k1;
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
-      round(c, ka, kb);
+      round<USER>(c, ka, kb);
       ka += 0x9E3779B9u;
       kb += 0xBB67AE85u;
     }
@@ -531,6 +536,14 @@ __device__ __forceinline__ float u01(unsigned x) { return (float)(x >> 8) * (1.0
 
 __device__ __forceinline__ float sigmoid1(float x) { return 1.0f / (1.0f + expf(-x)); }   // eigenmat.cc:1389; exp overflow gives 1 / inf = 0
 
+// The four uniforms of one Philox quad to its four normals (Box-Muller, two pairs), in place: the one copy of the normal draw, shared
+// by rng_kernel<1> (fill_with_randn) and gauss_kernel below, whose noise must be fill_with_randn's bit for bit.
+__device__ __forceinline__ void box_muller(float (&u)[4]) {
+  const float r0 = sqrtf(-2.f * logf(1.f - u[0])), r1 = sqrtf(-2.f * logf(1.f - u[2]));
+  const float t0 = 6.2831853f * u[1], t1 = 6.2831853f * u[3];
+  u[0] = r0 * cosf(t0); u[1] = r0 * sinf(t0); u[2] = r1 * cosf(t1); u[3] = r1 * sinf(t1);
+}
+
 // MODE 0: uniform fill; 1: normal fill (Box-Muller); 2: dropout(p,val,scale) in place; 3: bernoulli(target = u < mat);
 // 4: relu then dropout(p, 0, scale); 5: sigmoid then dropout(p, 0, scale)
 template <int MODE>
@@ -540,11 +553,7 @@ __global__ void rng_kernel(float* __restrict__ out, const float* __restrict__ in
     unsigned c[4];
     ph.gen(q, c);
     float u[4] = {u01(c[0]), u01(c[1]), u01(c[2]), u01(c[3])};
-    if (MODE == 1) {
-      const float r0 = sqrtf(-2.f * logf(1.f - u[0])), r1 = sqrtf(-2.f * logf(1.f - u[2]));
-      const float t0 = 6.2831853f * u[1], t1 = 6.2831853f * u[3];
-      u[0] = r0 * cosf(t0); u[1] = r0 * sinf(t0); u[2] = r1 * cosf(t1); u[3] = r1 * sinf(t1);
-    }
+    if (MODE == 1) box_muller(u);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const size_t i = (q << 2) + e;
@@ -560,17 +569,162 @@ __global__ void rng_kernel(float* __restrict__ out, const float* __restrict__ in
 
 struct RngHost { unsigned long long seed, counter; };
 
+// the key of one call: (seed, the call counter's value)
+inline Philox philox_key(unsigned long long seed, unsigned long long counter) {
+  Philox ph;
+  ph.k0 = (unsigned)(seed * 0x9E3779B97F4A7C15ull >> 32) ^ (unsigned)counter;
+  ph.k1 = (unsigned)seed ^ (unsigned)(counter >> 32) ^ 0x85EBCA6Bu;
+  return ph;
+}
+
 template <int MODE>
 int rng_launch(rnd_struct* st, float* out, const float* in, size_t n, float p, float val, float scale) {
   if (!st || !st->dev_words) return ERROR_GENERIC;
   RngHost* h = reinterpret_cast<RngHost*>(st->dev_words);
-  Philox ph;
-  ph.k0 = (unsigned)(h->seed * 0x9E3779B97F4A7C15ull >> 32) ^ (unsigned)h->counter;
-  ph.k1 = (unsigned)h->seed ^ (unsigned)(h->counter >> 32) ^ 0x85EBCA6Bu;
+  const Philox ph = philox_key(h->seed, h->counter);
   h->counter++;
   if (n == 0) return 0;
   KernelTimer timer(MODE == 2 ? "rng_kernel<dropout>" : MODE == 4 ? "rng_kernel<relu_dropout>" : MODE == 5 ? "rng_kernel<logistic_dropout>" : "rng_kernel", "rng", 0.0, 4.0 * n * (in ? 2 : 1));
   hipLaunchKernelGGL(rng_kernel<MODE>, dim3(blocks_for(n / 4 + 1)), dim3(kThreads), 0, stream(), out, in, n, ph, p, val, scale);
+  return launch_status();
+}
+
+// ---- Gaussian dropout (src/layer.cc:369-377, 399-404) without a stored noise matrix ------------------------------------------------------
+// noise[i] = z[i] * stddev + 1 with z[i] what fill_with_randn writes to element i under the same key: the normal e of Philox quad i / 4,
+// quads counted from the FIRST element of the matrix or view.  OP 0 writes the noise; OP 1 is the forward pass in place,
+// a = clip(act(a) * noise); OP 2 the backward pass, a = act'(a * noise, b / noise) [b = b / noise when `restore`], drawing the forward
+// pass's noise again from its call id.
+// The body moves 16 bytes per lane and array and starts at the first 16-byte boundary, `head` (0..3) floats in: lane j holds elements
+// head + 4j .. head + 4j + 3, which lie in quad j and, when head != 0, in quad j + 1 — the two groupings of four do not coincide, so
+// such a view draws both quads and shifts (twice the draws, on views that start off a boundary only).  The head and the tail, six
+// floats at the most, go one element per lane.  Arrays that disagree in their offset (`vec` 0) run the same loop from element 0 with
+// four 4-byte accesses per array.
+struct GaussArgs {
+  float* a;        // OP 0: target; 1: the state; 2: the derivative
+  float* b;        // OP 2: the state
+  size_t n, head;
+  Philox ph;
+  float stddev, max_act;
+  int vec, restore;
+};
+__device__ __forceinline__ void gauss_quad(const Philox& ph, size_t q, float (&z)[4]) {
+  unsigned c[4];
+  ph.gen<1>(q, c);   // (an instantiation of its own: see Philox)
+  z[0] = u01(c[0]); z[1] = u01(c[1]); z[2] = u01(c[2]); z[3] = u01(c[3]);
+  box_muller(z);
+}
+template <int OP, int ACT>
+__device__ __forceinline__ void gauss_one(const GaussArgs& g, float z, float& a, float& b) {
+#pragma clang fp contract(off)
+  const float zs = z * g.stddev;
+  const float nz = zs + 1.0f;   // mult_by_scalar, then add_scalar: two roundings
+  if (OP == 0) {
+    a = nz;
+  } else if (OP == 1) {
+    float x = a;
+    if (ACT == 1) x = x > 0.f ? x : 0.f;
+    if (ACT == 2) x = sigmoid1(x);
+    x = x * nz;
+    if (g.max_act > 0.f) x = x > g.max_act ? g.max_act : (x < -g.max_act ? -g.max_act : x);
+    a = x;
+  } else {
+    const float d = a * nz;
+    const float s = b / nz;
+    if (ACT == 0) a = d;
+    if (ACT == 1) a = s > 0.f ? d : 0.f * d;
+    if (ACT == 2) {
+      const float dy = d * s;
+      const float om = 1.0f - s;
+      a = dy * om;
+    }
+    b = s;
+  }
+}
+template <int OP, int ACT>
+__global__ void gauss_kernel(const GaussArgs g) {
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  const size_t n4 = (g.n - g.head) >> 2;
+  float* const pa = g.a + g.head;
+  float* const pb = OP == 2 ? g.b + g.head : nullptr;
+  for (size_t j = tid; j < n4; j += stride) {
+    float w[8];
+    gauss_quad(g.ph, j, reinterpret_cast<float(&)[4]>(w[0]));
+    if (g.head) {   // (the same in every lane)
+      gauss_quad(g.ph, j + 1, reinterpret_cast<float(&)[4]>(w[4]));
+      if (g.head & 1) {
+#pragma unroll
+        for (int k = 0; k < 7; ++k) w[k] = w[k + 1];
+      }
+      if (g.head & 2) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) w[k] = w[k + 2];
+      }
+    }
+    f32x4 a, b;
+    if (g.vec) {
+      if (OP != 0) a = reinterpret_cast<const f32x4*>(pa)[j];
+      if (OP == 2) b = reinterpret_cast<const f32x4*>(pb)[j];
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (OP != 0) a[e] = pa[4 * j + e];
+        if (OP == 2) b[e] = pb[4 * j + e];
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float x = OP != 0 ? a[e] : 0.f, y = OP == 2 ? b[e] : 0.f;
+      gauss_one<OP, ACT>(g, w[e], x, y);
+      a[e] = x;
+      b[e] = y;
+    }
+    if (g.vec) {
+      reinterpret_cast<f32x4*>(pa)[j] = a;
+      if (OP == 2 && g.restore) reinterpret_cast<f32x4*>(pb)[j] = b;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        pa[4 * j + e] = a[e];
+        if (OP == 2 && g.restore) pb[4 * j + e] = b[e];
+      }
+    }
+  }
+  const size_t rest = g.n - (n4 << 2);   // head + tail
+  for (size_t r = tid; r < rest; r += stride) {
+    const size_t i = r < g.head ? r : (n4 << 2) + r;
+    float z[4];
+    gauss_quad(g.ph, i >> 2, z);
+    const int e = (int)(i & 3);
+    const float zi = e == 0 ? z[0] : e == 1 ? z[1] : e == 2 ? z[2] : z[3];
+    float x = OP != 0 ? g.a[i] : 0.f, y = OP == 2 ? g.b[i] : 0.f;
+    gauss_one<OP, ACT>(g, zi, x, y);
+    g.a[i] = x;
+    if (OP == 2 && g.restore) g.b[i] = y;
+  }
+}
+
+// `a` and `b` (OP 2 only) hold n floats on the device; the key is (the state's seed, call_id)
+template <int OP>
+int gauss_launch(const rnd_struct* st, unsigned long long call_id, float* a, float* b, size_t n, float stddev, float max_act, int act, int restore) {
+  if (n == 0) return 0;
+  GaussArgs g{a, b, n, 0, philox_key(reinterpret_cast<const RngHost*>(st->dev_words)->seed, call_id), stddev, max_act, 1, restore};
+  const uintptr_t off = reinterpret_cast<uintptr_t>(a) & 15;
+  g.vec = (off & 3) == 0 && (OP != 2 || (reinterpret_cast<uintptr_t>(b) & 15) == off);
+  g.head = g.vec ? ((16 - off) & 15) >> 2 : 0;
+  if (g.head > n) g.head = n;
+  // bytes: the noise is written; the state read and written; derivative and state read, the derivative (and the state) written
+  const double arrays = OP == 0 ? 1 : OP == 1 ? 2 : restore ? 4 : 3;
+  KernelTimer timer(OP == 0 ? "gauss_kernel<noise>" : OP == 1 ? "gauss_kernel<dropout>" : "gauss_kernel<undo>", "gaussian_dropout", 0.0, 4.0 * n * arrays);
+  const dim3 grid(blocks_for(n / 4 + 1)), block(kThreads);
+  if constexpr (OP == 0) {
+    hipLaunchKernelGGL((gauss_kernel<0, 0>), grid, block, 0, stream(), g);
+  } else {
+    switch (act) {
+      case 0: hipLaunchKernelGGL((gauss_kernel<OP, 0>), grid, block, 0, stream(), g); break;
+      case 1: hipLaunchKernelGGL((gauss_kernel<OP, 1>), grid, block, 0, stream(), g); break;
+      default: hipLaunchKernelGGL((gauss_kernel<OP, 2>), grid, block, 0, stream(), g); break;
+    }
+  }
   return launch_status();
 }
 
@@ -1369,6 +1523,36 @@ int dropout(rnd_struct* st, cudamat* mat, float dropprob, float val, float scale
 }
 int relu_dropout(rnd_struct* st, cudamat* mat, float dropprob, float scale) {
   return rng_launch<4>(st, mat->data_device, mat->data_device, numel(mat), dropprob, 0.f, scale);
+}
+
+// ---- Gaussian dropout (include/convnet_hip.h).  Every check comes before the counter moves or anything is launched. ---------------------
+static_assert(sizeof(size_t) == sizeof(unsigned long long), "a call id travels as size_t");
+namespace {
+int gauss_check(const rnd_struct* st, const cudamat* a, const cudamat* b, int act) {
+  if (!st || !st->dev_words) return ERROR_GENERIC;
+  if (b) {
+    if (int rc = same_shape_check(a, b, nullptr)) return rc;
+  } else if (!a->on_device) {
+    return ERROR_NOT_ON_DEVICE;
+  }
+  if (act < 0 || act > 2 || numel(a) > (size_t)INT_MAX) return ERROR_UNSUPPORTED;
+  return 0;
+}
+}  // namespace
+int gaussian_dropout(rnd_struct* st, cudamat* mat, float stddev, float max_act, int act, void* call_id) {
+  if (int rc = gauss_check(st, mat, nullptr, act)) return rc;
+  RngHost* h = reinterpret_cast<RngHost*>(st->dev_words);
+  const unsigned long long id = h->counter++;   // one counter value per call, as fill_with_randn takes
+  if (call_id) *static_cast<unsigned long long*>(call_id) = id;
+  return gauss_launch<1>(st, id, mat->data_device, nullptr, numel(mat), stddev, max_act, act, 0);
+}
+int gaussian_dropout_noise(rnd_struct* st, size_t call_id, float stddev, cudamat* target) {
+  if (int rc = gauss_check(st, target, nullptr, 0)) return rc;
+  return gauss_launch<0>(st, call_id, target->data_device, nullptr, numel(target), stddev, 0.f, 0, 0);
+}
+int gaussian_dropout_undo(rnd_struct* st, size_t call_id, float stddev, cudamat* deriv, cudamat* state, int act, int restore_state) {
+  if (int rc = gauss_check(st, deriv, state, act)) return rc;
+  return gauss_launch<2>(st, call_id, deriv->data_device, state->data_device, numel(deriv), stddev, 0.f, act, restore_state != 0);
 }
 
 }  // extern "C"

@@ -4,8 +4,11 @@ that edges read (``source_slice``) or write (``dest_slice``) on their own — gr
 CHWN layout a channel range is a contiguous column range, so a slice is a get_slice view of the state and of the derivative with its
 own Shape4D and its own add-or-overwrite flags; the slices lie in NAME order from column 0 (the reference keeps them in std::maps), a
 non-zero ``num_channels`` of the layer itself sits behind the last slice.  Layer-level passes (activation, dropout, loss) stay on the
-whole layer.  DESIGN.md §2.9 has the supported and the refused sets.  Gaussian dropout and the model-parallel state copies are out of
-scope."""
+whole layer.  DESIGN.md §2.9 has the supported and the refused sets.  Gaussian dropout (``gaussian_dropout`` with ``dropprob`` as the
+noise's standard deviation, ``max_act_gaussian_dropout``) runs on LINEAR, RECTIFIED_LINEAR and LOGISTIC hidden and
+input layers: unfused as the reference's call sequence on a stored noise matrix — allocated for every such layer, which the reference
+forgets for most classes — and fused as one pass forward and one backward that redraws the noise from the forward pass's RNG call id.
+The model-parallel state copies are out of scope."""
 import numpy as np
 
 from .loss_functions import LossFunction
@@ -54,9 +57,22 @@ class Layer:
         self.deriv_ = Matrix()
         self.data_ = Matrix()
         self.dropout_noise_ = Matrix()
+        # Gaussian dropout (src/layer.cc:369-377, 399-404): dropprob is the noise's standard deviation.  What the layer's place in the
+        # graph decides (no output layer, the layer class) is checked by ConvNet._check_gaussian_dropout
+        self.max_act_gaussian_dropout_ = config.max_act_gaussian_dropout
+        self.gaussian_call_id_ = None   # fused: the RNG call id of the last training forward pass, from which the backward pass redraws
         if self.gaussian_dropout_:
-            # (the reference runs it on a noise matrix it never allocates for every layer class that clears store_dropout_noise_)
-            raise SystemExit(f"gaussian_dropout on layer {self.name_} is out of hot-path scope")
+            if not np.isfinite(self.dropprob_):
+                raise SystemExit(f"gaussian_dropout on layer {self.name_}: dropprob (the noise's standard deviation) is {self.dropprob_}, "
+                                 "not a finite number")
+            if not self.dropprob_ > 0:
+                # (the reference silently does nothing)
+                raise SystemExit(f"gaussian_dropout on layer {self.name_}: dropprob is {self.dropprob_}; it is the standard deviation of "
+                                 "the noise and must be positive")
+        elif self.max_act_gaussian_dropout_ > 0:
+            # (ignored silently by the reference)
+            raise SystemExit(f"max_act_gaussian_dropout on layer {self.name_} is set ({self.max_act_gaussian_dropout_}) without "
+                             "gaussian_dropout: it clips the state after Gaussian noise only")
         # slices: src/layer.cc:66-73.  name -> channels in NAME order (std::map), which is also the order of their columns
         self.slice_channels_ = {}
         for s in config.layer_slice:
@@ -197,7 +213,12 @@ class Layer:
         self.deriv_.AllocateGPUMemory(batch_size, num_pixels * self.num_channels_, self.name_ + " deriv")
         for m in (self.state_, self.deriv_):
             m.SetShape4D(batch_size, self.image_size_x_, self.image_size_y_, self.num_channels_ * self.image_size_t_)
-        if self.is_input_:
+        if self.gaussian_dropout_:
+            # The unfused sequence multiplies by a stored noise matrix and divides by it again, whatever the layer's class, input layers
+            # included (the reference allocates none for the classes that clear the flag, and then runs on an empty matrix); the fused
+            # entries draw the noise again from the call id and store nothing
+            self.store_dropout_noise_ = not self.FusedGaussianDropout()
+        elif self.is_input_:
             self.store_dropout_noise_ = False
         if self.store_dropout_noise_:
             self.dropout_noise_.AllocateGPUMemory(batch_size, num_pixels * self.num_channels_, self.name_ + " dropout")
@@ -298,12 +319,43 @@ class Layer:
             self.ApplyDropoutAtTestTime()
 
     def TrainDropoutScale(self):
-        """What the units kept at train time are scaled by: 1 / (1 - p) with dropout and scale-up at train time, else 1."""
-        return 1.0 / (1 - self.dropprob_) if (self.dropprob_ > 0 and self.dropout_scale_up_at_train_time_) else 1.0
+        """What the units kept at train time are scaled by: 1 / (1 - p) with binary dropout and scale-up at train time, else 1 (Gaussian
+        noise has mean 1)."""
+        binary = self.dropprob_ > 0 and not self.gaussian_dropout_
+        return 1.0 / (1 - self.dropprob_) if (binary and self.dropout_scale_up_at_train_time_) else 1.0
+
+    def FusedGaussianDropout(self):
+        """Whether this layer's Gaussian dropout runs through the fused pair of entries (the fused host's choice for every Gaussian
+        layer: measured faster than the sequences it replaces at both shapes of profiles/gaussian_dropout_bench.json) —
+        the one place that decides it."""
+        return self.fused and self.gaussian_dropout_
+
+    def ApplyGaussianDropout(self, act):
+        """Fused host: Gaussian dropout in one pass, with the activation ``act`` (0 when something before has applied it, else
+        ``gaussian_act``) in front; the call id stays with the layer for ApplyDerivativeofGaussianDropout."""
+        self.gaussian_call_id_ = self.state_.GaussianDropout(self.dropprob_, self.max_act_gaussian_dropout_, act)
+
+    def ApplyDerivativeofGaussianDropout(self, restore_state):
+        """Fused host, hidden layers: dropout' and the activation's derivative at state / noise in one pass, the noise drawn again from the
+        forward pass's call id.  Without ``restore_state`` the state is only read, so a weight gradient reading it on another stream
+        needs no ordering; with it the state is left as the reference leaves it, state / noise, for whoever reads it afterwards
+        (ConvNet.gaussian_restore_)."""
+        self.deriv_.GaussianDropoutUndo(self.gaussian_call_id_, self.dropprob_, self.state_, self.gaussian_act, restore_state)
 
     def ApplyDropoutAtTrainTime(self):
         # src/layer.cc:367-397
         if self.dropprob_ > 0:
+            if self.gaussian_dropout_:
+                if self.FusedGaussianDropout():
+                    self.ApplyGaussianDropout(0)
+                    return
+                self.dropout_noise_.FillWithRandn()
+                self.dropout_noise_.Mult(self.dropprob_)
+                self.dropout_noise_.Add(1)
+                self.state_.Mult(self.dropout_noise_)
+                if self.max_act_gaussian_dropout_ > 0:
+                    self.state_.UpperBoundMod(self.max_act_gaussian_dropout_)   # |state| <= max_act
+                return
             scale = self.TrainDropoutScale()
             if self.store_dropout_noise_:
                 self.dropout_noise_.SampleBernoulli(1 - self.dropprob_)
@@ -315,7 +367,12 @@ class Layer:
     def ApplyDerivativeofDropout(self):
         # src/layer.cc:399-413
         if self.dropprob_ > 0:
-            if self.store_dropout_noise_:
+            if self.gaussian_dropout_:
+                # unfused (the fused host calls ApplyDerivativeofGaussianDropout instead).  An input layer takes no derivative
+                if not self.is_input_:
+                    self.deriv_.Mult(self.dropout_noise_)
+                    self.state_.Divide(self.dropout_noise_)   # the activation's derivative is taken at the state before the noise
+            elif self.store_dropout_noise_:
                 self.deriv_.Mult(self.dropout_noise_)
             elif self.dropout_scale_up_at_train_time_:
                 self.deriv_.Mult(self.TrainDropoutScale())
@@ -339,6 +396,7 @@ class Layer:
 
 class LinearLayer(Layer):
     is_relu = False
+    gaussian_act = 0   # the activation's code in gaussian_dropout / gaussian_dropout_undo (include/convnet_hip.h)
 
     def ApplyActivation(self):
         pass  # linear: nothing to do (src/layer.cc:530-532)
@@ -355,6 +413,7 @@ class LinearLayer(Layer):
 
 class ReLULayer(LinearLayer):
     is_relu = True
+    gaussian_act = 1
 
     def __init__(self, config):
         super().__init__(config)
@@ -396,8 +455,10 @@ class SoftmaxDistLayer(SoftmaxLayer):
 
 class LogisticLayer(Layer):
     """src/layer.cc:586-602.  The dropout mask is not stored: ApplyDerivativeofDropout scales the derivative by 1 / (1 - p) and the
-    logistic derivative y (1 - y) is then taken at the dropout-SCALED state, exactly 0 for a dropped unit — the reference's quirk, kept."""
+    logistic derivative y (1 - y) is then taken at the dropout-SCALED state, exactly 0 for a dropped unit — the reference's quirk, kept.
+    (Gaussian dropout stores or redraws its noise like every other class: Layer.AllocateMemory.)"""
     is_relu = False
+    gaussian_act = 2
 
     def __init__(self, config):
         super().__init__(config)

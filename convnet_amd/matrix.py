@@ -506,6 +506,24 @@ class Matrix:
         """Fused LowerBound(0) + Dropout(p, 0, scale) (one pass; same arithmetic)."""
         _chk(lib.relu_dropout(ctypes.byref(Matrix._rnd), self.GetMat(), float(dropprob), float(scale_factor)), "relu_dropout")
 
+    def GaussianDropout(self, stddev, max_act, act):
+        """Fused [activation,] FillWithRandn, Mult(stddev), Add(1), Mult(noise)[, UpperBoundMod(max_act)] on this matrix without a
+        noise matrix (one pass; same bits).  ``act``: 0 none, 1 ReLU, 2 logistic.  Returns the call id the noise was drawn under."""
+        call_id = ctypes.c_ulonglong(0)
+        _chk(lib.gaussian_dropout(ctypes.byref(Matrix._rnd), self.GetMat(), float(stddev), float(max_act), int(act),
+                                  ctypes.byref(call_id)), "gaussian_dropout")
+        return call_id.value
+
+    def GaussianDropoutNoise(self, call_id, stddev):
+        """This matrix = the noise GaussianDropout multiplied by under ``call_id`` (the RNG call counter stays where it is)."""
+        _chk(lib.gaussian_dropout_noise(ctypes.byref(Matrix._rnd), int(call_id), float(stddev), self.GetMat()), "gaussian_dropout_noise")
+
+    def GaussianDropoutUndo(self, call_id, stddev, state, act, restore_state):
+        """This derivative through the Gaussian dropout of ``call_id`` and the activation ``act`` at ``state`` / noise: fused Mult(noise),
+        state.Divide(noise) and the activation's derivative (one pass; same bits).  ``state`` is rewritten only with ``restore_state``."""
+        _chk(lib.gaussian_dropout_undo(ctypes.byref(Matrix._rnd), int(call_id), float(stddev), self.GetMat(), state.GetMat(), int(act),
+                                       int(bool(restore_state))), "gaussian_dropout_undo")
+
     def FillWithRand(self):
         _chk(lib.fill_with_rand(ctypes.byref(Matrix._rnd), self.GetMat()), "Could not fill with rand")
 

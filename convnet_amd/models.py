@@ -25,6 +25,8 @@ text so they can also be written to disk and fed to the reference's own binaries
                      SQUARED_ERROR against a target stream.
 * ``skip_sum_small()`` — a small net whose input goes through an ``RGBTOYUV`` edge and in which a coarse branch upsampled by 4 and a
                      1x1 branch sum into one layer.
+* ``gaussian_dropout_small()`` — a small net with Gaussian dropout (``gaussian_dropout``, ``max_act_gaussian_dropout``) on a ReLU conv
+                     layer, a ReLU FC layer and a LOGISTIC FC layer.
 tests/test_models.py checks the first two against the reference's files when they are mounted.
 """
 
@@ -319,6 +321,27 @@ def softdist_small(image_size=12, num_classes=10, dropprob=0.0, grad_check=False
     out = _layer("output", num_classes, "SOFTMAX_DIST", extra="  loss_function: CROSS_ENTROPY_MULTINOMIAL_DISTRIBUTED\n"
                  "  performance_metric: CROSS_ENTROPY_MULTINOMIAL_DISTRIBUTED\n")
     return _small_head_trunk("softdist_small", "RECTIFIED_LINEAR", dropprob, image_size, out, 1.0, _gc(grad_check, 6))
+
+
+def _gaussian(stddev, max_act=None):
+    """``extra`` of _layer for Gaussian dropout; the standard deviation itself is the layer's ``dropprob``."""
+    return "  gaussian_dropout: true\n" + (f"  max_act_gaussian_dropout: {max_act}\n" if max_act is not None else "")
+
+
+def gaussian_dropout_small(image_size=12, num_classes=10, relu=True, pool="MAXPOOL", batch_normalize=False):
+    """A small net with multiplicative Gaussian noise N(1, dropprob^2) on three hidden layers: conv3p1/16 ReLU (0.3) -> max3s2 ->
+    fc32 ReLU (0.5, clipped to |x| <= 10 by ``max_act_gaussian_dropout``) -> fc24 LOGISTIC (0.2) -> softmax.  Every noised layer has
+    one conv or FC edge in with a shared bias, so the fused host's bias / ReLU epilogues apply in front of the noise.  ``relu=False``
+    makes the first two LINEAR, ``pool`` can be AVERAGE_POOL, ``batch_normalize`` batch-normalises conv1."""
+    act = "RECTIFIED_LINEAR" if relu else "LINEAR"
+    s = _header("gaussian_dropout_small") + (_BN_DEFAULTS if batch_normalize else "")
+    s += _layer("input", 3, size=image_size)
+    s += _layer("conv1", 16, act, 0.3, extra=_gaussian(0.3) + (_BN if batch_normalize else "")) + _layer("pool1", 16)
+    s += _layer("fc2", 32, act, 0.5, extra=_gaussian(0.5, 10)) + _layer("fc3", 24, "LOGISTIC", 0.2, extra=_gaussian(0.2))
+    s += _layer("output", num_classes, "SOFTMAX")
+    s += _conv("input", "conv1", 3, 1, 1) + _pool("conv1", "pool1", 3, 2, kind=pool)
+    s += _fc("pool1", "fc2") + _fc("fc2", "fc3") + _fc("fc3", "output")
+    return s
 
 
 def _slices(**channels):

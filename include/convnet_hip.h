@@ -714,6 +714,32 @@ int logistic_ce_grad_correct(cudamat* logits, cudamat* targets, cudamat* probs, 
                              float deriv_scale);
 int softmax_dist_ce_grad(cudamat* logits, cudamat* targets, cudamat* probs, cudamat* deriv, cudamat* ce_accum, float deriv_scale,
                          float tiny);
+/* Gaussian dropout (Layer with dropprob > 0 and gaussian_dropout, src/layer.cc:369-377 and 399-404) in one pass each way and without a
+ * stored noise matrix: the backward pass draws the forward pass's noise again from the counter value that call used (its call id).
+ *   z[i]     = the float fill_with_randn writes to element i of a matrix of the same element count when the state's call counter
+ *              equals the call id: same key, Philox quad i / 4 counted from the first element of the matrix or view, same Box-Muller.
+ *   noise[i] = (z[i] * stddev) + 1, two separately rounded fp32 operations.  stddev is the layer's dropprob: a standard deviation.
+ *  gaussian_dropout      : takes the counter's value as this call's id, writes it to *call_id (call_id: NULL, or the address of an
+ *                          unsigned 64-bit integer) and advances the counter once, as fill_with_randn does.  In place:
+ *                          x = act(mat[i]) with act 0 the identity, 1 lower_bound_scalar(0), 2 apply_sigmoid's arithmetic;
+ *                          x = x * noise[i]; when max_act > 0, upper_bound_mod_scalar(max_act).  Bit for bit what the sequence
+ *                          [activation entry,] fill_with_randn, mult_by_scalar, add_scalar, mult_elementwise[, upper_bound_mod_scalar]
+ *                          leaves in the state.
+ *  gaussian_dropout_noise: target = noise of the given call id — the matrix that sequence holds in its noise matrix.  The seed comes
+ *                          from rnd_state; the counter is neither read nor advanced.
+ *  gaussian_dropout_undo : the counter is untouched.  n = noise[i]; d = deriv[i] * n; s = state[i] / n (IEEE division, as
+ *                          divide_elementwise); deriv[i] = d (act 0), apply_rectified_linear_deriv(d, s) (act 1) or
+ *                          apply_logistic_deriv(d, s) with its three roundings (act 2): Layer::ApplyDerivativeofDropout followed by the
+ *                          layer's ApplyDerivativeOfActivation at the restored state.  restore_state != 0 also writes s to state[i]
+ *                          (the reference's bits); 0 leaves the state untouched.
+ * One launch per call, no workspace, no atomics, the same bits from call to call.  ERROR_GENERIC for a NULL or uninitialised rnd_state,
+ * ERROR_NOT_ON_DEVICE, ERROR_INCOMPATIBLE_DIMENSIONS when deriv and state differ in shape, ERROR_UNSUPPORTED for act outside 0..2 and
+ * for more than INT_MAX (2^31 - 1) floats; nothing is launched and no counter moves on an error.  (A call id is a 64-bit counter value;
+ * it travels as size_t, which is 64 bits wide on every platform this library builds for.) */
+int gaussian_dropout(rnd_struct* rnd_state, cudamat* mat, float stddev, float max_act, int act, void* call_id);
+int gaussian_dropout_noise(rnd_struct* rnd_state, size_t call_id, float stddev, cudamat* target);
+int gaussian_dropout_undo(rnd_struct* rnd_state, size_t call_id, float stddev, cudamat* deriv, cudamat* state, int act,
+                          int restore_state);
 /* Batch normalisation of a layer's state in place, `state` read as (numel / C, C) with C = numel(gamma) (layer.cc:454: Reshape(-1, C));
  * gamma, beta, mu, sigma, batch_mu, batch_sigma are C-float device vectors.
  *  bn_fprop_act  : Layer::ApplyBatchNormalization(train) (src/layer.cc:452-480) [+ ReLULayer::ApplyActivation, layer.cc:549-551 when
